@@ -7,6 +7,12 @@ extraction of B+1 frames (frame 0 is the halo that gives frame 1 its LastFrame) 
 SearchByProjection calls (th = 15, retried at 30 below 20 matches, Tracking.cc:947-958).
 Only the B matched frames are counted.
 
+A plain run (python bench.py --gpus 1 --steps N --warmup W) sets up, warms up, times the N steps
+and prints the result line; --dump-outputs DIR also writes a fixed sample of what the last timed
+step computed.  Everything else the line can carry (HIP-event per-kernel times and roofline, the
+oracle parity sample, per-call extras, the CPU baseline, the PCIe-inclusive rate) runs only with
+--full.
+
 Multi-GPU (python -m torch.distributed.run --nproc-per-node N bench.py --gpus N): one
 process per GPU, each with its own batch (frames are independent; no data-path collective,
 scaling "weak").  torch.distributed (gloo) is used only for the barrier and the max-over-
@@ -845,6 +851,16 @@ class DryRunPipeline:
         out = [(np.zeros(1000, KEYPOINT_DTYPE), np.zeros((1000, 32), np.uint8))] * self.F
         return out, None, [None] + [750] * (self.F - 1)
 
+    def frame(self, f, track=False):
+        from coeb_front import KEYPOINT_DTYPE
+        out = dict(kps=np.zeros(1000, KEYPOINT_DTYPE), desc=np.zeros((1000, 32), np.uint8), nmatch=750,
+                   match=np.full(1000, -1, np.int32))
+        if track:
+            out.update(T1=np.eye(4, dtype=np.float32), T=np.eye(4, dtype=np.float32), nin1=0, ninliers=0,
+                       nmatches_map=0, nlocal=0, state=0, local_match=np.full(1000, -1, np.int32),
+                       outlier=np.zeros(1000, np.uint8))
+        return out
+
     def close(self):
         pass
 
@@ -962,11 +978,21 @@ def parse_args(argv=None):
                          "(shared), or none (off); default: the config's")
     ap.add_argument("--streams", type=int, default=1,
                     help="HIP streams the batch is chunked over (kernels of different chunks overlap)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="skip HIP-event kernel timing")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the PCIe-inclusive host-buffer measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs beyond the headline figure: the HIP-event "
+                         "per-kernel pass and roofline, the oracle parity sample, the per-call extras, the CPU "
+                         "baseline and the PCIe-inclusive measurement (each can be dropped with its --no-... option). "
+                         "Without --full a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed (a fixed sample of the counted "
+                         "frames' keypoints, descriptors and matches, for config D also the tracking records) as "
+                         "DIR/<name>.npy, float32 / float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity sample")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip HIP-event kernel timing")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the PCIe-inclusive host-buffer measurement")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the per-call timing of the other entry points (local map, relocalisation, pose)")
+                    help="with --full: skip the per-call timing of the other entry points (local map, "
+                         "relocalisation, pose)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: exercise the rank/timing/JSON plumbing with a stand-in pipeline (tests)")
     return ap.parse_args(argv)
@@ -974,6 +1000,11 @@ def parse_args(argv=None):
 
 def main():
     args = parse_args()
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
+    if not args.full:
+        # a plain run times the steps and nothing else: every other leg belongs to --full
+        args.no_cpu_baseline = args.no_profile = args.no_e2e = args.no_extras = True
     if args.global_frames is None and args.config == "B":
         args.global_frames = 512
     if args.batch is None:
@@ -1114,6 +1145,8 @@ def rank_main(ranks, args):
     t1 = time.perf_counter()
     ranks.barrier()
     elapsed = ranks.max(t1 - t0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, bps, subs, chain, rank, world)
 
     # per-kernel device time (rank 0): a separate pass with HIP events, kernels serialised on
     # one stream so each event pair brackets exactly one launch
@@ -1257,6 +1290,59 @@ def rank_main(ranks, args):
         line["pcie_inclusive"] = e2e
         print(json.dumps(line), flush=True)
     ranks.close()
+
+
+DUMP_FRAMES = 32          # counted frames sampled per pipeline by --dump-outputs
+DUMP_SEED = 20240229
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, bps, subs, chain, rank=0, world=1):
+    """--dump-outputs: what the timed path's last step left in every pipeline, for a fixed seeded
+    sample of DUMP_FRAMES counted frames per pipeline (all of them when there are fewer), written as
+    <path>/<name>.npy (<name>_rank<r>.npy with more than one rank).  Per sampled frame, in pipeline
+    then frame order: its global frame index, keypoint count and SearchByProjection count (float64,
+    one row per frame); the keypoint records (x, y, size, angle, response, octave, class_id), the
+    descriptor bytes and the match index of every keypoint (float32, the frames' rows concatenated;
+    every value is exact in float32).  Config D adds the configs[4] loop's records: both poses, the
+    inlier / nmatchesMap / local-match counts and state per frame, local-match indices and outlier
+    flags per keypoint."""
+    rng = np.random.default_rng(DUMP_SEED)
+    per_frame = dict(frame_index=[], keypoint_count=[], match_count=[])
+    per_kp = dict(keypoints=[], descriptors=[], matches=[])
+    if chain:
+        per_frame.update(pose_motion_model=[], inliers_motion_model=[], pose=[], inliers=[], matches_map=[],
+                         local_match_count=[], state=[])
+        per_kp.update(local_matches=[], outliers=[])
+    for bp, (first, F, nm) in zip(bps, subs):
+        counted = np.arange(F - nm, F)
+        for f in np.sort(rng.choice(counted, size=min(nm, DUMP_FRAMES), replace=False)):
+            got = bp.frame(int(f), track=chain)
+            k = got["kps"]
+            per_frame["frame_index"].append(first + int(f))
+            per_frame["keypoint_count"].append(len(k))
+            per_frame["match_count"].append(got["nmatch"])
+            per_kp["keypoints"].append(np.stack([k[n].astype(np.float32) for n in k.dtype.names], 1).reshape(-1, 7))
+            per_kp["descriptors"].append(got["desc"].astype(np.float32).reshape(-1, 32))
+            per_kp["matches"].append(got["match"].astype(np.float32))
+            if chain:
+                per_frame["pose_motion_model"].append(got["T1"])
+                per_frame["inliers_motion_model"].append(got["nin1"])
+                per_frame["pose"].append(got["T"])
+                per_frame["inliers"].append(got["ninliers"])
+                per_frame["matches_map"].append(got["nmatches_map"])
+                per_frame["local_match_count"].append(got["nlocal"])
+                per_frame["state"].append(got["state"])
+                per_kp["local_matches"].append(got["local_match"].astype(np.float32))
+                per_kp["outliers"].append(got["outlier"].astype(np.float32))
+    arrays = {n: np.asarray(v, np.float32 if n.startswith("pose") else np.float64) for n, v in per_frame.items()}
+    arrays.update({n: np.concatenate(v) for n, v in per_kp.items()})
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes sampled, above the %d allowed" % (total, DUMP_MAX_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(os.path.join(path, n + (".npy" if world == 1 else "_rank%d.npy" % rank)), a)
 
 
 def _thread_rank_type():

@@ -204,3 +204,52 @@ def test_bench_side_stream_option():
         assert out.returncode == 0, out.stderr[-2000:]
         rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
         assert rec["config"]["side_stream"] == want
+
+
+def test_bench_plain_run_times_only_and_full_adds_the_rest():
+    """A plain run carries the headline fields and none of the legs that take runs of their own;
+    --full brings the per-kernel pass back (the dry run's stand-in reports one kernel)."""
+    out, lines = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4", "--dry-run"], timeout=120)
+    assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["unit"] == "frames/s" and rec["dtype"] == "u8"
+    assert rec["higher_is_better"] is True and rec["ms_per_step"] >= 2.0          # the stand-in sleeps 2 ms per step
+    assert abs(rec["value"] - 4 * 3 / (rec["ms_per_step"] * 3 / 1e3)) / rec["value"] < 1e-3
+    assert rec["kernels_profiled_steps"] == 0 and rec["kernels_ms_per_step"] == {} and rec["roofline"] is None
+    for leg in ("parity_sample", "extras", "cpu_baseline"):
+        assert leg not in rec
+    assert rec["pcie_inclusive"] is None
+    out, lines = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4", "--dry-run", "--full"],
+                        timeout=120)
+    assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["kernels_profiled_steps"] == 3 and "k_fast" in rec["kernels_ms_per_step"] and rec["roofline"]
+    out, _ = _bench(["--steps", "0", "--dry-run"], timeout=120)
+    assert out.returncode != 0 and "--steps" in out.stderr
+
+
+@pytest.mark.parametrize("config", ["A", "D"])
+def test_bench_dump_outputs_layout(tmp_path, config):
+    """--dump-outputs writes float32 / float64 .npy arrays of the sampled counted frames: one row per
+    frame in the per-frame arrays, the frames' keypoint rows concatenated in the others."""
+    import numpy as np
+    d = tmp_path / "dump"
+    out, lines = _bench(["--config", config, "--steps", "2", "--warmup", "0", "--batch", "80", "--pipelines", "2",
+                         "--dry-run", "--dump-outputs", str(d)], timeout=120)
+    assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]
+    arr = {p.stem: np.load(p) for p in d.iterdir()}
+    want = {"frame_index", "keypoint_count", "match_count", "keypoints", "descriptors", "matches"}
+    if config == "D":
+        want |= {"pose_motion_model", "inliers_motion_model", "pose", "inliers", "matches_map", "local_match_count",
+                 "state", "local_matches", "outliers"}
+    assert set(arr) == want
+    assert all(a.dtype in (np.float32, np.float64) for a in arr.values())
+    assert sum(a.nbytes for a in arr.values()) <= 64 * 1000 * 1000
+    fi = arr["frame_index"]
+    # 2 pipelines x 32 of their 40 counted frames: global frames 1..40 and 41..80 (halo frames are not counted)
+    assert len(fi) == 64 and len(set(fi)) == 64 and fi.min() >= 1 and fi.max() <= 80
+    assert np.all(np.diff(fi[:32]) > 0) and fi[:32].max() <= 40 < fi[32:].min()
+    n = int(arr["keypoint_count"].sum())
+    assert arr["keypoints"].shape == (n, 7) and arr["descriptors"].shape == (n, 32) and arr["matches"].shape == (n,)
+    if config == "D":
+        assert arr["pose"].shape == (64, 4, 4) and arr["outliers"].shape == (n,)

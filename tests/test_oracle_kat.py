@@ -33,12 +33,23 @@ def test_pattern_table_pinned():
     assert min(vals) >= -13 and max(vals) <= 12
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/src/ORBextractor.cc"), reason="reference not mounted")
-def test_pattern_table_matches_reference_source():
+def test_pattern_table_matches_reference_source(tmp_path):
+    """tools/gen_pattern.py's extraction, on a C++ source written here around the committed table
+    (comments and line breaks inside the initialiser, other initialisers before and after it), and
+    on the reference's own source file where a checkout of it is readable."""
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tools"))
-    from gen_pattern import extract
-    assert extract() == inc_ints()
+    import gen_pattern
+    vals = inc_ints()
+    rows = ["    %d,%d, %d,%d, /*mean (0), correlation (%d)*/" % (*vals[i:i + 4], i) for i in range(0, 1024, 4)]
+    src = tmp_path / "ORBextractor.cc"
+    src.write_text("const int HALF_PATCH_SIZE = 15;\nstatic int other_[2] = { 7, -7 };\n"
+                   "static int bit_pattern_31_[256*4] =\n{\n" + "\n".join(rows) + "\n};\n"
+                   "static int after_[3] = { 1, 2, 3 };\n")
+    assert gen_pattern.extract(str(src)) == vals
+    assert gen_pattern.digest(vals) == PATTERN_SHA
+    if os.access(gen_pattern.SRC, os.R_OK):
+        assert gen_pattern.extract() == vals
 
 
 def test_oracle_pattern_loaded(oracle_mod):

@@ -25,10 +25,10 @@ for step in "$@"; do
         scale) run scale 900 python -u -m pytest tests/test_gpu_bench_scale.py -v -s -m gpu --timeout 300 --timeout-method thread ;;
         pytestall) run pytest_gpu 900 python -u -m pytest tests -q -m gpu --timeout 120 --timeout-method thread ;;
         smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-        bench) run bench 600 python bench.py ;;
-        benchB) run benchB 600 python bench.py --config B --batch 64 --no-cpu-baseline ;;
-        benchC) run benchC 600 python bench.py --config C --no-cpu-baseline --no-extras ;;
-        benchD) run benchD 600 python bench.py --config D --no-cpu-baseline --no-extras ;;
+        bench) run bench 600 python bench.py --full ;;
+        benchB) run benchB 600 python bench.py --full --config B --batch 64 --no-cpu-baseline ;;
+        benchC) run benchC 600 python bench.py --full --config C --no-cpu-baseline --no-extras ;;
+        benchD) run benchD 600 python bench.py --full --config D --no-cpu-baseline --no-extras ;;
         # per-kernel evidence with the side stream off and one pipeline: every kernel is then one
         # whole-batch launch running alone, the same launches bench.py's HIP-event pass times (it
         # disables the side stream and profiles pipeline 0 by itself)
@@ -45,7 +45,7 @@ for step in "$@"; do
         rehearsal)
             # the process-per-GPU path (torch.distributed.run, gloo barrier / max) with both ranks on
             # device 0 of this one-GPU box: plumbing only, the line is marked rehearsal_one_device
-            COEB_BENCH_ONE_DEVICE=1 run rehearsal 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline --no-extras --no-e2e ;;
+            COEB_BENCH_ONE_DEVICE=1 run rehearsal 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline --no-extras --no-e2e ;;
         posetime) run posetime 300 python tools/pose_timing.py ;;
         flow) run flow 300 python tools/flow_bench.py ;;
         flowprof) run flowprof 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/flowprof -o run -- python tools/flow_bench.py ;;
@@ -74,9 +74,9 @@ for step in "$@"; do
             python tools/pmc_summary.py gpurun_out/pmcB_sq/run_counter_collection.csv gpurun_out/pmcB_sq2/run_counter_collection.csv \
                 --valu-json gpurun_out/pmc_valu_1280x960.json --frames 257 --size 1280x960 --command "$B" > gpurun_out/pmcB_valu.log 2>&1
             ;;
-        benchB512) run benchB512 600 python bench.py --config B ;;
-        benchCfull) run benchC 600 python bench.py --config C ;;
-        benchDfull) run benchD 600 python bench.py --config D --no-extras ;;
+        benchB512) run benchB512 600 python bench.py --full --config B ;;
+        benchCfull) run benchC 600 python bench.py --full --config C ;;
+        benchDfull) run benchD 600 python bench.py --full --config D --no-extras ;;
         pmcD)
             # the configs[4] loop's kernels (flow, pose, TrackLocalMap) with their own traffic / VALU passes
             export COEB_SIDE_STREAM=0
