@@ -173,14 +173,20 @@ class BatchPipeline:
         if f == 0:
             return out
         m_ptr, n_ptr = c.batch_match_results()
+        if not m_ptr or not n_ptr:                  # as results(): nothing was matched yet
+            raise ValueError("frame(%d): the batch has no match results (run(match=True) first)" % f)
         out["nmatch"] = int(c.download(n_ptr + 4 * f, 4, np.int32)[0])
         out["match"] = c.download(m_ptr + 4 * kcap * f, 4 * n, np.int32)
         if not track:
             return out
         t_ptr, ni_ptr, _ = c.batch_pose_results()
+        if not t_ptr or not ni_ptr:
+            raise ValueError("frame(%d, track=True): the batch has no pose results (run(pose=True) first)" % f)
         out["T1"] = c.download(t_ptr + 64 * f, 64, np.float32).reshape(4, 4)
         out["nin1"] = int(c.download(ni_ptr + 4 * f, 4, np.int32)[0])
         t_ptr, ni_ptr, nm_ptr, nl_ptr, lm_ptr, o_ptr = c.batch_track_results()
+        if not all((t_ptr, ni_ptr, nm_ptr, nl_ptr, lm_ptr, o_ptr)):
+            raise ValueError("frame(%d, track=True): the batch has no TrackLocalMap results (run(track=True) first)" % f)
         out["T"] = c.download(t_ptr + 64 * f, 64, np.float32).reshape(4, 4)
         out["ninliers"] = int(c.download(ni_ptr + 4 * f, 4, np.int32)[0])
         out["nmatches_map"] = int(c.download(nm_ptr + 4 * f, 4, np.int32)[0])

@@ -1202,10 +1202,11 @@ int coeb_extract(coeb_ctx* c, const uint8_t* gray, int W, int H, size_t stride, 
         return hip_err(c, hipGetLastError(), "launch_extract");
     c->batch_frames = 1;
     c->batch_gray = dgray;
-    // the retained set is nfeatures plus at most a few per level (the final cull, ORBextractor.cc
-    // :1204-1207), so nfeatures + 256 records almost always cover it; a larger count costs a
-    // second round trip for the rest
-    const int guess = (kp_out && desc_out) ? std::min({kcap, std::max(cap, 0), c->params.nfeatures + 256}) : 0;
+    // with both arrays set, k_out_pack delivers every record the caller can take in the same
+    // synchronisation as the count: it copies min(count, guess) records and count <= kcap (kcap
+    // sums the levels' out_cap, make_plan), so min(count, cap) <= guess and the second round trip
+    // below serves one-array calls only
+    const int guess = (kp_out && desc_out) ? std::min(kcap, std::max(cap, 0)) : 0;
     hipStream_t s = main_stream(c);
     hipLaunchKernelGGL(k_out_pack, dim3(16), dim3(256), 0, s, b.counts, static_cast<const uint32_t*>(b.kps),
                        reinterpret_cast<const uint4*>(b.desc), guess, reinterpret_cast<int*>(c->pin_dev + o_n),
@@ -1218,13 +1219,10 @@ int coeb_extract(coeb_ctx* c, const uint8_t* gray, int W, int H, size_t stride, 
     memcpy(&n, c->pin + o_n, 4);
     *n_out = n;
     const int m = std::min(n, cap);
-    if (m > guess) {                         // past the packed records (or one output array only)
-        const size_t r = (size_t)(m - guess);
+    if (m > guess) {                         // one output array only (guess = 0): fetch it by a copy
         if (kp_out)
-            HIP_TRY(c, hipMemcpyAsync(c->pin + o_k + (size_t)guess * sizeof(coeb_keypoint), static_cast<const coeb_keypoint*>(b.kps) + guess,
-                                      r * sizeof(coeb_keypoint), hipMemcpyDeviceToHost, s));
-        if (desc_out) HIP_TRY(c, hipMemcpyAsync(c->pin + o_d + (size_t)guess * 32, b.desc + (size_t)guess * 32, r * 32,
-                                                hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipMemcpyAsync(c->pin + o_k, b.kps, (size_t)m * sizeof(coeb_keypoint), hipMemcpyDeviceToHost, s));
+        if (desc_out) HIP_TRY(c, hipMemcpyAsync(c->pin + o_d, b.desc, (size_t)m * 32, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
     }
     if (m > 0 && kp_out) memcpy(kp_out, c->pin + o_k, (size_t)m * sizeof(coeb_keypoint));

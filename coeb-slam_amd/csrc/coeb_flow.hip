@@ -938,15 +938,28 @@ __device__ __forceinline__ void tap_pairs(uint32_t q, uint32_t* t)
     t[2] = __builtin_amdgcn_perm(0u, q, 0x0c030c02u);
 }
 
-// The four row segments of the lane's tile as tap pairs, through a buffer resource over the level image (bounds-checked: a dword past the
-// image end reads as 0, so no per-row clamp), the window at scalar byte offset s_off and the
-// lane's four row offsets lofs[i] = min(C0, win) + min(R0 + i, win) * pitch fixed per level:
+// The four row segments of the lane's tile as tap pairs, through a buffer resource over the
+// level image, the window at scalar byte offset s_off and the lane's four row offsets
+// lofs[i] = min(C0, win) + min(R0 + i, win) * pitch fixed per level.  Every load is a dword at a
+// multiple of 4 bytes from the level's base, and a row's dword pair covers the four bytes wanted
+// and up to 4 more, which on the last inside window of a level whose pitch equals its width
+// (ipx = lw - win - 1, ipy = lh - win - 1) reach past the level's last pixel.  The resource's
+// limit is the level's byte size rounded up to a dword (lk_level_limit): the range check takes
+// in the scalar window base and returns 0 for a dword that crosses the limit, so a dword that
+// holds a valid byte is read whole and a dword wholly past the level reads as 0.  At most 3
+// bytes after the last pixel are touched, in the dword that holds it, and none when the level's
+// byte size is a multiple of 4 (every level of 640x480); they meet zero derivative weights.  For
+// the levels flow_alloc owns they lie in the level's align256 slot or the array after it; for
+// device-resident frames they are the next frame's first bytes or the rest of the caller's last
+// dword.
+// Cost:
 // per row one add and two ands, two loads with a scalar base, one alignbyte (round 5's 64-bit
 // addresses with a clamped second dword cost ~30 more VALU per LK iteration: k_lk 3.27 -> 2.95 ms
 // per config-D step, profiles/r06/s3).  Every lane loads all four rows (no divergent waits):
 // rows and columns are clamped to the window's +1 row / column, which the caller has checked lie
 // inside the level, and the samples this brings in outside the tile's pixels are weighed by zero
 // derivatives.
+__device__ __forceinline__ int lk_level_limit(int pitch, int lh) { return (pitch * lh + 3) & ~3; }
 __device__ __forceinline__ void tile_pairs_buf(__amdgpu_buffer_rsrc_t r, int s_off, const int (&lofs)[4], uint32_t (*t)[3])
 {
     const int s_al = s_off & ~3, s_mis = s_off & 3;
@@ -1011,8 +1024,8 @@ __global__ __launch_bounds__(256, COEB_LK_MINW) void k_lk(LkPyr pyr, const float
         const uint8_t* I = at_pair(pyr.P[level], level == 0 ? iz : pz, z);
         const uint8_t* J = at_pair(pyr.N[level], level == 0 ? iz : pz, z);
         const short2* D = at_pair(pyr.D[level], pz, z);
-        const __amdgpu_buffer_rsrc_t rI = __builtin_amdgcn_make_buffer_rsrc((void*)I, 0, pitch * lh, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rJ = __builtin_amdgcn_make_buffer_rsrc((void*)J, 0, pitch * lh, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rI = __builtin_amdgcn_make_buffer_rsrc((void*)I, 0, lk_level_limit(pitch, lh), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rJ = __builtin_amdgcn_make_buffer_rsrc((void*)J, 0, lk_level_limit(pitch, lh), 0x00020000);
         int lofs[4];
 #pragma unroll
         for (int i = 0; i < 4; i++) lofs[i] = min(C0, win) + min(R0 + i, win) * pitch;

@@ -129,9 +129,10 @@ def test_blur_pyramid_matches_oracle(ctx, ex, oracle_mod, w, h, pyr_form, monkey
 
 
 @pytest.mark.parametrize("nfeat,scale,nlev", [(500, 1.2, 8), (2000, 1.2, 8), (1000, 1.3, 6), (1000, 1.2, 4),
-                                              (1000, 1.1, 10)])
+                                              (1000, 1.1, 10), (1500, 1.2, 8)])
 def test_extract_params(oracle_mod, nfeat, scale, nlev):
-    """nlevels = 10 exercises CheckMovingKeyPoints_finall's hard-coded 8-level loop."""
+    """nlevels = 10 exercises CheckMovingKeyPoints_finall's hard-coded 8-level loop; nfeatures =
+    1500 is the middle step of the reference's adaptive extractor (Tracking.cc:426-466)."""
     from coeb_front import Context
     ex2 = oracle_mod.Extractor(nfeat, scale, nlev, 20, 7)
     c2 = Context(nfeat, scale, nlev, 20, 7, max_width=640, max_height=480)
