@@ -13,8 +13,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/coeb_front.h"
-#include "coeb_internal.hpp"
+#include "coeb_ctx.hpp"
 
 static const int8_t kPattern[1024] = {
 #include "../../data/orb_bit_pattern_31.inc"
@@ -24,32 +23,17 @@ static const int8_t kPattern[1024] = {
 // the library concurrently; coeb_last_error(NULL) returns the calling thread's last message
 static thread_local std::string g_last_error;
 
-// coeb_flow.hip
-extern "C" int coeb_internal_flow_counts(coeb_ctx* c, int* out, int cap, int* npairs);
-extern "C" void coeb_internal_flow_forget(const coeb_ctx* c);
-
 namespace {
 
 enum { PATCH_SIZE = 31, HALF_PATCH_SIZE = 15, EDGE_THRESHOLD = 19 };
 constexpr int kRoiMax = 64;
 constexpr int kFrameTmCap = 1024;     // T_M points per frame kept on the device (coeb_frame_batch_device)
-constexpr int kCurMax = 4095;
-constexpr int kMatchCQ = 64;   // candidate list entries per LastFrame point (coeb_match.hip kCQ)
 
 inline int cv_round(float v) { return (int)lrintf(v); }
 inline int cv_round_d(double v) { return (int)lrint(v); }
 inline int cv_floor(float v) { int i = (int)v; return i - (i > v); }
 inline int cv_ceil_d(double v) { int i = (int)v; return i + (i < v); }
 inline int64_t align256(int64_t v) { return (v + 255) & ~int64_t(255); }
-
-struct Tables {
-    int nfeatures;
-    double scale_factor;   // ORBextractor.h:114 `double scaleFactor`
-    int nlevels;
-    float scale[COEB_MAXL], inv_scale[COEB_MAXL], sigma2[COEB_MAXL], inv_sigma2[COEB_MAXL];
-    int nfeat[COEB_MAXL];
-    int umax[16];
-};
 
 // ORBextractor::ORBextractor (src/ORBextractor.cc:418-477)
 bool make_tables(const coeb_orb_params& prm, Tables& t)
@@ -293,42 +277,6 @@ bool make_plan(const Tables& t, int W, int H, Plan& P, std::vector<int>& rtab, s
     return true;
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t n = 0;
-};
-
-struct ProfImpl {
-    bool enabled = false;
-    std::vector<std::string> names;
-    std::vector<double> ms;
-    std::vector<int64_t> launches;
-    std::vector<hipEvent_t> pool;
-    std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;
-    int cur_name = -1;
-    hipEvent_t cur_start = nullptr;
-    hipEvent_t get()
-    {
-        if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
-        hipEvent_t e;
-        (void)hipEventCreate(&e);
-        return e;
-    }
-    void drain()
-    {
-        for (auto& pe : pending) {
-            float t = 0.f;
-            (void)hipEventSynchronize(pe.second.second);
-            (void)hipEventElapsedTime(&t, pe.second.first, pe.second.second);
-            ms[pe.first] += t;
-            launches[pe.first] += 1;
-            pool.push_back(pe.second.first);
-            pool.push_back(pe.second.second);
-        }
-        pending.clear();
-    }
-};
-
 }  // namespace
 
 void prof_begin(ProfileHook* p, const char* name, hipStream_t s)
@@ -362,62 +310,6 @@ void prof_end(ProfileHook* p, hipStream_t s)
     if (pi->pending.size() > 4096) pi->drain();
 }
 
-struct coeb_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    coeb_orb_params params{};
-    Tables tab{};
-    int max_w = 0, max_h = 0, max_batch = 0;
-    bool has_plan = false;
-    Plan plan{};
-    std::vector<int> rtab;
-    std::vector<CellDesc> cells;
-    std::map<std::string, DevBuf> bufs;
-    std::string err;
-    ProfImpl prof;
-    ProfileHook hook;
-    int batch_frames = 0;      // frames of the last extracted batch
-    const uint8_t* batch_gray = nullptr;
-    int ident_frames = 0;      // identity poses initialised in "b_I"
-    // Batch chunking over several HIP streams (coeb_set_batch_streams): chunk k = frames
-    // [chunk[k], chunk[k+1]) runs extract -> prep -> match on subs[k]; match of chunk k's first
-    // frame waits for chunk k-1's prep (its LastFrame).  The context stream joins the chunk
-    // streams lazily, before anything else is enqueued on it (main_stream()).
-    int nstreams = 1;
-    std::vector<hipStream_t> subs;
-    std::vector<int> chunk;                      // chunk boundaries of the last batch
-    std::vector<hipEvent_t> ev_prep, ev_mdone;   // per chunk: prep done / match done
-    bool mdone_valid = false;                    // ev_mdone holds the previous batch's matches
-    bool pending_join = false;
-    bool extract_chunked = false;                // the last batch extract ran on the chunk streams
-    hipEvent_t ev_main = nullptr, ev_join = nullptr;
-    // coeb_pose_batch_device runs k_pose on its own stream, so the optimiser of batch k overlaps
-    // the extraction and matching of batch k+1 (k_pose is latency bound, one workgroup per frame;
-    // the extraction kernels are VALU bound).  k_track_prep copies everything k_pose reads into
-    // t_* buffers; the next coeb_pose_batch_device, coeb_batch_pose_results, coeb_memcpy_d2h,
-    // coeb_synchronize and coeb_destroy join it (join_pose()).
-    hipStream_t pose_stream = nullptr;
-    // level-0 blur + FAST beside the pyramid (launch_extract's SideStream); COEB_SIDE_STREAM=0 disables
-    SideStream side{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 2, true, false};
-    bool side_init = false;
-    bool side_shared = false;                 // side.s is the device's shared side stream
-    hipEvent_t ev_ffork = nullptr, ev_fjoin = nullptr;   // the moving-object batch's LK-pyramid fork / join
-    hipEvent_t ev_tprep = nullptr, ev_pose = nullptr;
-    bool pose_pending = false;
-    // batch tracking state: Observations() the matcher gave the LastFrame points, the frames and
-    // min_matches of the last coeb_pose_batch_device (TrackLocalMap continues that batch)
-    int batch_nobs = 2, pose_frames = 0, pose_min_matches = 20;
-    hipEvent_t ev_tlm = nullptr;
-    int tlm_frames = 0;
-    // pinned host staging of the host-buffer entry points: their inputs are packed here and
-    // moved in one copy (a dozen small pageable copies cost more than the kernels)
-    uint8_t* pin = nullptr;
-    uint8_t* pin_dev = nullptr;        // the same page-locked bytes as the device addresses them
-    size_t pin_n = 0;
-};
-
-namespace {
-
 int set_err(coeb_ctx* c, int code, const std::string& msg)
 {
     if (c) c->err = msg;
@@ -430,34 +322,7 @@ int hip_err(coeb_ctx* c, hipError_t e, const char* where)
     return set_err(c, COEB_EDEVICE, std::string(where) + ": " + hipGetErrorString(e));
 }
 
-#define HIP_TRY(ctx, expr)                                          \
-    do {                                                            \
-        hipError_t _e = (expr);                                     \
-        if (_e != hipSuccess) return hip_err((ctx), _e, #expr);     \
-    } while (0)
-
-int quiesce(coeb_ctx* c);
-
-template <typename T>
-int ensure(coeb_ctx* c, const char* name, size_t count, T** out)
-{
-    DevBuf& b = c->bufs[name];
-    const size_t bytes = std::max<size_t>(count * sizeof(T), 256);
-    if (b.n < bytes) {
-        if (b.p) {
-            int rc = quiesce(c);          // work in flight on any of the context's streams may read it
-            if (rc) return rc;
-            (void)hipFree(b.p);
-        }
-        b.p = nullptr;
-        b.n = 0;
-        hipError_t e = hipMalloc(&b.p, bytes);
-        if (e != hipSuccess) return set_err(c, COEB_ENOMEM, std::string("hipMalloc ") + name + ": " + hipGetErrorString(e));
-        b.n = bytes;
-    }
-    *out = static_cast<T*>(b.p);
-    return 0;
-}
+namespace {
 
 // One frame's results written straight into the context's page-locked buffer (its device
 // alias): the keypoint count and the first min(count, guess) records and descriptors, so the
@@ -517,7 +382,8 @@ int stage_in(coeb_ctx* c, const Pack& pk, uint8_t** dbase, hipStream_t s)
 {
     int rc;
     const size_t total = std::max<size_t>(pk.total, 16);
-    if ((rc = pinned(c, total)) || (rc = ensure(c, "stage", total, dbase))) return rc;
+    if ((rc = pinned(c, total)) || (rc = ensure(c, c->ex.stage, total))) return rc;
+    *dbase = c->ex.stage.p;
     size_t off = 0;
     for (const Pack::Part& q : pk.parts) {
         if (q.n) {
@@ -543,18 +409,14 @@ int ensure_plan(coeb_ctx* c, int W, int H)
     int rc;
     if ((rc = quiesce(c))) return rc;
     c->plan = P;
-    Plan* dplan;
-    int* drtab;
-    CellDesc* dcells;
-    int8_t* dpat;
-    if ((rc = ensure(c, "plan", 1, &dplan))) return rc;
-    if ((rc = ensure(c, "rtab", std::max<size_t>(c->rtab.size(), 1), &drtab))) return rc;
-    if ((rc = ensure(c, "cells", c->cells.size(), &dcells))) return rc;
-    if ((rc = ensure(c, "pattern", 1024, &dpat))) return rc;
-    HIP_TRY(c, hipMemcpy(dplan, &c->plan, sizeof(Plan), hipMemcpyHostToDevice));
-    if (!c->rtab.empty()) HIP_TRY(c, hipMemcpy(drtab, c->rtab.data(), c->rtab.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(dcells, c->cells.data(), c->cells.size() * sizeof(CellDesc), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(dpat, kPattern, 1024, hipMemcpyHostToDevice));
+    PlanBufs& d = c->pl;
+    if ((rc = ensure(c, d.plan, 1)) || (rc = ensure(c, d.rtab, std::max<size_t>(c->rtab.size(), 1))) ||
+        (rc = ensure(c, d.cells, c->cells.size())) || (rc = ensure(c, d.pattern, 1024)))
+        return rc;
+    HIP_TRY(c, hipMemcpy(d.plan.p, &c->plan, sizeof(Plan), hipMemcpyHostToDevice));
+    if (!c->rtab.empty()) HIP_TRY(c, hipMemcpy(d.rtab.p, c->rtab.data(), c->rtab.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d.cells.p, c->cells.data(), c->cells.size() * sizeof(CellDesc), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d.pattern.p, kPattern, 1024, hipMemcpyHostToDevice));
     c->has_plan = true;
     return 0;
 }
@@ -565,29 +427,17 @@ int extract_bufs(coeb_ctx* c, int F, ExtractBufs& b)
     const Plan& P = c->plan;
     memset(&b, 0, sizeof(b));
     int rc;
-    uint8_t *pyr, *blur, *nodes, *desc;
-    int *cand_n, *lvl_n, *counts, *err;
-    uint32_t *cand, *keys, *lvl_kp;
-    coeb_keypoint* kps;
-    DynMask* dyn;
-    if ((rc = ensure(c, "pyr", (size_t)F * P.pyr_stride + 4096, &pyr))) return rc;
-    if ((rc = ensure(c, "blur", (size_t)F * P.blur_stride + 4096, &blur))) return rc;
-    if ((rc = ensure(c, "cand_n", (size_t)F * P.ncells, &cand_n))) return rc;
-    if ((rc = ensure(c, "cand", (size_t)F * P.ncells * P.cell_cap, &cand))) return rc;
-    if ((rc = ensure(c, "keys", (size_t)F * 2 * P.kbuf_stride, &keys))) return rc;
-    if ((rc = ensure(c, "nodes", (size_t)F * P.node_stride * 4, &nodes))) return rc;
-    if ((rc = ensure(c, "lvl_n", (size_t)F * P.L, &lvl_n))) return rc;
-    if ((rc = ensure(c, "lvl_kp", (size_t)F * P.lvl_stride, &lvl_kp))) return rc;
-    if ((rc = ensure(c, "kps", (size_t)F * P.kcap, &kps))) return rc;
-    if ((rc = ensure(c, "desc", (size_t)F * P.kcap * 32, &desc))) return rc;
-    if ((rc = ensure(c, "counts", (size_t)F, &counts))) return rc;
-    if ((rc = ensure(c, "dyn", (size_t)F, &dyn))) return rc;
-    if ((rc = ensure(c, "err", 4, &err))) return rc;
-    b.pyr = pyr; b.blur = blur; b.cand_n = cand_n; b.cand = cand; b.keys = keys; b.nodes = nodes;
-    b.lvl_n = lvl_n; b.lvl_kp = lvl_kp; b.kps = kps; b.desc = desc; b.counts = counts; b.dyn = dyn; b.err = err;
-    b.rtab = static_cast<const int*>(c->bufs["rtab"].p);
-    b.cells = static_cast<const CellDesc*>(c->bufs["cells"].p);
-    b.pattern = static_cast<const int8_t*>(c->bufs["pattern"].p);
+    ExtractDev& d = c->ex;
+    if ((rc = ensure(c, d.pyr, (size_t)F * P.pyr_stride + 4096)) || (rc = ensure(c, d.blur, (size_t)F * P.blur_stride + 4096)) ||
+        (rc = ensure(c, d.cand_n, (size_t)F * P.ncells)) || (rc = ensure(c, d.cand, (size_t)F * P.ncells * P.cell_cap)) ||
+        (rc = ensure(c, d.keys, (size_t)F * 2 * P.kbuf_stride)) || (rc = ensure(c, d.nodes, (size_t)F * P.node_stride * 4)) ||
+        (rc = ensure(c, d.lvl_n, (size_t)F * P.L)) || (rc = ensure(c, d.lvl_kp, (size_t)F * P.lvl_stride)) ||
+        (rc = ensure(c, d.kps, (size_t)F * P.kcap)) || (rc = ensure(c, d.desc, (size_t)F * P.kcap * 32)) ||
+        (rc = ensure(c, d.counts, (size_t)F)) || (rc = ensure(c, d.dyn, (size_t)F)) || (rc = ensure(c, d.err, 4)))
+        return rc;
+    b.pyr = d.pyr.p; b.blur = d.blur.p; b.cand_n = d.cand_n.p; b.cand = d.cand.p; b.keys = d.keys.p; b.nodes = d.nodes.p;
+    b.lvl_n = d.lvl_n.p; b.lvl_kp = d.lvl_kp.p; b.kps = d.kps.p; b.desc = d.desc.p; b.counts = d.counts.p; b.dyn = d.dyn.p;
+    b.err = d.err.p; b.rtab = c->pl.rtab.p; b.cells = c->pl.cells.p; b.pattern = c->pl.pattern.p;
     return 0;
 }
 
@@ -598,8 +448,7 @@ int upload_dyn(coeb_ctx* c, int F, const coeb_box* boxes, const int32_t* box_off
     const int nbox = (box_off && boxes) ? box_off[F] : 0;
     const int ntm = (tm_off && tm_xy) ? tm_off[F] : 0;
     int rc;
-    float *dbox, *dtm;
-    int32_t *dboff, *dtoff, *dblur;
+    ExtractDev& d = c->ex;
     // offsets must start at 0 and never decrease: every box then gets its frame from
     // k_box_frame, and every T_M range lies inside the uploaded array
     if (box_off && boxes && box_off[0] != 0) return set_err(c, COEB_EINVAL, "box_off[0] != 0");
@@ -611,30 +460,27 @@ int upload_dyn(coeb_ctx* c, int F, const coeb_box* boxes, const int32_t* box_off
     if (nbox > 0) {
         for (int f = 0; f < F; f++)
             if (box_off[f + 1] - box_off[f] > COEB_MAXBOX) return set_err(c, COEB_EINVAL, "more than 16 boxes in a frame");
-        if ((rc = ensure(c, "boxes", (size_t)nbox * 4, &dbox))) return rc;
-        if ((rc = ensure(c, "box_off", (size_t)F + 1, &dboff))) return rc;
-        if ((rc = ensure(c, "blurf", (size_t)nbox, &dblur))) return rc;
-        HIP_TRY(c, hipMemcpyAsync(dbox, boxes, (size_t)nbox * 16, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(dboff, box_off, (size_t)(F + 1) * 4, hipMemcpyHostToDevice, c->stream));
+        if ((rc = ensure(c, d.boxes, (size_t)nbox * 4)) || (rc = ensure(c, d.box_off, (size_t)F + 1)) ||
+            (rc = ensure(c, d.blurf, (size_t)nbox)))
+            return rc;
+        HIP_TRY(c, hipMemcpyAsync(d.boxes.p, boxes, (size_t)nbox * 16, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d.box_off.p, box_off, (size_t)(F + 1) * 4, hipMemcpyHostToDevice, c->stream));
         if (blur_flag) {
-            HIP_TRY(c, hipMemcpyAsync(dblur, blur_flag, (size_t)nbox * 4, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(d.blurf.p, blur_flag, (size_t)nbox * 4, hipMemcpyHostToDevice, c->stream));
         } else {
-            HIP_TRY(c, hipMemsetAsync(dblur, 0, (size_t)nbox * 4, c->stream));
+            HIP_TRY(c, hipMemsetAsync(d.blurf.p, 0, (size_t)nbox * 4, c->stream));
         }
-        b.boxes = dbox; b.box_off = dboff; b.blurf = dblur;
+        b.boxes = d.boxes.p; b.box_off = d.box_off.p; b.blurf = d.blurf.p;
     }
     if (ntm > 0) {
-        if ((rc = ensure(c, "tm", (size_t)ntm * 2, &dtm))) return rc;
-        if ((rc = ensure(c, "tm_off", (size_t)F + 1, &dtoff))) return rc;
-        HIP_TRY(c, hipMemcpyAsync(dtm, tm_xy, (size_t)ntm * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(dtoff, tm_off, (size_t)(F + 1) * 4, hipMemcpyHostToDevice, c->stream));
-        b.tm = dtm; b.tm_off = dtoff;
+        if ((rc = ensure(c, d.tm, (size_t)ntm * 2)) || (rc = ensure(c, d.tm_off, (size_t)F + 1))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(d.tm.p, tm_xy, (size_t)ntm * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d.tm_off.p, tm_off, (size_t)(F + 1) * 4, hipMemcpyHostToDevice, c->stream));
+        b.tm = d.tm.p; b.tm_off = d.tm_off.p;
     }
     return 0;
 }
 
-// The context stream, after it has been made to wait for every chunk stream of the last
-// batch (so work enqueued on it sees the batch's results).
 }  // namespace
 
 // The product switches (coeb_internal.hpp); every one of them is set by a GPU test.
@@ -667,9 +513,6 @@ const char* coeb_experiment(const char* name)
 
 namespace {
 
-// The side stream of launch_extract (created on first use), or null when disabled.  Per-kernel
-// profiling (coeb_profile_enable) serialises everything on the context stream, so each event
-// pair brackets one whole-batch launch.
 // A non-blocking stream whose priority the environment variable `env` may set ("high" / "low":
 // the device's greatest / least stream priority; unset: the default).  Experiment knob for the
 // multi-stream schedules (which queue the dispatcher serves first when CUs free up).
@@ -713,6 +556,11 @@ static void shared_side_release(int device)
     g_shared_side.erase(it);
 }
 
+}  // namespace
+
+// The side stream of launch_extract (created on first use), or null when disabled.  Per-kernel
+// profiling (coeb_profile_enable) serialises everything on the context stream, so each event
+// pair brackets one whole-batch launch.
 const SideStream* side_stream(coeb_ctx* c)
 {
     if (c->prof.enabled) return nullptr;
@@ -787,6 +635,8 @@ int quiesce(coeb_ctx* c)
     return 0;
 }
 
+namespace {
+
 // Chunk boundaries for F frames over the context's batch streams (>= 16 frames per chunk).
 int make_chunks(coeb_ctx* c, int F)
 {
@@ -835,12 +685,11 @@ ExtractBufs offset_bufs(const Plan& P, const ExtractBufs& b, int f0)
 // so the call's one synchronisation also brings the word back; err_word_seen checks the copy.
 int err_word_async(coeb_ctx* c, uint8_t* dst)
 {
-    int* derr = static_cast<int*>(c->bufs["err"].p);
-    if (!derr) {
+    if (!c->ex.err.p) {
         memset(dst, 0, 4);
         return 0;
     }
-    HIP_TRY(c, hipMemcpyAsync(dst, derr, 4, hipMemcpyDeviceToHost, main_stream(c)));
+    HIP_TRY(c, hipMemcpyAsync(dst, c->ex.err.p, 4, hipMemcpyDeviceToHost, main_stream(c)));
     return 0;
 }
 
@@ -851,14 +700,14 @@ int err_word_seen(coeb_ctx* c, const uint8_t* src)
     if (!h) return 0;
     char msg[160];
     snprintf(msg, sizeof msg, "internal capacity exceeded (device error bits 0x%x)", h);
-    HIP_TRY(c, hipMemsetAsync(c->bufs["err"].p, 0, 4, main_stream(c)));
+    HIP_TRY(c, hipMemsetAsync(c->ex.err.p, 0, 4, main_stream(c)));
     return set_err(c, COEB_ERANGE, msg);
 }
 
 int check_err_word(coeb_ctx* c)
 {
     main_stream(c);
-    int* derr = static_cast<int*>(c->bufs["err"].p);
+    int* derr = c->ex.err.p;
     if (!derr) return 0;
     int h = 0;
     HIP_TRY(c, hipMemcpyAsync(&h, derr, 4, hipMemcpyDeviceToHost, main_stream(c)));
@@ -929,8 +778,7 @@ coeb_ctx* coeb_create(const coeb_orb_params* params, int device, int max_width, 
         coeb_destroy(c);
         return nullptr;
     }
-    int* err;
-    if (ensure(c, "err", 4, &err) || hipMemset(err, 0, 16) != hipSuccess) {
+    if (ensure(c, c->ex.err, 4) || hipMemset(c->ex.err.p, 0, 16) != hipSuccess) {
         g_last_error = "coeb_create: device allocation failed";
         coeb_destroy(c);
         return nullptr;
@@ -970,8 +818,10 @@ void coeb_destroy(coeb_ctx* c)
         (void)hipEventDestroy(c->ev_pose);
         if (c->ev_tlm) (void)hipEventDestroy(c->ev_tlm);
     }
-    for (auto& kv : c->bufs)
-        if (kv.second.p) (void)hipFree(kv.second.p);
+    auto free_buf = [](auto& a) { if (a.p) (void)hipFree(a.p); };
+    each_buf(c->pl, free_buf); each_buf(c->ex, free_buf); each_buf(c->fb, free_buf);
+    each_buf(c->bm, free_buf); each_buf(c->bp, free_buf); each_buf(c->tl, free_buf);
+    each_buf(c->sf, free_buf); each_buf(c->tim, free_buf); each_buf(c->hl, free_buf);
     c->prof.drain();
     for (auto e : c->prof.pool) (void)hipEventDestroy(e);
     for (size_t k = 0; k < c->subs.size(); k++) {
@@ -983,7 +833,6 @@ void coeb_destroy(coeb_ctx* c)
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->pin) (void)hipHostFree(c->pin);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    coeb_internal_flow_forget(c);
     delete c;
 }
 
@@ -1041,7 +890,7 @@ int coeb_extract_batch_device(coeb_ctx* c, const uint8_t* d_gray, int F, int W, 
     if ((rc = extract_bufs(c, F, b))) return rc;
     if ((rc = upload_dyn(c, F, boxes, box_off, tm_xy, tm_off, blur_flag, b))) return rc;
     b.gray = d_gray;
-    const Plan* dplan = static_cast<const Plan*>(c->bufs["plan"].p);
+    const Plan* dplan = c->pl.plan.p;
     c->mdone_valid = false;
     c->extract_chunked = n > 1;
     if (n == 1) {
@@ -1066,12 +915,6 @@ int coeb_extract_batch_device(coeb_ctx* c, const uint8_t* d_gray, int F, int W, 
     return COEB_OK;
 }
 
-extern "C" int coeb_internal_pmo_batch(coeb_ctx* c, const uint8_t* d_gray, int F, int w, int h, float* tm_out,
-                                       int* ntm_out, int tm_cap);
-extern "C" int coeb_internal_blur_flags_batch(coeb_ctx* c, const uint8_t* d_gray, int W, int H, const float* d_boxes,
-                                              const int* d_box_off, int F, int* d_box_frame, int nbox, int* d_out,
-                                              hipStream_t s);
-
 int coeb_frame_batch_device(coeb_ctx* c, const uint8_t* d_gray, int F, int W, int H, const coeb_box* boxes,
                             const int32_t* box_off)
 {
@@ -1086,33 +929,30 @@ int coeb_frame_batch_device(coeb_ctx* c, const uint8_t* d_gray, int F, int W, in
     // the pose stream reads only its own snapshots (k_track_prep / k_tlm_snapshot).
     hipStream_t s = main_stream(c);
     const int nbox = boxes ? box_off[F] : 0;
-    float* tm;
-    int32_t *ntm, *bframe = nullptr, *blur = nullptr;
-    if ((rc = ensure(c, "f_tm", (size_t)F * kFrameTmCap * 2, &tm)) || (rc = ensure(c, "f_ntm", (size_t)F, &ntm)))
-        return rc;
+    FrameBatchBufs& fb = c->fb;
+    if ((rc = ensure(c, fb.f_tm, (size_t)F * kFrameTmCap * 2)) || (rc = ensure(c, fb.f_ntm, (size_t)F))) return rc;
     // ProcessMovingObject(frame f-1, frame f) -> T_M of frame f (Frame.cc:164-166)
-    if ((rc = coeb_internal_pmo_batch(c, d_gray, F, W, H, tm, ntm, kFrameTmCap))) return rc;
+    if ((rc = pmo_batch(c, d_gray, F, W, H, fb.f_tm.p, fb.f_ntm.p, kFrameTmCap))) return rc;
     ExtractBufs b;
     if ((rc = extract_bufs(c, F, b))) return rc;
     if ((rc = upload_dyn(c, F, boxes, box_off, nullptr, nullptr, nullptr, b))) return rc;
     if (nbox > 0) {
         // detect_laplacian blur flag of every box (Frame.cc:171-202); frame 0 = the first frame.
         // The box -> frame map is built on the device from the box offsets upload_dyn staged.
-        if ((rc = ensure(c, "f_bframe", (size_t)nbox, &bframe)) || (rc = ensure(c, "f_blur", (size_t)nbox, &blur)))
-            return rc;
-        if (coeb_internal_blur_flags_batch(c, d_gray, W, H, b.boxes, b.box_off, F, bframe, nbox, blur, s))
+        if ((rc = ensure(c, fb.f_bframe, (size_t)nbox)) || (rc = ensure(c, fb.f_blur, (size_t)nbox))) return rc;
+        if (blur_flags_batch(c, d_gray, W, H, b.boxes, b.box_off, F, fb.f_bframe.p, nbox, fb.f_blur.p, s))
             return hip_err(c, hipGetLastError(), "blur flags");
-        b.blurf = blur;
+        b.blurf = fb.f_blur.p;
     }
-    b.tmd = tm;
-    b.ntmd = ntm;
+    b.tmd = fb.f_tm.p;
+    b.ntmd = fb.f_ntm.p;
     b.tmd_cap = kFrameTmCap;
     b.gray = d_gray;
     c->mdone_valid = false;
     c->extract_chunked = false;
     c->chunk.assign(2, 0);
     c->chunk[1] = F;
-    if (launch_extract(c->plan, static_cast<const Plan*>(c->bufs["plan"].p), b, F, s, &c->hook, side_stream(c)))
+    if (launch_extract(c->plan, c->pl.plan.p, b, F, s, &c->hook, side_stream(c)))
         return hip_err(c, hipGetLastError(), "launch_extract");
     c->batch_frames = F;
     c->batch_gray = d_gray;
@@ -1122,11 +962,11 @@ int coeb_frame_batch_device(coeb_ctx* c, const uint8_t* d_gray, int F, int W, in
 int coeb_batch_frame_results(coeb_ctx* c, const float** d_tm, const int32_t** d_ntm, int* tm_cap,
                              const int32_t** d_blur)
 {
-    if (!c || !c->bufs.count("f_ntm")) return set_err(c, COEB_EINVAL, "no frame batch yet");
-    if (d_tm) *d_tm = static_cast<const float*>(c->bufs["f_tm"].p);
-    if (d_ntm) *d_ntm = static_cast<const int32_t*>(c->bufs["f_ntm"].p);
+    if (!c || !c->fb.f_ntm.p) return set_err(c, COEB_EINVAL, "no frame batch yet");
+    if (d_tm) *d_tm = c->fb.f_tm.p;
+    if (d_ntm) *d_ntm = c->fb.f_ntm.p;
     if (tm_cap) *tm_cap = kFrameTmCap;
-    if (d_blur) *d_blur = c->bufs.count("f_blur") ? static_cast<const int32_t*>(c->bufs["f_blur"].p) : nullptr;
+    if (d_blur) *d_blur = c->fb.f_blur.p;
     return COEB_OK;
 }
 
@@ -1144,9 +984,9 @@ int coeb_batch_results(coeb_ctx* c, const coeb_keypoint** d_kps, const uint8_t**
                        int* kcap)
 {
     if (!c || !c->has_plan) return set_err(c, COEB_EINVAL, "no batch extracted yet");
-    if (d_kps) *d_kps = static_cast<const coeb_keypoint*>(c->bufs["kps"].p);
-    if (d_desc) *d_desc = static_cast<const uint8_t*>(c->bufs["desc"].p);
-    if (d_counts) *d_counts = static_cast<const int32_t*>(c->bufs["counts"].p);
+    if (d_kps) *d_kps = c->ex.kps.p;
+    if (d_desc) *d_desc = c->ex.desc.p;
+    if (d_counts) *d_counts = c->ex.counts.p;
     if (kcap) *kcap = c->plan.kcap;
     return COEB_OK;
 }
@@ -1164,8 +1004,8 @@ int coeb_extract(coeb_ctx* c, const uint8_t* gray, int W, int H, size_t stride, 
     (void)hipSetDevice(c->device);
     int rc;
     if ((rc = ensure_plan(c, W, H))) return rc;
-    uint8_t* dgray;
-    if ((rc = ensure(c, "gray_stage", (size_t)W * H, &dgray))) return rc;
+    if ((rc = ensure(c, c->ex.gray_stage, (size_t)W * H))) return rc;
+    uint8_t* dgray = c->ex.gray_stage.p;
     // pinned staging at both ends: the image rows go through the context's page-locked buffer
     // (one DMA, no runtime pinning of the caller's pages), and the results come back into it
     // behind the kernels -- the count and the first `guess` records in one synchronisation
@@ -1198,7 +1038,7 @@ int coeb_extract(coeb_ctx* c, const uint8_t* gray, int W, int H, size_t stride, 
     b.gray = dgray;
     // one frame on one stream: the side stream's fork / join cost more than the overlap it buys
     // at F = 1 (0.389 vs 0.350 ms per single-frame step, profiles/r06/sf)
-    if (launch_extract(c->plan, static_cast<const Plan*>(c->bufs["plan"].p), b, 1, main_stream(c), &c->hook, nullptr))
+    if (launch_extract(c->plan, c->pl.plan.p, b, 1, main_stream(c), &c->hook, nullptr))
         return hip_err(c, hipGetLastError(), "launch_extract");
     c->batch_frames = 1;
     c->batch_gray = dgray;
@@ -1269,10 +1109,10 @@ int coeb_match_lastframe(coeb_ctx* c, const coeb_camera* cam, const coeb_curfram
     (void)hipSetDevice(c->device);
     const int cs = std::max(n, 1), ls = std::max(nl, 1);
     int rc;
-    int32_t *dscr, *derr, *dqn;
     uint8_t* dbase;
-    if ((rc = ensure(c, "m_scr", (size_t)ls * kMatchCQ, &dscr)) || (rc = ensure(c, "m_qn", (size_t)ls + 8, &dqn)) ||
-        (rc = ensure(c, "err", 4, &derr)))
+    SingleFrameBufs& sf = c->sf;
+    if ((rc = ensure(c, sf.m_scr, (size_t)ls * kCQ)) || (rc = ensure(c, sf.m_qn, (size_t)ls + kMaxSplit)) ||
+        (rc = ensure(c, c->ex.err, 4)))
         return rc;
     hipStream_t s = main_stream(c);
     // every input in one pinned staged copy (ten small pageable copies cost more than the kernel)
@@ -1308,10 +1148,10 @@ int coeb_match_lastframe(coeb_ctx* c, const coeb_camera* cam, const coeb_curfram
     mb.last_stride = ls;
     mb.Tcw_cur = reinterpret_cast<const float*>(dbase + o_T);
     mb.Tcw_last = reinterpret_cast<const float*>(dbase + o_Tl);
-    mb.match = dout; mb.nmatch = dout + cs; mb.scratch = dscr; mb.scratch_stride = ls * kMatchCQ; mb.err = derr;
+    mb.match = dout; mb.nmatch = dout + cs; mb.scratch = sf.m_scr.p; mb.scratch_stride = ls * kCQ; mb.err = c->ex.err.p;
     // one pair: its candidate lists are built by 8 workgroups (k_match_lists), as for a small
     // batch, instead of by the pair's one workgroup
-    mb.qn = dqn; mb.qn_stride = ls + 8;
+    mb.qn = sf.m_qn.p; mb.qn_stride = mb.last_stride + kMaxSplit;
     if (launch_match(make_cam(c, cam), mb, 1, th, bmono, check_ori, 0, s, &c->hook))
         return hip_err(c, hipGetLastError(), "launch_match");
     if ((rc = err_word_async(c, c->pin + o_err))) return rc;
@@ -1343,12 +1183,12 @@ int coeb_match_localmap(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe
     (void)hipSetDevice(c->device);
     const int cs = std::max(n, 1), qs = std::max(nq, 1);
     int rc;
-    int32_t *dout, *derr, *dpath;
-    uint32_t* dlist;
     uint8_t* dbase;
-    if ((rc = ensure(c, "l_out", (size_t)cs + 1, &dout)) || (rc = ensure(c, "l_list", (size_t)qs * match_list_cap(), &dlist)) ||
-        (rc = ensure(c, "err", 4, &derr)) || (rc = ensure(c, "l_path", 2, &dpath)))
+    SingleFrameBufs& sf = c->sf;
+    if ((rc = ensure(c, sf.l_out, (size_t)cs + 1)) || (rc = ensure(c, sf.l_list, (size_t)qs * kCQ)) ||
+        (rc = ensure(c, c->ex.err, 4)) || (rc = ensure(c, sf.l_path, 2)))
         return rc;
+    int32_t* dout = sf.l_out.p;
     hipStream_t s = main_stream(c);
     Pack pk;
     const size_t o_k = pk.add(cur->keys_un, (size_t)n * sizeof(coeb_keypoint)), o_d = pk.add(cur->descriptors, (size_t)n * 32);
@@ -1365,7 +1205,7 @@ int coeb_match_localmap(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe
     b.in_view = dbase + o_v; b.proj_x = (const float*)(dbase + o_px); b.proj_y = (const float*)(dbase + o_py);
     b.proj_xr = (const float*)(dbase + o_pxr); b.level = (const int*)(dbase + o_l); b.view_cos = (const float*)(dbase + o_c);
     b.desc = dbase + o_qd; b.nobs = (const int*)(dbase + o_no); b.mp_n = nq;
-    b.match = dout; b.nmatch = dout + cs; b.lists = dlist; b.err = derr; b.path = dpath;
+    b.match = dout; b.nmatch = dout + cs; b.lists = sf.l_list.p; b.err = c->ex.err.p; b.path = sf.l_path.p;
     rc = launch_match_local(make_cam(c, cam), b, th, nnratio, s, &c->hook);
     if (rc == -2) return set_err(c, COEB_ERANGE, "coeb_match_localmap: frame and local map exceed the LDS budget");
     if (rc) return hip_err(c, hipGetLastError(), "launch_match_local");
@@ -1393,12 +1233,12 @@ int coeb_match_keyframe(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe
     (void)hipSetDevice(c->device);
     const int cs = std::max(n, 1), qs = std::max(nq, 1);
     int rc;
-    int32_t *dout, *derr, *dpath;
-    uint32_t* dlist;
     uint8_t* dbase;
-    if ((rc = ensure(c, "l_out", (size_t)cs + 1, &dout)) || (rc = ensure(c, "l_list", (size_t)qs * match_list_cap(), &dlist)) ||
-        (rc = ensure(c, "err", 4, &derr)) || (rc = ensure(c, "l_path", 2, &dpath)))
+    SingleFrameBufs& sf = c->sf;
+    if ((rc = ensure(c, sf.l_out, (size_t)cs + 1)) || (rc = ensure(c, sf.l_list, (size_t)qs * kCQ)) ||
+        (rc = ensure(c, c->ex.err, 4)) || (rc = ensure(c, sf.l_path, 2)))
         return rc;
+    int32_t* dout = sf.l_out.p;
     hipStream_t s = main_stream(c);
     Pack pk;
     const size_t o_k = pk.add(cur->keys_un, (size_t)n * sizeof(coeb_keypoint)), o_d = pk.add(cur->descriptors, (size_t)n * 32);
@@ -1413,7 +1253,7 @@ int coeb_match_keyframe(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe
     b.valid = dbase + o_v; b.xw = (const float*)(dbase + o_x); b.desc = dbase + o_qd;
     b.maxd = (const float*)(dbase + o_mx); b.mind = (const float*)(dbase + o_mn); b.angle = (const float*)(dbase + o_a);
     b.kf_n = nq; b.Tcw = (const float*)(dbase + o_T);
-    b.match = dout; b.nmatch = dout + cs; b.lists = dlist; b.err = derr; b.path = dpath;
+    b.match = dout; b.nmatch = dout + cs; b.lists = sf.l_list.p; b.err = c->ex.err.p; b.path = sf.l_path.p;
     rc = launch_match_kf(make_cam(c, cam), b, th, orb_dist, check_ori ? 1 : 0, s, &c->hook);
     if (rc == -2) return set_err(c, COEB_ERANGE, "coeb_match_keyframe: frame and keyframe exceed the LDS budget");
     if (rc) return hip_err(c, hipGetLastError(), "launch_match_kf");
@@ -1441,11 +1281,9 @@ int coeb_pose_optimization(coeb_ctx* c, const coeb_camera* cam, const coeb_pose_
     (void)hipSetDevice(c->device);
     const int cs = std::max(n, 1);
     int rc;
-    uint8_t *dact, *dbase;
-    PoseEdgeRec* dedge;
-    double* dchi;
-    if ((rc = ensure(c, "p_act", cs, &dact)) || (rc = ensure(c, "p_edge", cs, &dedge)) || (rc = ensure(c, "p_chi", cs, &dchi)))
-        return rc;
+    uint8_t* dbase;
+    SingleFrameBufs& sf = c->sf;
+    if ((rc = ensure(c, sf.p_act, cs)) || (rc = ensure(c, sf.p_edge, cs)) || (rc = ensure(c, sf.p_chi, cs))) return rc;
     hipStream_t s = main_stream(c);
     // one staged region: outputs first (result, pose, outlier flags; copied back in one go), then inputs
     Pack pk;
@@ -1458,7 +1296,7 @@ int coeb_pose_optimization(coeb_ctx* c, const coeb_camera* cam, const coeb_pose_
     PoseBufs b;
     b.n = (const int*)(dbase + o_n); b.has_mp = dbase + o_h; b.xw = (const float*)(dbase + o_x); b.kps = dbase + o_k;
     b.ur = (const float*)(dbase + o_ur); b.inv_sigma2 = (const float*)(dbase + o_is); b.Tcw = (float*)(dbase + o_T);
-    b.outlier = dbase + o_out; b.result = (int*)(dbase + o_res); b.edges = dedge; b.active = dact; b.chi2 = dchi;
+    b.outlier = dbase + o_out; b.result = (int*)(dbase + o_res); b.edges = sf.p_edge.p; b.active = sf.p_act.p; b.chi2 = sf.p_chi.p;
     b.timing = nullptr;
     b.stride = cs;
     if (launch_pose(b, 1, cam->fx, cam->fy, cam->cx, cam->cy, cam->bf, s, &c->hook))
@@ -1485,29 +1323,27 @@ int match_batch_impl(coeb_ctx* c, const float* d_depth, int F, int W, int H, con
     const int K = c->plan.kcap;
     if (K > kCurMax) return set_err(c, COEB_EINVAL, "keypoint capacity exceeds the matcher limit (4095)");
     int rc;
-    float *ur, *dep, *xw, *dI;
-    uint8_t *has, *outl;
-    int32_t *nobsb, *match, *nm, *scr, *mqn, *derr;
-    const int qs = K + 8;                                   // split-list counts + 8 flags per pair
-    if ((rc = ensure(c, "b_mqn", (size_t)F * qs, &mqn)) || (rc = ensure(c, "b_ur", (size_t)F * K, &ur)) || (rc = ensure(c, "b_dep", (size_t)F * K, &dep)) ||
-        (rc = ensure(c, "b_xw", (size_t)F * K * 3, &xw)) || (rc = ensure(c, "b_has", (size_t)F * K, &has)) ||
-        (rc = ensure(c, "b_outl", (size_t)F * K, &outl)) || (rc = ensure(c, "b_nobs", (size_t)F * K, &nobsb)) ||
-        (rc = ensure(c, "b_match", (size_t)F * K, &match)) || (rc = ensure(c, "b_nm", (size_t)F, &nm)) ||
-        (rc = ensure(c, "b_scr", (size_t)F * K * kMatchCQ, &scr)) || (rc = ensure(c, "err", 4, &derr)))
+    BatchMatchBufs& bm = c->bm;
+    const int qs = K + kMaxSplit;                           // split-list counts + kMaxSplit flags per pair (last_stride = K)
+    if ((rc = ensure(c, bm.b_mqn, (size_t)F * qs)) || (rc = ensure(c, bm.b_ur, (size_t)F * K)) || (rc = ensure(c, bm.b_dep, (size_t)F * K)) ||
+        (rc = ensure(c, bm.b_xw, (size_t)F * K * 3)) || (rc = ensure(c, bm.b_has, (size_t)F * K)) ||
+        (rc = ensure(c, bm.b_outl, (size_t)F * K)) || (rc = ensure(c, bm.b_nobs, (size_t)F * K)) ||
+        (rc = ensure(c, bm.b_match, (size_t)F * K)) || (rc = ensure(c, bm.b_nm, (size_t)F)) ||
+        (rc = ensure(c, bm.b_scr, (size_t)F * K * kCQ)) || (rc = ensure(c, c->ex.err, 4)))
         return rc;
-    if (c->ident_frames < F || !c->bufs.count("b_I")) {
+    if (c->ident_frames < F || !bm.b_I.p) {
         const int n = std::max(F, c->max_batch);
         HIP_TRY(c, hipStreamSynchronize(main_stream(c)));
-        if ((rc = ensure(c, "b_I", (size_t)n * 16, &dI))) return rc;
+        if ((rc = ensure(c, bm.b_I, (size_t)n * 16))) return rc;
         std::vector<float> I((size_t)n * 16, 0.f);
         for (int p = 0; p < n; p++) I[(size_t)p * 16 + 0] = I[(size_t)p * 16 + 5] = I[(size_t)p * 16 + 10] = I[(size_t)p * 16 + 15] = 1.f;
-        HIP_TRY(c, hipMemcpy(dI, I.data(), I.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(bm.b_I.p, I.data(), I.size() * 4, hipMemcpyHostToDevice));
         c->ident_frames = n;
     }
-    dI = static_cast<float*>(c->bufs["b_I"].p);
-    const coeb_keypoint* kps = static_cast<const coeb_keypoint*>(c->bufs["kps"].p);
-    const uint8_t* desc = static_cast<const uint8_t*>(c->bufs["desc"].p);
-    const int32_t* counts = static_cast<const int32_t*>(c->bufs["counts"].p);
+    float *ur = bm.b_ur.p, *xw = bm.b_xw.p;
+    uint8_t *has = bm.b_has.p, *outl = bm.b_outl.p, *desc = c->ex.desc.p;
+    int32_t *nobsb = bm.b_nobs.p, *counts = c->ex.counts.p;
+    const coeb_keypoint* kps = c->ex.kps.p;
     const MatchCam mcam = make_cam(c, cam);
     // chunk k (frames [f0, f1)) on its stream: prep, then the pairs whose current frame is in
     // the chunk; the first of them needs chunk k-1's last frame prepared
@@ -1524,7 +1360,7 @@ int match_batch_impl(coeb_ctx* c, const float* d_depth, int F, int W, int H, con
         const int64_t o = (int64_t)f0 * K;
         pb.kps = kps + o; pb.n = counts + f0; pb.stride = K; pb.depth = d_depth + (int64_t)f0 * W * H; pb.W = W; pb.H = H;
         pb.bf = cam->bf; pb.fx = cam->fx; pb.fy = cam->fy; pb.cx = cam->cx; pb.cy = cam->cy;
-        pb.ur = ur + o; pb.dep = dep + o; pb.has = has + o; pb.outl = outl + o; pb.xw = xw + 3 * o;
+        pb.ur = ur + o; pb.dep = bm.b_dep.p + o; pb.has = has + o; pb.outl = outl + o; pb.xw = xw + 3 * o;
         pb.nobs = nobsb + o; pb.nobs_value = nobs;
         if (launch_prep(pb, f1 - f0, s, &c->hook)) return hip_err(c, hipGetLastError(), "launch_prep");
         if (chunked) {
@@ -1540,14 +1376,13 @@ int match_batch_impl(coeb_ctx* c, const float* d_depth, int F, int W, int H, con
             mb.cur_stride = K;
             mb.last_kps = kps + q; mb.last_desc = desc + q * 32; mb.last_n = counts + p0; mb.last_has = has + q;
             mb.last_out = outl + q; mb.last_xw = xw + 3 * q; mb.last_nobs = nobsb + q; mb.last_stride = K;
-            mb.Tcw_cur = dT_cur + 16 * p0; mb.Tcw_last = dI + 16 * p0;
-            mb.match = match + q + K; mb.nmatch = nm + p0 + 1; mb.scratch = scr + q * kMatchCQ;
-            mb.scratch_stride = K * kMatchCQ; mb.err = derr;
-            mb.qn = mqn + (int64_t)p0 * qs; mb.qn_stride = qs;
+            mb.Tcw_cur = dT_cur + 16 * p0; mb.Tcw_last = bm.b_I.p + 16 * p0;
+            mb.match = bm.b_match.p + q + K; mb.nmatch = bm.b_nm.p + p0 + 1; mb.scratch = bm.b_scr.p + q * kCQ;
+            mb.scratch_stride = K * kCQ; mb.err = c->ex.err.p;
+            mb.qn = bm.b_mqn.p + (int64_t)p0 * qs; mb.qn_stride = qs;
             if (COEB_MATCH_CLOCK && coeb_experiment("COEB_MATCH_TIMING")) {
-                long long* tmb;
-                if ((rc = ensure(c, "m_timing", (size_t)F * 16, &tmb))) return rc;
-                mb.timing = tmb + (int64_t)p0 * 16;
+                if ((rc = ensure(c, c->tim.m_timing, (size_t)F * 16))) return rc;
+                mb.timing = c->tim.m_timing.p + (int64_t)p0 * 16;
             }
             if (launch_match(mcam, mb, np, th, 0, 1, 20, s, &c->hook)) return hip_err(c, hipGetLastError(), "launch_match");
         }
@@ -1575,8 +1410,8 @@ int coeb_match_batch_device(coeb_ctx* c, const float* d_depth, int F, int W, int
     int rc;
     if ((rc = match_batch_check(c, d_depth, F, W, H, cam, Tcw))) return rc;
     (void)hipSetDevice(c->device);
-    float* dT;
-    if ((rc = ensure(c, "b_T", (size_t)F * 16, &dT))) return rc;
+    if ((rc = ensure(c, c->bm.b_T, (size_t)F * 16))) return rc;
+    float* dT = c->bm.b_T.p;
     // the previous batch's matchers may still read b_T: join them before overwriting it
     HIP_TRY(c, hipMemcpyAsync(dT, Tcw, (size_t)F * 64, hipMemcpyHostToDevice, main_stream(c)));
     return match_batch_impl(c, d_depth, F, W, H, cam, dT + 16, th, nobs, true);
@@ -1594,31 +1429,26 @@ int coeb_match_batch_device_tcw(coeb_ctx* c, const float* d_depth, int F, int W,
 int coeb_batch_match_results(coeb_ctx* c, const int32_t** d_match, const int32_t** d_nmatches)
 {
     if (!c) return COEB_EINVAL;
-    if (d_match) *d_match = static_cast<const int32_t*>(c->bufs["b_match"].p);
-    if (d_nmatches) *d_nmatches = static_cast<const int32_t*>(c->bufs["b_nm"].p);
+    if (d_match) *d_match = c->bm.b_match.p;
+    if (d_nmatches) *d_nmatches = c->bm.b_nm.p;
     return COEB_OK;
 }
 
 int coeb_pose_batch_device(coeb_ctx* c, const coeb_camera* cam, int F, const float* d_Tcw, int32_t min_matches)
 {
     if (!c || !cam || !d_Tcw || F <= 0) return set_err(c, COEB_EINVAL, "coeb_pose_batch_device: invalid arguments");
-    if (!c->has_plan || c->batch_frames != F || !c->bufs.count("b_match") || !c->bufs.count("b_xw"))
+    if (!c->has_plan || c->batch_frames != F || !c->bm.b_match.p || !c->bm.b_xw.p)
         return set_err(c, COEB_EINVAL, "coeb_pose_batch_device: must follow coeb_match_batch_device on the same batch");
     (void)hipSetDevice(c->device);
     const int K = c->plan.kcap;
     int rc;
-    float *tout, *txw, *isg, *tur;
-    coeb_keypoint* tkp;
-    uint8_t *thas, *toutl, *tact;
-    int32_t *tn, *tres;
-    PoseEdgeRec* tedge;
-    double* tchi;
-    if ((rc = ensure(c, "t_T", (size_t)F * 16, &tout)) || (rc = ensure(c, "t_xw", (size_t)F * K * 3, &txw)) ||
-        (rc = ensure(c, "t_isg", COEB_MAXL, &isg)) || (rc = ensure(c, "t_has", (size_t)F * K, &thas)) ||
-        (rc = ensure(c, "t_outl", (size_t)F * K, &toutl)) || (rc = ensure(c, "t_act", (size_t)F * K, &tact)) ||
-        (rc = ensure(c, "t_n", (size_t)F, &tn)) || (rc = ensure(c, "t_res", (size_t)F, &tres)) ||
-        (rc = ensure(c, "t_edge", (size_t)F * K, &tedge)) || (rc = ensure(c, "t_chi", (size_t)F * K, &tchi)) ||
-        (rc = ensure(c, "t_kp", (size_t)F * K, &tkp)) || (rc = ensure(c, "t_ur", (size_t)F * K, &tur)))
+    BatchPoseBufs& bp = c->bp;
+    if ((rc = ensure(c, bp.t_T, (size_t)F * 16)) || (rc = ensure(c, bp.t_xw, (size_t)F * K * 3)) ||
+        (rc = ensure(c, bp.t_isg, COEB_MAXL)) || (rc = ensure(c, bp.t_has, (size_t)F * K)) ||
+        (rc = ensure(c, bp.t_outl, (size_t)F * K)) || (rc = ensure(c, bp.t_act, (size_t)F * K)) ||
+        (rc = ensure(c, bp.t_n, (size_t)F)) || (rc = ensure(c, bp.t_res, (size_t)F)) ||
+        (rc = ensure(c, bp.t_edge, (size_t)F * K)) || (rc = ensure(c, bp.t_chi, (size_t)F * K)) ||
+        (rc = ensure(c, bp.t_kp, (size_t)F * K)) || (rc = ensure(c, bp.t_ur, (size_t)F * K)))
         return rc;
     hipStream_t s = main_stream(c);                 // joins the matchers' chunk streams
     if (!c->pose_stream) {
@@ -1627,18 +1457,15 @@ int coeb_pose_batch_device(coeb_ctx* c, const coeb_camera* cam, int F, const flo
         HIP_TRY(c, hipEventCreateWithFlags(&c->ev_pose, hipEventDisableTiming));
     }
     join_pose(c);                                   // the previous batch's k_pose still reads t_*
-    HIP_TRY(c, hipMemsetAsync(thas, 0, (size_t)F * K, s));
-    HIP_TRY(c, hipMemsetAsync(toutl, 0, (size_t)F * K, s));
-    HIP_TRY(c, hipMemsetAsync(tres, 0, (size_t)F * 4, s));
+    HIP_TRY(c, hipMemsetAsync(bp.t_has.p, 0, (size_t)F * K, s));
+    HIP_TRY(c, hipMemsetAsync(bp.t_outl.p, 0, (size_t)F * K, s));
+    HIP_TRY(c, hipMemsetAsync(bp.t_res.p, 0, (size_t)F * 4, s));
     TrackPrepBufs t;
     memset(&t, 0, sizeof(t));
-    t.match = static_cast<const int32_t*>(c->bufs["b_match"].p);
-    t.nmatch = static_cast<const int32_t*>(c->bufs["b_nm"].p);
-    t.counts = static_cast<const int32_t*>(c->bufs["counts"].p);
-    t.last_xw = static_cast<const float*>(c->bufs["b_xw"].p);
-    t.kps_in = c->bufs["kps"].p; t.ur_in = static_cast<const float*>(c->bufs["b_ur"].p);
-    t.kps_out = tkp; t.ur_out = tur;
-    t.Tin = d_Tcw; t.Tout = tout; t.has = thas; t.xw = txw; t.n = tn; t.isg_out = isg;
+    t.match = c->bm.b_match.p; t.nmatch = c->bm.b_nm.p; t.counts = c->ex.counts.p; t.last_xw = c->bm.b_xw.p;
+    t.kps_in = c->ex.kps.p; t.ur_in = c->bm.b_ur.p;
+    t.kps_out = bp.t_kp.p; t.ur_out = bp.t_ur.p;
+    t.Tin = d_Tcw; t.Tout = bp.t_T.p; t.has = bp.t_has.p; t.xw = bp.t_xw.p; t.n = bp.t_n.p; t.isg_out = bp.t_isg.p;
     for (int l = 0; l < COEB_MAXL; l++) t.isg[l] = l < c->tab.nlevels ? c->tab.inv_sigma2[l] : 0.f;
     t.stride = K;
     t.min_matches = min_matches;
@@ -1646,14 +1473,14 @@ int coeb_pose_batch_device(coeb_ctx* c, const coeb_camera* cam, int F, const flo
     if (F < 2) return COEB_OK;
     const int64_t o = K;                            // frame 1 = current frame of pair 0
     PoseBufs b;
-    b.n = tn + 1; b.has_mp = thas + o; b.xw = txw + 3 * o;
-    b.kps = tkp + o; b.ur = tur + o;
-    b.inv_sigma2 = isg; b.Tcw = tout + 16; b.outlier = toutl + o; b.result = tres + 1;
-    b.edges = tedge + o; b.active = tact + o; b.chi2 = tchi + o; b.stride = K;
+    b.n = bp.t_n.p + 1; b.has_mp = bp.t_has.p + o; b.xw = bp.t_xw.p + 3 * o;
+    b.kps = bp.t_kp.p + o; b.ur = bp.t_ur.p + o;
+    b.inv_sigma2 = bp.t_isg.p; b.Tcw = bp.t_T.p + 16; b.outlier = bp.t_outl.p + o; b.result = bp.t_res.p + 1;
+    b.edges = bp.t_edge.p + o; b.active = bp.t_act.p + o; b.chi2 = bp.t_chi.p + o; b.stride = K;
     b.timing = nullptr;
     if (coeb_experiment("COEB_POSE_TIMING")) {               // diagnostic phase clocks, tools/_pose_timing.py
-        long long* tmb;
-        if ((rc = ensure(c, "p_timing", (size_t)F * 8, &tmb))) return rc;
+        if ((rc = ensure(c, c->tim.p_timing, (size_t)F * 8))) return rc;
+        long long* tmb = c->tim.p_timing.p;
         HIP_TRY(c, hipMemsetAsync(tmb, 0, (size_t)F * 64, s));
         b.timing = tmb + 8;
     }
@@ -1671,11 +1498,11 @@ int coeb_pose_batch_device(coeb_ctx* c, const coeb_camera* cam, int F, const flo
 
 int coeb_batch_pose_results(coeb_ctx* c, const float** d_Tcw, const int32_t** d_ninliers, const uint8_t** d_outlier)
 {
-    if (!c || !c->bufs.count("t_T")) return set_err(c, COEB_EINVAL, "coeb_batch_pose_results: no batch pose yet");
+    if (!c || !c->bp.t_T.p) return set_err(c, COEB_EINVAL, "coeb_batch_pose_results: no batch pose yet");
     join_pose(c);
-    if (d_Tcw) *d_Tcw = static_cast<const float*>(c->bufs["t_T"].p);
-    if (d_ninliers) *d_ninliers = static_cast<const int32_t*>(c->bufs["t_res"].p);
-    if (d_outlier) *d_outlier = static_cast<const uint8_t*>(c->bufs["t_outl"].p);
+    if (d_Tcw) *d_Tcw = c->bp.t_T.p;
+    if (d_ninliers) *d_ninliers = c->bp.t_res.p;
+    if (d_outlier) *d_outlier = c->bp.t_outl.p;
     return COEB_OK;
 }
 
@@ -1683,7 +1510,7 @@ int coeb_track_local_map_batch_device(coeb_ctx* c, const coeb_camera* cam, int F
 {
     if (!c || !cam || F <= 0 || nkf < 1 || nkf > 2 || !(th > 0) || !(nnratio > 0))
         return set_err(c, COEB_EINVAL, "coeb_track_local_map_batch_device: invalid arguments");
-    if (!c->has_plan || c->batch_frames != F || c->pose_frames != F || !c->bufs.count("t_T"))
+    if (!c->has_plan || c->batch_frames != F || c->pose_frames != F || !c->bp.t_T.p)
         return set_err(c, COEB_EINVAL, "coeb_track_local_map_batch_device: must follow coeb_pose_batch_device on the same batch");
     if (c->tlm_frames) return set_err(c, COEB_EINVAL, "coeb_track_local_map_batch_device: already run on this batch");
     (void)hipSetDevice(c->device);
@@ -1692,38 +1519,37 @@ int coeb_track_local_map_batch_device(coeb_ctx* c, const coeb_camera* cam, int F
     int rc;
     TlmBufs t;
     memset(&t, 0, sizeof(t));
-    uint8_t *s_desc, *s_has, *seen, *act, *inv, *has2, *outl2;
-    int8_t* s_oct;
-    float *s_xw, *px, *py, *pxr, *vc, *lxw, *xw2, *T2;
-    int32_t *s_m1, *s_cnt, *s_nm1, *cobs, *nmap, *lvl, *lno, *lmatch, *nloc, *lpath, *n2, *res2, *derr;
-    uint32_t* lists;
-    if ((rc = ensure(c, "tl_sdesc", (size_t)(FK + K) * 32, &s_desc)) || (rc = ensure(c, "tl_soct", (size_t)FK, &s_oct)) ||
-        (rc = ensure(c, "tl_shas", (size_t)FK, &s_has)) || (rc = ensure(c, "tl_sxw", (size_t)FK * 3, &s_xw)) ||
-        (rc = ensure(c, "tl_sm1", (size_t)FK, &s_m1)) || (rc = ensure(c, "tl_scnt", (size_t)F, &s_cnt)) ||
-        (rc = ensure(c, "tl_snm1", (size_t)F, &s_nm1)) || (rc = ensure(c, "tl_seen", (size_t)FK, &seen)) ||
-        (rc = ensure(c, "tl_cobs", (size_t)FK, &cobs)) || (rc = ensure(c, "tl_nmap", (size_t)F, &nmap)) ||
-        (rc = ensure(c, "tl_active", (size_t)F, &act)) || (rc = ensure(c, "tl_inview", (size_t)FM, &inv)) ||
-        (rc = ensure(c, "tl_px", (size_t)FM, &px)) || (rc = ensure(c, "tl_py", (size_t)FM, &py)) ||
-        (rc = ensure(c, "tl_pxr", (size_t)FM, &pxr)) || (rc = ensure(c, "tl_level", (size_t)FM, &lvl)) ||
-        (rc = ensure(c, "tl_vcos", (size_t)FM, &vc)) || (rc = ensure(c, "tl_lnobs", (size_t)FM, &lno)) ||
-        (rc = ensure(c, "tl_lxw", (size_t)FM * 3, &lxw)) || (rc = ensure(c, "tl_lmatch", (size_t)FK, &lmatch)) ||
-        (rc = ensure(c, "tl_nlocal", (size_t)F, &nloc)) || (rc = ensure(c, "tl_path", (size_t)F * 2, &lpath)) ||
-        (rc = ensure(c, "tl_lists", (size_t)FM * match_list_cap(), &lists)) ||
-        (rc = ensure(c, "tl_has2", (size_t)FK, &has2)) || (rc = ensure(c, "tl_xw2", (size_t)FK * 3, &xw2)) ||
-        (rc = ensure(c, "tl_T2", (size_t)F * 16, &T2)) || (rc = ensure(c, "tl_outl2", (size_t)FK, &outl2)) ||
-        (rc = ensure(c, "tl_n2", (size_t)F, &n2)) || (rc = ensure(c, "tl_res2", (size_t)F, &res2)) ||
-        (rc = ensure(c, "err", 4, &derr)))
+    TrackLocalMapBufs& tl = c->tl;
+    const BatchPoseBufs& bp = c->bp;
+    if ((rc = ensure(c, tl.tl_sdesc, (size_t)(FK + K) * 32)) || (rc = ensure(c, tl.tl_soct, (size_t)FK)) ||
+        (rc = ensure(c, tl.tl_shas, (size_t)FK)) || (rc = ensure(c, tl.tl_sxw, (size_t)FK * 3)) ||
+        (rc = ensure(c, tl.tl_sm1, (size_t)FK)) || (rc = ensure(c, tl.tl_scnt, (size_t)F)) ||
+        (rc = ensure(c, tl.tl_snm1, (size_t)F)) || (rc = ensure(c, tl.tl_seen, (size_t)FK)) ||
+        (rc = ensure(c, tl.tl_cobs, (size_t)FK)) || (rc = ensure(c, tl.tl_nmap, (size_t)F)) ||
+        (rc = ensure(c, tl.tl_active, (size_t)F)) || (rc = ensure(c, tl.tl_inview, (size_t)FM)) ||
+        (rc = ensure(c, tl.tl_px, (size_t)FM)) || (rc = ensure(c, tl.tl_py, (size_t)FM)) ||
+        (rc = ensure(c, tl.tl_pxr, (size_t)FM)) || (rc = ensure(c, tl.tl_level, (size_t)FM)) ||
+        (rc = ensure(c, tl.tl_vcos, (size_t)FM)) || (rc = ensure(c, tl.tl_lnobs, (size_t)FM)) ||
+        (rc = ensure(c, tl.tl_lxw, (size_t)FM * 3)) || (rc = ensure(c, tl.tl_lmatch, (size_t)FK)) ||
+        (rc = ensure(c, tl.tl_nlocal, (size_t)F)) || (rc = ensure(c, tl.tl_path, (size_t)F * 2)) ||
+        (rc = ensure(c, tl.tl_lists, (size_t)FM * kCQ)) ||
+        (rc = ensure(c, tl.tl_has2, (size_t)FK)) || (rc = ensure(c, tl.tl_xw2, (size_t)FK * 3)) ||
+        (rc = ensure(c, tl.tl_T2, (size_t)F * 16)) || (rc = ensure(c, tl.tl_outl2, (size_t)FK)) ||
+        (rc = ensure(c, tl.tl_n2, (size_t)F)) || (rc = ensure(c, tl.tl_res2, (size_t)F)) ||
+        (rc = ensure(c, c->ex.err, 4)))
         return rc;
+    uint8_t *s_desc = tl.tl_sdesc.p, *act = tl.tl_active.p, *inv = tl.tl_inview.p, *has2 = tl.tl_has2.p, *outl2 = tl.tl_outl2.p;
+    float *px = tl.tl_px.p, *py = tl.tl_py.p, *pxr = tl.tl_pxr.p, *vc = tl.tl_vcos.p, *xw2 = tl.tl_xw2.p, *T2 = tl.tl_T2.p;
+    int32_t *s_cnt = tl.tl_scnt.p, *cobs = tl.tl_cobs.p, *lvl = tl.tl_level.p, *lno = tl.tl_lnobs.p, *lmatch = tl.tl_lmatch.p,
+            *n2 = tl.tl_n2.p;
     t.K = K; t.nkf = nkf; t.nobs = c->batch_nobs; t.min_matches = c->pose_min_matches; t.min_map = 10;
-    t.kps = c->bufs["kps"].p; t.desc = static_cast<const uint8_t*>(c->bufs["desc"].p);
-    t.counts = static_cast<const int32_t*>(c->bufs["counts"].p);
-    t.match1 = static_cast<const int32_t*>(c->bufs["b_match"].p); t.nmatch1 = static_cast<const int32_t*>(c->bufs["b_nm"].p);
-    t.has = static_cast<const uint8_t*>(c->bufs["b_has"].p); t.xw = static_cast<const float*>(c->bufs["b_xw"].p);
-    t.s_desc = s_desc; t.s_oct = s_oct; t.s_has = s_has; t.s_xw = s_xw; t.s_m1 = s_m1; t.s_cnt = s_cnt; t.s_nm1 = s_nm1;
-    t.T1 = static_cast<const float*>(c->bufs["t_T"].p); t.has1 = static_cast<const uint8_t*>(c->bufs["t_has"].p);
-    t.outl1 = static_cast<const uint8_t*>(c->bufs["t_outl"].p); t.xw1 = static_cast<const float*>(c->bufs["t_xw"].p);
-    t.seen = seen; t.cur_obs = cobs; t.nmap = nmap; t.active = act;
-    t.in_view = inv; t.px = px; t.py = py; t.pxr = pxr; t.level = lvl; t.vcos = vc; t.lm_nobs = lno; t.lm_xw = lxw;
+    t.kps = c->ex.kps.p; t.desc = c->ex.desc.p; t.counts = c->ex.counts.p;
+    t.match1 = c->bm.b_match.p; t.nmatch1 = c->bm.b_nm.p; t.has = c->bm.b_has.p; t.xw = c->bm.b_xw.p;
+    t.s_desc = s_desc; t.s_oct = tl.tl_soct.p; t.s_has = tl.tl_shas.p; t.s_xw = tl.tl_sxw.p; t.s_m1 = tl.tl_sm1.p;
+    t.s_cnt = s_cnt; t.s_nm1 = tl.tl_snm1.p;
+    t.T1 = bp.t_T.p; t.has1 = bp.t_has.p; t.outl1 = bp.t_outl.p; t.xw1 = bp.t_xw.p;
+    t.seen = tl.tl_seen.p; t.cur_obs = cobs; t.nmap = tl.tl_nmap.p; t.active = act;
+    t.in_view = inv; t.px = px; t.py = py; t.pxr = pxr; t.level = lvl; t.vcos = vc; t.lm_nobs = lno; t.lm_xw = tl.tl_lxw.p;
     t.lmatch = lmatch; t.has2 = has2; t.xw2 = xw2; t.T2 = T2; t.outl2 = outl2; t.n2 = n2;
     // the snapshot runs on the context stream, after this batch's matcher and before the next
     // batch's extraction; coeb_pose_batch_device already joined the previous pose-stream work
@@ -1737,15 +1563,16 @@ int coeb_track_local_map_batch_device(coeb_ctx* c, const coeb_camera* cam, int F
     const MatchCam mcam = make_cam(c, cam);
     if (launch_tlm_frustum(mcam, t, F, ps, &c->hook)) return hip_err(c, hipGetLastError(), "launch_tlm_frustum");
     LocalBufsHost lb;
-    lb.cur_kps = static_cast<const coeb_keypoint*>(c->bufs["t_kp"].p) + K;
+    lb.cur_kps = bp.t_kp.p + K;
     lb.cur_desc = s_desc + (int64_t)2 * K * 32;      // frame 1 = row 2
-    lb.cur_ur = static_cast<const float*>(c->bufs["t_ur"].p) + K;
+    lb.cur_ur = bp.t_ur.p + K;
     lb.cur_obs = cobs + K; lb.cur_n = K;
     const int64_t M = 2 * (int64_t)K;
     lb.in_view = inv + M; lb.proj_x = px + M; lb.proj_y = py + M; lb.proj_xr = pxr + M; lb.level = lvl + M;
     lb.view_cos = vc + M; lb.nobs = lno + M; lb.mp_n = (int)M;
     lb.desc = s_desc;                                // frame 1's local map: KF2 = frame -1 (row 0), KF1 = frame 0
-    lb.match = lmatch + K; lb.nmatch = nloc + 1; lb.lists = lists; lb.err = derr; lb.path = lpath + 2;
+    lb.match = lmatch + K; lb.nmatch = tl.tl_nlocal.p + 1; lb.lists = tl.tl_lists.p; lb.err = c->ex.err.p;
+    lb.path = tl.tl_path.p + 2;
     lb.cur_n_arr = s_cnt + 1; lb.active = act + 1; lb.npairs = F - 1; lb.cur_stride = K; lb.mp_desc_stride = K;
     rc = launch_match_local(mcam, lb, th, nnratio, ps, &c->hook);
     if (rc == -2) return set_err(c, COEB_ERANGE, "coeb_track_local_map_batch_device: frame and local map exceed the LDS budget");
@@ -1754,11 +1581,9 @@ int coeb_track_local_map_batch_device(coeb_ctx* c, const coeb_camera* cam, int F
     PoseBufs b;
     const int64_t o = K;
     b.n = n2 + 1; b.has_mp = has2 + o; b.xw = xw2 + 3 * o;
-    b.kps = static_cast<const coeb_keypoint*>(c->bufs["t_kp"].p) + o; b.ur = static_cast<const float*>(c->bufs["t_ur"].p) + o;
-    b.inv_sigma2 = static_cast<const float*>(c->bufs["t_isg"].p); b.Tcw = T2 + 16; b.outlier = outl2 + o;
-    b.result = res2 + 1;
-    b.edges = static_cast<PoseEdgeRec*>(c->bufs["t_edge"].p) + o; b.active = static_cast<uint8_t*>(c->bufs["t_act"].p) + o;
-    b.chi2 = static_cast<double*>(c->bufs["t_chi"].p) + o; b.stride = K; b.timing = nullptr;
+    b.kps = bp.t_kp.p + o; b.ur = bp.t_ur.p + o;
+    b.inv_sigma2 = bp.t_isg.p; b.Tcw = T2 + 16; b.outlier = outl2 + o; b.result = tl.tl_res2.p + 1;
+    b.edges = bp.t_edge.p + o; b.active = bp.t_act.p + o; b.chi2 = bp.t_chi.p + o; b.stride = K; b.timing = nullptr;
     if (launch_pose(b, F - 1, cam->fx, cam->fy, cam->cx, cam->cy, cam->bf, ps, &c->hook))
         return hip_err(c, hipGetLastError(), "launch_pose");
     HIP_TRY(c, hipEventRecord(c->ev_pose, ps));
@@ -1772,12 +1597,12 @@ int coeb_batch_track_results(coeb_ctx* c, const float** d_Tcw, const int32_t** d
 {
     if (!c || !c->tlm_frames) return set_err(c, COEB_EINVAL, "coeb_batch_track_results: no batch TrackLocalMap yet");
     join_pose(c);
-    if (d_Tcw) *d_Tcw = static_cast<const float*>(c->bufs["tl_T2"].p);
-    if (d_ninliers) *d_ninliers = static_cast<const int32_t*>(c->bufs["tl_res2"].p);
-    if (d_nmatches_map) *d_nmatches_map = static_cast<const int32_t*>(c->bufs["tl_nmap"].p);
-    if (d_nlocal) *d_nlocal = static_cast<const int32_t*>(c->bufs["tl_nlocal"].p);
-    if (d_local_match) *d_local_match = static_cast<const int32_t*>(c->bufs["tl_lmatch"].p);
-    if (d_outlier) *d_outlier = static_cast<const uint8_t*>(c->bufs["tl_outl2"].p);
+    if (d_Tcw) *d_Tcw = c->tl.tl_T2.p;
+    if (d_ninliers) *d_ninliers = c->tl.tl_res2.p;
+    if (d_nmatches_map) *d_nmatches_map = c->tl.tl_nmap.p;
+    if (d_nlocal) *d_nlocal = c->tl.tl_nlocal.p;
+    if (d_local_match) *d_local_match = c->tl.tl_lmatch.p;
+    if (d_outlier) *d_outlier = c->tl.tl_outl2.p;
     return COEB_OK;
 }
 
@@ -2100,50 +1925,6 @@ int coeb_marker_synchronize(coeb_marker* m)
     return COEB_OK;
 }
 
-int coeb_internal_stream(coeb_ctx* c, hipStream_t* s, int* device)
-{
-    if (!c) return COEB_EINVAL;
-    *s = main_stream(c);
-    *device = c->device;
-    return COEB_OK;
-}
-
-// The side stream for the moving-object batch's LK pyramids, with the context's fork / join events
-// (created on first use), when COEB_FLOW_SIDE=1; nonzero otherwise (also with the side stream off
-// or per-kernel profiling), and then everything stays on the context stream.  Off by default: config
-// D's step measured 13.30-13.37 ms with the fork against 13.10-13.30 without (profiles/r05/s24): the
-// step is bound by the kernels' combined demand for CUs, not by the context stream's chain.
-int coeb_internal_flow_side(coeb_ctx* c, hipStream_t* side, hipEvent_t* fork, hipEvent_t* join)
-{
-    if (!c) return COEB_EINVAL;
-    const char* e = coeb_experiment("COEB_FLOW_SIDE");
-    if (!(e && e[0] == '1')) return 1;
-    const SideStream* sd = side_stream(c);
-    if (!sd) return 1;
-    if (!c->ev_ffork && (hipEventCreateWithFlags(&c->ev_ffork, hipEventDisableTiming) != hipSuccess ||
-                         hipEventCreateWithFlags(&c->ev_fjoin, hipEventDisableTiming) != hipSuccess)) {
-        if (c->ev_ffork) (void)hipEventDestroy(c->ev_ffork);
-        c->ev_ffork = c->ev_fjoin = nullptr;
-        return 1;
-    }
-    *side = sd->s;
-    *fork = c->ev_ffork;
-    *join = c->ev_fjoin;
-    return 0;
-}
-
-int coeb_internal_scratch(coeb_ctx* c, const char* name, size_t bytes, void** p)
-{
-    uint8_t* q;
-    int rc = ensure(c, name, bytes, &q);
-    *p = q;
-    return rc;
-}
-
-int coeb_internal_error(coeb_ctx* c, int code, const char* msg) { return set_err(c, code, msg); }
-
-ProfileHook* coeb_internal_prof(coeb_ctx* c) { return c ? &c->hook : nullptr; }
-
 /* Debug readback of intermediate buffers of frame f of the last batch (test support):
  * what = "pyr" | "blur" | "cand_n" | "lvl_n" | "lvl_kp" | "dyn"; copies min(bytes, size). */
 int coeb_debug_read(coeb_ctx* c, const char* what, int f, void* host, size_t bytes, size_t* size_out)
@@ -2161,7 +1942,7 @@ int coeb_debug_read(coeb_ctx* c, const char* what, int f, void* host, size_t byt
     if (c && what && std::string(what) == "flow_counts") {     // [pairs][2] {Harris keys, corners}
         static thread_local int t[2 * 8192];
         int np = 0;
-        int rc = coeb_internal_flow_counts(c, t, 2 * 8192, &np);
+        int rc = flow_counts(c, t, 2 * 8192, &np);
         if (rc) return rc;
         const size_t n = (size_t)std::min(np, 8192) * 8;
         if (size_out) *size_out = n;
@@ -2177,34 +1958,24 @@ int coeb_debug_read(coeb_ctx* c, const char* what, int f, void* host, size_t byt
         memcpy(host, t, std::min(bytes, sizeof(t)));
         return 0;
     }
-    if (c && what && std::string(what) == "pose_timing") {      // [F][8] k_pose phase clocks (COEB_POSE_TIMING)
-        if (!c->bufs.count("p_timing")) return COEB_EINVAL;
-        join_pose(c);
-        const size_t nb = c->bufs["p_timing"].n;
-        if (size_out) *size_out = nb;
+    if (c && what && (std::string(what) == "pose_timing" || std::string(what) == "match_timing")) {
+        // [F][8] k_pose phase clocks (COEB_POSE_TIMING) / [F][16] k_match phase clocks (COEB_MATCH_TIMING)
+        const DevArr<long long>& t = what[0] == 'p' ? c->tim.p_timing : c->tim.m_timing;
+        if (!t.p) return COEB_EINVAL;
+        if (size_out) *size_out = t.bytes;
         if (host && bytes) {
             HIP_TRY(c, hipStreamSynchronize(main_stream(c)));
-            HIP_TRY(c, hipMemcpy(host, c->bufs["p_timing"].p, std::min(bytes, nb), hipMemcpyDeviceToHost));
-        }
-        return COEB_OK;
-    }
-    if (c && what && std::string(what) == "match_timing") {     // [F][16] k_match phase clocks (COEB_MATCH_TIMING)
-        if (!c->bufs.count("m_timing")) return COEB_EINVAL;
-        const size_t nb = c->bufs["m_timing"].n;
-        if (size_out) *size_out = nb;
-        if (host && bytes) {
-            HIP_TRY(c, hipStreamSynchronize(main_stream(c)));
-            HIP_TRY(c, hipMemcpy(host, c->bufs["m_timing"].p, std::min(bytes, nb), hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(host, t.p, std::min(bytes, t.bytes), hipMemcpyDeviceToHost));
         }
         return COEB_OK;
     }
     if (c && what && (std::string(what) == "search_path" || std::string(what) == "localmap_path")) {
         // {path, iterations} of the last coeb_match_localmap / coeb_match_keyframe
-        if (!c->bufs.count("l_path")) return COEB_EINVAL;
+        if (!c->sf.l_path.p) return COEB_EINVAL;
         if (size_out) *size_out = 8;
         if (host && bytes) {
             HIP_TRY(c, hipStreamSynchronize(main_stream(c)));
-            HIP_TRY(c, hipMemcpy(host, c->bufs["l_path"].p, std::min(bytes, (size_t)8), hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(host, c->sf.l_path.p, std::min(bytes, (size_t)8), hipMemcpyDeviceToHost));
         }
         return COEB_OK;
     }
@@ -2214,13 +1985,13 @@ int coeb_debug_read(coeb_ctx* c, const char* what, int f, void* host, size_t byt
     const uint8_t* src = nullptr;
     size_t n = 0;
     std::string w(what);
-    if (w == "pyr") { src = (const uint8_t*)c->bufs["pyr"].p + (size_t)f * P.pyr_stride; n = P.pyr_stride; }
+    if (w == "pyr") { src = c->ex.pyr.p + (size_t)f * P.pyr_stride; n = P.pyr_stride; }
     else if (w == "blur") {
         // the blurred levels row-major at their pitch, each 256-B aligned (the device copy is tiled,
         // blur_tile_off)
         std::vector<uint8_t> raw(P.blur_stride);
         HIP_TRY(c, hipStreamSynchronize(main_stream(c)));
-        HIP_TRY(c, hipMemcpy(raw.data(), (const uint8_t*)c->bufs["blur"].p + (size_t)f * P.blur_stride, raw.size(),
+        HIP_TRY(c, hipMemcpy(raw.data(), c->ex.blur.p + (size_t)f * P.blur_stride, raw.size(),
                              hipMemcpyDeviceToHost));
         std::vector<uint8_t> rm;
         size_t off = 0;
@@ -2237,10 +2008,10 @@ int coeb_debug_read(coeb_ctx* c, const char* what, int f, void* host, size_t byt
         if (host && bytes) memcpy(host, rm.data(), std::min(bytes, rm.size()));
         return COEB_OK;
     }
-    else if (w == "cand_n") { src = (const uint8_t*)c->bufs["cand_n"].p + (size_t)f * P.ncells * 4; n = (size_t)P.ncells * 4; }
-    else if (w == "lvl_n") { src = (const uint8_t*)c->bufs["lvl_n"].p + (size_t)f * P.L * 4; n = (size_t)P.L * 4; }
-    else if (w == "lvl_kp") { src = (const uint8_t*)c->bufs["lvl_kp"].p + (size_t)f * P.lvl_stride * 4; n = (size_t)P.lvl_stride * 4; }
-    else if (w == "dyn") { src = (const uint8_t*)c->bufs["dyn"].p + (size_t)f * sizeof(DynMask); n = sizeof(DynMask); }
+    else if (w == "cand_n") { src = (const uint8_t*)c->ex.cand_n.p + (size_t)f * P.ncells * 4; n = (size_t)P.ncells * 4; }
+    else if (w == "lvl_n") { src = (const uint8_t*)c->ex.lvl_n.p + (size_t)f * P.L * 4; n = (size_t)P.L * 4; }
+    else if (w == "lvl_kp") { src = (const uint8_t*)c->ex.lvl_kp.p + (size_t)f * P.lvl_stride * 4; n = (size_t)P.lvl_stride * 4; }
+    else if (w == "dyn") { src = (const uint8_t*)c->ex.dyn.p + (size_t)f * sizeof(DynMask); n = sizeof(DynMask); }
     else if (w == "plan") { if (size_out) *size_out = sizeof(Plan); if (host) memcpy(host, &P, std::min(bytes, sizeof(Plan))); return COEB_OK; }
     else return COEB_EINVAL;
     if (size_out) *size_out = n;

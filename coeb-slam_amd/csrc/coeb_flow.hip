@@ -34,19 +34,8 @@
 #include <cstdlib>
 #include <cmath>
 #include <cstring>
-#include <array>
-#include <map>
-#include <mutex>
 
-#include "../../include/coeb_front.h"
-#include "coeb_internal.hpp"
-
-extern "C" int coeb_internal_stream(coeb_ctx* c, hipStream_t* s, int* device);
-extern "C" int coeb_internal_scratch(coeb_ctx* c, const char* name, size_t bytes, void** p);
-extern "C" int coeb_internal_error(coeb_ctx* c, int code, const char* msg);
-extern "C" ProfileHook* coeb_internal_prof(coeb_ctx* c);
-extern "C" void coeb_internal_flow_forget(const coeb_ctx* c);
-extern "C" int coeb_internal_flow_side(coeb_ctx* c, hipStream_t* side, hipEvent_t* fork, hipEvent_t* join);
+#include "coeb_ctx.hpp"
 
 namespace {
 
@@ -1840,12 +1829,11 @@ int flow_alloc(coeb_ctx* c, int w, int h, FlowDev* d, int npairs = 1)
     size_t pair_bytes = 0, shared_bytes = 0;
     for (size_t v : sizes) pair_bytes += v;
     for (size_t v : shared) shared_bytes += v;
-    void* base;
     // npairs + 1 blocks: a batch's pyramids are kept per frame, pair z's next frame being pair
     // z + 1's previous one (launch_lk), so frame `npairs` needs a block of its own
-    const int rc = coeb_internal_scratch(c, "flow", shared_bytes + pair_bytes * (size_t)(npairs + 1), &base);
+    const int rc = ensure(c, c->hl.flow, shared_bytes + pair_bytes * (size_t)(npairs + 1));
     if (rc) return rc;
-    uint8_t* p = (uint8_t*)base;
+    uint8_t* p = c->hl.flow.p;
     size_t o = 0;
     d->prev = p + o; o += shared[0];
     d->cur = p + o; o += shared[1];
@@ -1861,7 +1849,7 @@ int flow_alloc(coeb_ctx* c, int w, int h, FlowDev* d, int npairs = 1)
     d->tm = (float*)take(); d->ntm = (int*)take(); d->F = (double*)take(); d->nf = (int*)take();
     d->npairs = npairs;
     d->pz = (int64_t)pair_bytes;
-    d->prof = coeb_internal_prof(c);
+    d->prof = &c->hook;
     return COEB_OK;
 }
 
@@ -1947,7 +1935,7 @@ int launch_subpix(const FlowDev* d, const uint8_t* img, int w, int h, int stride
 
 // LK pyramids of both frames (pyrDown levels and the Scharr derivatives of every level): they read
 // only the images, so a batch builds them on a second stream beside goodFeaturesToTrack and
-// cornerSubPix (coeb_internal_pmo_batch); `pyr` is filled for launch_lk_track.
+// cornerSubPix (pmo_batch); `pyr` is filled for launch_lk_track.
 int launch_lk_pyramids(const FlowDev* d, const uint8_t* prev, const uint8_t* cur, int w, int h, int stride, int win,
                        int max_level, hipStream_t s, int64_t iz, LkPyr& pyr)
 {
@@ -2032,7 +2020,7 @@ int launch_fm(const FlowDev* d, const uint8_t* prev, const uint8_t* cur, int w, 
 #define FL_TRY(c, x)                                                                          \
     do {                                                                                      \
         const hipError_t e_ = (x);                                                            \
-        if (e_ != hipSuccess) return coeb_internal_error(c, COEB_EDEVICE, hipGetErrorString(e_)); \
+        if (e_ != hipSuccess) return set_err(c, COEB_EDEVICE, hipGetErrorString(e_));             \
     } while (0)
 
 struct FlowCall {
@@ -2042,13 +2030,13 @@ struct FlowCall {
 
 int flow_begin(coeb_ctx* c, int w, int h, FlowCall* fc, const char* who)
 {
-    int dev;
-    if (coeb_internal_stream(c, &fc->s, &dev)) return coeb_internal_error(c, COEB_EINVAL, who);
-    (void)hipSetDevice(dev);
-    if (w < 32 || h < 32 || (size_t)w * h > (size_t)1 << 26) return coeb_internal_error(c, COEB_EINVAL, who);
+    if (!c) return set_err(c, COEB_EINVAL, who);
+    fc->s = main_stream(c);
+    (void)hipSetDevice(c->device);
+    if (w < 32 || h < 32 || (size_t)w * h > (size_t)1 << 26) return set_err(c, COEB_EINVAL, who);
     // a single-pair call rewrites the flow scratch with npairs = 1: the last batch's geometry
-    // no longer describes it, so coeb_internal_flow_counts must refuse rather than misread
-    coeb_internal_flow_forget(c);
+    // no longer describes it, so flow_counts must refuse rather than misread
+    c->pmo_last.pairs = 0;
     return flow_alloc(c, w, h, &fc->d);
 }
 
@@ -2064,19 +2052,19 @@ extern "C" int coeb_good_features(coeb_ctx* c, const uint8_t* img, int w, int h,
                                   double quality, double min_distance, double k, float* xy_out, int cap, int* n_out)
 {
     if (!c || !img || !n_out || (cap > 0 && !xy_out) || stride < (size_t)w || quality <= 0 || min_distance < 1)
-        return coeb_internal_error(c, COEB_EINVAL, "coeb_good_features: invalid arguments");
+        return set_err(c, COEB_EINVAL, "coeb_good_features: invalid arguments");
     if (max_corners <= 0 || max_corners > kMaxPts)
-        return coeb_internal_error(c, COEB_EINVAL, "coeb_good_features: max_corners must be in 1..1024");
+        return set_err(c, COEB_EINVAL, "coeb_good_features: max_corners must be in 1..1024");
     FlowCall fc;
     int rc = flow_begin(c, w, h, &fc, "coeb_good_features: invalid arguments");
     if (rc) return rc;
     if ((rc = upload_gray(c, fc.s, fc.d.prev, img, w, h, stride))) return rc;
     if (launch_gf(&fc.d, fc.d.prev, w, h, w, max_corners, quality, min_distance, k, fc.s))
-        return coeb_internal_error(c, COEB_EDEVICE, "coeb_good_features: launch failed");
+        return set_err(c, COEB_EDEVICE, "coeb_good_features: launch failed");
     int n = 0;
     FL_TRY(c, hipMemcpyAsync(&n, fc.d.npts, 4, hipMemcpyDeviceToHost, fc.s));
     FL_TRY(c, hipStreamSynchronize(fc.s));
-    if (n < 0) return coeb_internal_error(c, COEB_ERANGE, "coeb_good_features: more local maxima than the exact selection covers");
+    if (n < 0) return set_err(c, COEB_ERANGE, "coeb_good_features: more local maxima than the exact selection covers");
     if (n > 0 && cap > 0) {
         FL_TRY(c, hipMemcpyAsync(xy_out, fc.d.pts, (size_t)(n < cap ? n : cap) * 8, hipMemcpyDeviceToHost, fc.s));
         FL_TRY(c, hipStreamSynchronize(fc.s));
@@ -2089,8 +2077,8 @@ extern "C" int coeb_corner_subpix(coeb_ctx* c, const uint8_t* img, int w, int h,
                                   int win, int max_iter, double eps)
 {
     if (!c || !img || n < 0 || n > kMaxPts || (n > 0 && !xy) || stride < (size_t)w)
-        return coeb_internal_error(c, COEB_EINVAL, "coeb_corner_subpix: invalid arguments");
-    if (win != 10) return coeb_internal_error(c, COEB_EINVAL, "coeb_corner_subpix: window 10 only (Frame.cc:334)");
+        return set_err(c, COEB_EINVAL, "coeb_corner_subpix: invalid arguments");
+    if (win != 10) return set_err(c, COEB_EINVAL, "coeb_corner_subpix: window 10 only (Frame.cc:334)");
     if (n == 0) return COEB_OK;
     FlowCall fc;
     int rc = flow_begin(c, w, h, &fc, "coeb_corner_subpix: invalid arguments");
@@ -2102,7 +2090,7 @@ extern "C" int coeb_corner_subpix(coeb_ctx* c, const uint8_t* img, int w, int h,
     FL_TRY(c, hipMemcpyAsync(fc.d.pts, xy, (size_t)n * 8, hipMemcpyHostToDevice, fc.s));
     FL_TRY(c, hipMemcpyAsync(fc.d.npts, &n, 4, hipMemcpyHostToDevice, fc.s));
     if (launch_subpix(&fc.d, fc.d.prev, w, h, w, max_iter, eps, fc.s))
-        return coeb_internal_error(c, COEB_EDEVICE, "coeb_corner_subpix: launch failed");
+        return set_err(c, COEB_EDEVICE, "coeb_corner_subpix: launch failed");
     FL_TRY(c, hipMemcpyAsync(xy, fc.d.pts, (size_t)n * 8, hipMemcpyDeviceToHost, fc.s));
     FL_TRY(c, hipStreamSynchronize(fc.s));
     return COEB_OK;
@@ -2114,21 +2102,21 @@ extern "C" int coeb_optical_flow_pyr_lk(coeb_ctx* c, const uint8_t* prev, const 
 {
     if (!c || !prev || !next || n < 0 || n > kMaxPts || (n > 0 && (!prev_xy || !next_xy || !status)) ||
         stride < (size_t)w || max_level < 0 || max_count < 1)
-        return coeb_internal_error(c, COEB_EINVAL, "coeb_optical_flow_pyr_lk: invalid arguments");
+        return set_err(c, COEB_EINVAL, "coeb_optical_flow_pyr_lk: invalid arguments");
     if (win < 3 || win * win > 512)
-        return coeb_internal_error(c, COEB_EINVAL, "coeb_optical_flow_pyr_lk: window must be 3..22");
+        return set_err(c, COEB_EINVAL, "coeb_optical_flow_pyr_lk: window must be 3..22");
     if (n == 0) return COEB_OK;
     FlowCall fc;
     int rc = flow_begin(c, w, h, &fc, "coeb_optical_flow_pyr_lk: invalid arguments");
     if (rc) return rc;
     if (lk_levels(w, h, win, max_level) > kLkMaxLevels)
-        return coeb_internal_error(c, COEB_EINVAL, "coeb_optical_flow_pyr_lk: more than 8 pyramid levels");
+        return set_err(c, COEB_EINVAL, "coeb_optical_flow_pyr_lk: more than 8 pyramid levels");
     if ((rc = upload_gray(c, fc.s, fc.d.prev, prev, w, h, stride)) || (rc = upload_gray(c, fc.s, fc.d.cur, next, w, h, stride)))
         return rc;
     FL_TRY(c, hipMemcpyAsync(fc.d.pts, prev_xy, (size_t)n * 8, hipMemcpyHostToDevice, fc.s));
     FL_TRY(c, hipMemcpyAsync(fc.d.npts, &n, 4, hipMemcpyHostToDevice, fc.s));
     if (launch_lk(&fc.d, fc.d.prev, fc.d.cur, w, h, w, win, max_level, max_count, eps, fc.s))
-        return coeb_internal_error(c, COEB_EDEVICE, "coeb_optical_flow_pyr_lk: launch failed");
+        return set_err(c, COEB_EDEVICE, "coeb_optical_flow_pyr_lk: launch failed");
     FL_TRY(c, hipMemcpyAsync(next_xy, fc.d.nxt, (size_t)n * 8, hipMemcpyDeviceToHost, fc.s));
     FL_TRY(c, hipMemcpyAsync(status, fc.d.status, (size_t)n, hipMemcpyDeviceToHost, fc.s));
     FL_TRY(c, hipStreamSynchronize(fc.s));
@@ -2141,7 +2129,7 @@ extern "C" int coeb_moving_tail(coeb_ctx* c, const uint8_t* prev, const uint8_t*
 {
     if (!c || !prev || !cur || n < 0 || n > kMaxPts || (n > 0 && (!prev_xy || !next_xy || !state)) || !n_tm ||
         (tm_cap > 0 && !tm_xy) || stride < (size_t)w)
-        return coeb_internal_error(c, COEB_EINVAL, "coeb_moving_tail: invalid arguments");
+        return set_err(c, COEB_EINVAL, "coeb_moving_tail: invalid arguments");
     FlowCall fc;
     int rc = flow_begin(c, w, h, &fc, "coeb_moving_tail: invalid arguments");
     if (rc) return rc;
@@ -2154,7 +2142,7 @@ extern "C" int coeb_moving_tail(coeb_ctx* c, const uint8_t* prev, const uint8_t*
     }
     FL_TRY(c, hipMemcpyAsync(fc.d.npts, &n, 4, hipMemcpyHostToDevice, fc.s));
     if (launch_fm(&fc.d, fc.d.prev, fc.d.cur, w, h, w, 5, 2120.0, fc.s, kMaxPts))
-        return coeb_internal_error(c, COEB_EDEVICE, "coeb_moving_tail: launch failed");
+        return set_err(c, COEB_EDEVICE, "coeb_moving_tail: launch failed");
     int nt = 0, nf = 0;
     double F[9];
     FL_TRY(c, hipMemcpyAsync(&nt, fc.d.ntm, 4, hipMemcpyDeviceToHost, fc.s));
@@ -2176,12 +2164,12 @@ extern "C" int coeb_moving_object_points(coeb_ctx* c, const uint8_t* prev, const
                                          size_t stride, float* tm_xy, int tm_cap, int* n_tm, coeb_flow_debug* dbg)
 {
     if (!c || !prev || !cur || !n_tm || (tm_cap > 0 && !tm_xy) || stride < (size_t)w)
-        return coeb_internal_error(c, COEB_EINVAL, "coeb_moving_object_points: invalid arguments");
+        return set_err(c, COEB_EINVAL, "coeb_moving_object_points: invalid arguments");
     FlowCall fc;
     int rc = flow_begin(c, w, h, &fc, "coeb_moving_object_points: invalid arguments");
     if (rc) return rc;
     if (lk_levels(w, h, 22, 5) > kLkMaxLevels)
-        return coeb_internal_error(c, COEB_EINVAL, "coeb_moving_object_points: image too large");
+        return set_err(c, COEB_EINVAL, "coeb_moving_object_points: image too large");
     float mask[21];
     subpix_mask(10, mask);
     if ((rc = upload_gray(c, fc.s, fc.d.prev, prev, w, h, stride)) || (rc = upload_gray(c, fc.s, fc.d.cur, cur, w, h, stride)))
@@ -2203,87 +2191,86 @@ extern "C" int coeb_internal_subpix_count(int* out)
     return hipMemcpyToSymbol(HIP_SYMBOL(g_subpix_count_dev), z, 16) == hipSuccess ? COEB_OK : COEB_EDEVICE;
 }
 
-// geometry of each context's last moving-object batch, for coeb_internal_flow_counts
-static std::mutex g_pmo_mu;
-static std::map<const coeb_ctx*, std::array<int, 3>> g_pmo_last;
-
-extern "C" void coeb_internal_flow_forget(const coeb_ctx* c)   // coeb_destroy
-{
-    std::lock_guard<std::mutex> lk(g_pmo_mu);
-    g_pmo_last.erase(c);
-}
-
 // Per pair of the context's last moving-object batch: {Harris candidate keys, corners} (bench.py's
 // algorithmic bytes of k_gf_select / k_subpix / k_lk / k_fm).  Synchronises the context stream.
-extern "C" int coeb_internal_flow_counts(coeb_ctx* c, int* out, int cap, int* npairs)
+int flow_counts(coeb_ctx* c, int* out, int cap, int* npairs)
 {
-    std::array<int, 3> g;
-    {
-        std::lock_guard<std::mutex> lk(g_pmo_mu);
-        auto it = g_pmo_last.find(c);
-        if (it == g_pmo_last.end()) return COEB_EINVAL;
-        g = it->second;
-    }
+    const auto g = c->pmo_last;
+    if (!g.pairs) return COEB_EINVAL;
     FlowCall fc;
-    int dev;
-    if (coeb_internal_stream(c, &fc.s, &dev)) return COEB_EINVAL;
-    (void)hipSetDevice(dev);
-    int rc = flow_alloc(c, g[0], g[1], &fc.d, g[2]);
+    fc.s = main_stream(c);
+    (void)hipSetDevice(c->device);
+    int rc = flow_alloc(c, g.w, g.h, &fc.d, g.pairs);
     if (rc) return rc;
-    *npairs = g[2];
+    *npairs = g.pairs;
     FL_TRY(c, hipStreamSynchronize(fc.s));
-    for (int z = 0; z < g[2] && 2 * z + 1 < cap; z++) {
+    for (int z = 0; z < g.pairs && 2 * z + 1 < cap; z++) {
         FL_TRY(c, hipMemcpy(out + 2 * z, (const uint8_t*)fc.d.nkeys + (size_t)z * fc.d.pz, 4, hipMemcpyDeviceToHost));
         FL_TRY(c, hipMemcpy(out + 2 * z + 1, (const uint8_t*)fc.d.npts + (size_t)z * fc.d.pz, 4, hipMemcpyDeviceToHost));
     }
     return COEB_OK;
 }
 
-extern "C" int coeb_internal_pmo_batch(coeb_ctx* c, const uint8_t* d_gray, int F, int w, int h, float* tm_out,
-                                       int* ntm_out, int tm_cap)
+// The side stream for the moving-object batch's LK pyramids, with the context's fork / join events
+// (created on first use), when COEB_FLOW_SIDE=1; null otherwise (also with the side stream off
+// or per-kernel profiling), and then everything stays on the context stream.  Off by default: config
+// D's step measured 13.30-13.37 ms with the fork against 13.10-13.30 without (profiles/r05/s24): the
+// step is bound by the kernels' combined demand for CUs, not by the context stream's chain.
+static hipStream_t flow_side(coeb_ctx* c)
+{
+    const char* e = coeb_experiment("COEB_FLOW_SIDE");
+    if (!(e && e[0] == '1')) return nullptr;
+    const SideStream* sd = side_stream(c);
+    if (!sd) return nullptr;
+    if (!c->ev_ffork && (hipEventCreateWithFlags(&c->ev_ffork, hipEventDisableTiming) != hipSuccess ||
+                         hipEventCreateWithFlags(&c->ev_fjoin, hipEventDisableTiming) != hipSuccess)) {
+        if (c->ev_ffork) (void)hipEventDestroy(c->ev_ffork);
+        c->ev_ffork = c->ev_fjoin = nullptr;
+        return nullptr;
+    }
+    return sd->s;
+}
+
+int pmo_batch(coeb_ctx* c, const uint8_t* d_gray, int F, int w, int h, float* tm_out, int* ntm_out, int tm_cap)
 {
     if (F < 1 || !d_gray || !tm_out || !ntm_out || tm_cap < 1 || tm_cap > kMaxPts)
-        return coeb_internal_error(c, COEB_EINVAL, "moving-object batch: invalid arguments");
+        return set_err(c, COEB_EINVAL, "moving-object batch: invalid arguments");
     FlowCall fc;
-    int dev;
-    if (coeb_internal_stream(c, &fc.s, &dev)) return COEB_EINVAL;
-    (void)hipSetDevice(dev);
+    fc.s = main_stream(c);
+    (void)hipSetDevice(c->device);
     FL_TRY(c, hipMemsetAsync(ntm_out, 0, 4, fc.s));
     if (F < 2) return COEB_OK;
     if (w < 32 || h < 32 || lk_levels(w, h, 22, 5) > kLkMaxLevels)
-        return coeb_internal_error(c, COEB_EINVAL, "moving-object batch: frame size");
+        return set_err(c, COEB_EINVAL, "moving-object batch: frame size");
     int rc = flow_alloc(c, w, h, &fc.d, F - 1);
     if (rc) return rc;
-    {
-        std::lock_guard<std::mutex> lk(g_pmo_mu);
-        g_pmo_last[c] = {w, h, F - 1};
-    }
+    c->pmo_last = {w, h, F - 1};
     float mask[21];
     subpix_mask(10, mask);
     FL_TRY(c, hipMemcpyAsync(fc.d.mexp, mask, kSubpixMaskBytes, hipMemcpyHostToDevice, fc.s));
     const int64_t iz = (int64_t)w * h;
     // COEB_FLOW_SIDE=1: the LK pyramids go to the context's side stream (idle until extraction)
     // beside the corner detection, and the context stream joins them before k_lk (measured slower)
-    hipStream_t side = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
-    const bool split = coeb_internal_flow_side(c, &side, &fork, &join) == 0;
+    hipStream_t side = flow_side(c);
+    hipEvent_t fork = c->ev_ffork, join = c->ev_fjoin;
+    const bool split = side != nullptr;
     LkPyr pyr;
     if (split) {
         FL_TRY(c, hipEventRecord(fork, fc.s));
         FL_TRY(c, hipStreamWaitEvent(side, fork, 0));
         if (launch_lk_pyramids(&fc.d, d_gray, d_gray + iz, w, h, w, 22, 5, side, iz, pyr))
-            return coeb_internal_error(c, COEB_EDEVICE, "moving-object batch: launch failed");
+            return set_err(c, COEB_EDEVICE, "moving-object batch: launch failed");
         FL_TRY(c, hipEventRecord(join, side));
     }
     if (launch_gf(&fc.d, d_gray, w, h, w, 1000, 0.01, 8.0, 0.04, fc.s, iz) ||
         launch_subpix(&fc.d, d_gray, w, h, w, 20, 0.03, fc.s, iz))
-        return coeb_internal_error(c, COEB_EDEVICE, "moving-object batch: launch failed");
+        return set_err(c, COEB_EDEVICE, "moving-object batch: launch failed");
     if (split) FL_TRY(c, hipStreamWaitEvent(fc.s, join, 0));
     if ((split ? launch_lk_track(&fc.d, pyr, 22, 20, 0.01, fc.s, iz)
                : launch_lk(&fc.d, d_gray, d_gray + iz, w, h, w, 22, 5, 20, 0.01, fc.s, iz)) ||
         launch_fm(&fc.d, d_gray, d_gray + iz, w, h, w, 5, 2120.0, fc.s, tm_cap, iz, tm_out + (size_t)tm_cap * 2,
                   ntm_out + 1))
-        return coeb_internal_error(c, COEB_EDEVICE, "moving-object batch: launch failed");
+        return set_err(c, COEB_EDEVICE, "moving-object batch: launch failed");
     return COEB_OK;
 }
 
@@ -2293,25 +2280,25 @@ extern "C" int coeb_moving_object_points_device(coeb_ctx* c, const uint8_t* d_pr
                                                 coeb_flow_debug* dbg)
 {
     if (!c || !d_prev || !d_cur || !n_tm || (tm_cap > 0 && !tm_xy) || stride < (size_t)w)
-        return coeb_internal_error(c, COEB_EINVAL, "coeb_moving_object_points_device: invalid arguments");
+        return set_err(c, COEB_EINVAL, "coeb_moving_object_points_device: invalid arguments");
     FlowCall fc;
     int rc = flow_begin(c, w, h, &fc, "coeb_moving_object_points_device: invalid arguments");
     if (rc) return rc;
     if (lk_levels(w, h, 22, 5) > kLkMaxLevels)
-        return coeb_internal_error(c, COEB_EINVAL, "coeb_moving_object_points_device: image too large");
+        return set_err(c, COEB_EINVAL, "coeb_moving_object_points_device: image too large");
     float mask[21];
     subpix_mask(10, mask);
     FL_TRY(c, hipMemcpyAsync(fc.d.mexp, mask, kSubpixMaskBytes, hipMemcpyHostToDevice, fc.s));
     const int sp = (int)stride;
     if (launch_gf(&fc.d, d_prev, w, h, sp, 1000, 0.01, 8.0, 0.04, fc.s))
-        return coeb_internal_error(c, COEB_EDEVICE, "coeb_moving_object_points: goodFeaturesToTrack launch failed");
+        return set_err(c, COEB_EDEVICE, "coeb_moving_object_points: goodFeaturesToTrack launch failed");
     if (dbg && dbg->corners_raw) {
         FL_TRY(c, hipMemcpyAsync(dbg->corners_raw, fc.d.pts, (size_t)1000 * 8, hipMemcpyDeviceToHost, fc.s));
     }
     if (launch_subpix(&fc.d, d_prev, w, h, sp, 20, 0.03, fc.s) ||
         launch_lk(&fc.d, d_prev, d_cur, w, h, sp, 22, 5, 20, 0.01, fc.s) ||
         launch_fm(&fc.d, d_prev, d_cur, w, h, sp, 5, 2120.0, fc.s, kMaxPts))
-        return coeb_internal_error(c, COEB_EDEVICE, "coeb_moving_object_points: launch failed");
+        return set_err(c, COEB_EDEVICE, "coeb_moving_object_points: launch failed");
     int nt = 0, nc = 0;
     FL_TRY(c, hipMemcpyAsync(&nt, fc.d.ntm, 4, hipMemcpyDeviceToHost, fc.s));
     FL_TRY(c, hipMemcpyAsync(&nc, fc.d.npts, 4, hipMemcpyDeviceToHost, fc.s));
@@ -2324,7 +2311,7 @@ extern "C" int coeb_moving_object_points_device(coeb_ctx* c, const uint8_t* d_pr
         if (dbg->nf) FL_TRY(c, hipMemcpyAsync(dbg->nf, fc.d.nf, 4, hipMemcpyDeviceToHost, fc.s));
     }
     FL_TRY(c, hipStreamSynchronize(fc.s));
-    if (nc < 0) return coeb_internal_error(c, COEB_ERANGE, "coeb_moving_object_points: more local maxima than the exact selection covers");
+    if (nc < 0) return set_err(c, COEB_ERANGE, "coeb_moving_object_points: more local maxima than the exact selection covers");
     if (dbg && dbg->ncorners) *dbg->ncorners = nc;
     if (nt > 0 && tm_cap > 0) {
         FL_TRY(c, hipMemcpyAsync(tm_xy, fc.d.tm, (size_t)(nt < tm_cap ? nt : tm_cap) * 8, hipMemcpyDeviceToHost, fc.s));

@@ -9,8 +9,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/coeb_front.h"
-#include "coeb_internal.hpp"
+#include "coeb_ctx.hpp"
 
 namespace {
 
@@ -239,17 +238,11 @@ __global__ __launch_bounds__(256) void k_undistort(const KpRec* __restrict__ in,
 
 }  // namespace
 
-// host entry points (C-ABI); context internals are reached through small accessors in
-// coeb_capi.hip
-extern "C" int coeb_internal_stream(coeb_ctx* c, hipStream_t* s, int* device);
-extern "C" int coeb_internal_scratch(coeb_ctx* c, const char* name, size_t bytes, void** p);
-extern "C" int coeb_internal_error(coeb_ctx* c, int code, const char* msg);
-extern "C" ProfileHook* coeb_internal_prof(coeb_ctx* c);
-
-#define FR_TRY(c, expr)                                                                         \
-    do {                                                                                        \
-        hipError_t _e = (expr);                                                                 \
-        if (_e != hipSuccess) return coeb_internal_error((c), COEB_EDEVICE, hipGetErrorString(_e)); \
+// host entry points (C-ABI)
+#define FR_TRY(c, expr)                                                                 \
+    do {                                                                                \
+        hipError_t _e = (expr);                                                         \
+        if (_e != hipSuccess) return set_err((c), COEB_EDEVICE, hipGetErrorString(_e)); \
     } while (0)
 
 // box -> frame map of a batch from its box offsets (frame f owns boxes [box_off[f], box_off[f+1]))
@@ -263,13 +256,12 @@ __global__ __launch_bounds__(256) void k_box_frame(const int* __restrict__ box_o
 // The blur flags of every box of a device-resident batch (packed W x H frames): frame f's boxes
 // are [d_box_off[f], d_box_off[f+1]) of d_boxes (device arrays); d_box_frame is scratch for nbox
 // ints; frame 0's boxes get 0.  Enqueued on stream s, nothing staged from the host.
-extern "C" int coeb_internal_blur_flags_batch(coeb_ctx* c, const uint8_t* d_gray, int W, int H, const float* d_boxes,
-                                              const int* d_box_off, int F, int* d_box_frame, int nbox, int* d_out,
-                                              hipStream_t s)
+int blur_flags_batch(coeb_ctx* c, const uint8_t* d_gray, int W, int H, const float* d_boxes, const int* d_box_off, int F,
+                     int* d_box_frame, int nbox, int* d_out, hipStream_t s)
 {
     if (nbox <= 0) return COEB_OK;
     hipLaunchKernelGGL(k_box_frame, dim3((F + 255) / 256), dim3(256), 0, s, d_box_off, F, d_box_frame);
-    ProfileHook* prof = coeb_internal_prof(c);
+    ProfileHook* prof = &c->hook;
     prof_begin(prof, "k_blur_flags", s);
     hipLaunchKernelGGL(k_blur_flags, dim3(nbox), dim3(256), 0, s, d_gray, W, H, W, d_boxes, d_out, (double*)nullptr,
                        (const int*)d_box_frame, (int64_t)W * H);
@@ -281,24 +273,21 @@ extern "C" int coeb_blur_flags(coeb_ctx* c, const uint8_t* gray, int W, int H, s
                                int nbox, int32_t* flags_out)
 {
     if (!c || nbox < 0 || (nbox > 0 && (!gray || !boxes || !flags_out)) || stride < (size_t)W)
-        return coeb_internal_error(c, COEB_EINVAL, "coeb_blur_flags: invalid arguments");
+        return set_err(c, COEB_EINVAL, "coeb_blur_flags: invalid arguments");
     if (nbox == 0) return COEB_OK;
-    hipStream_t s;
-    int dev;
-    if (coeb_internal_stream(c, &s, &dev)) return COEB_EINVAL;
-    (void)hipSetDevice(dev);
-    void *dimg, *dbox, *dout;
+    hipStream_t s = main_stream(c);
+    (void)hipSetDevice(c->device);
+    HelperBufs& hl = c->hl;
     int rc;
-    if ((rc = coeb_internal_scratch(c, "bf_img", (size_t)W * H, &dimg)) ||
-        (rc = coeb_internal_scratch(c, "bf_box", (size_t)nbox * 16, &dbox)) ||
-        (rc = coeb_internal_scratch(c, "bf_out", (size_t)nbox * 4, &dout)))
+    if ((rc = ensure(c, hl.bf_img, (size_t)W * H)) || (rc = ensure(c, hl.bf_box, (size_t)nbox * 4)) ||
+        (rc = ensure(c, hl.bf_out, (size_t)nbox)))
         return rc;
-    FR_TRY(c, hipMemcpy2DAsync(dimg, W, gray, stride, W, H, hipMemcpyHostToDevice, s));
-    FR_TRY(c, hipMemcpyAsync(dbox, boxes, (size_t)nbox * 16, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_blur_flags, dim3(nbox), dim3(256), 0, s, (const uint8_t*)dimg, W, H, W, (const float*)dbox,
-                       (int*)dout, (double*)nullptr, (const int*)nullptr, (int64_t)0);
+    FR_TRY(c, hipMemcpy2DAsync(hl.bf_img.p, W, gray, stride, W, H, hipMemcpyHostToDevice, s));
+    FR_TRY(c, hipMemcpyAsync(hl.bf_box.p, boxes, (size_t)nbox * 16, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_blur_flags, dim3(nbox), dim3(256), 0, s, (const uint8_t*)hl.bf_img.p, W, H, W,
+                       (const float*)hl.bf_box.p, hl.bf_out.p, (double*)nullptr, (const int*)nullptr, (int64_t)0);
     FR_TRY(c, hipGetLastError());
-    FR_TRY(c, hipMemcpyAsync(flags_out, dout, (size_t)nbox * 4, hipMemcpyDeviceToHost, s));
+    FR_TRY(c, hipMemcpyAsync(flags_out, hl.bf_out.p, (size_t)nbox * 4, hipMemcpyDeviceToHost, s));
     FR_TRY(c, hipStreamSynchronize(s));
     return COEB_OK;
 }
@@ -312,31 +301,30 @@ extern "C" int coeb_rgbd_preprocess(coeb_ctx* c, const uint8_t* img, size_t img_
         (img && (!gray_out || (channels != 1 && channels != 3 && channels != 4) || img_stride < (size_t)channels * W)) ||
         (depth && (!depth_out || (depth_type != COEB_DEPTH_U16 && depth_type != COEB_DEPTH_F32) ||
                    depth_stride < dbytes * W || depth_stride % dbytes)))
-        return coeb_internal_error(c, COEB_EINVAL, "coeb_rgbd_preprocess: invalid arguments");
-    hipStream_t s;
-    int dev;
-    if (coeb_internal_stream(c, &s, &dev)) return COEB_EINVAL;
-    (void)hipSetDevice(dev);
-    void *dimg = nullptr, *dgray = nullptr, *dd = nullptr, *ddep = nullptr;
+        return set_err(c, COEB_EINVAL, "coeb_rgbd_preprocess: invalid arguments");
+    hipStream_t s = main_stream(c);
+    (void)hipSetDevice(c->device);
+    HelperBufs& hl = c->hl;
+    uint8_t *dimg = nullptr, *dgray = nullptr, *dd = nullptr;
+    float* ddep = nullptr;
     int rc;
     const size_t rowb = (size_t)channels * W;
     if (img) {
-        if ((rc = coeb_internal_scratch(c, "pp_img", rowb * H, &dimg)) ||
-            (rc = coeb_internal_scratch(c, "pp_gray", (size_t)W * H, &dgray)))
-            return rc;
+        if ((rc = ensure(c, hl.pp_img, rowb * H)) || (rc = ensure(c, hl.pp_gray, (size_t)W * H))) return rc;
+        dimg = hl.pp_img.p;
+        dgray = hl.pp_gray.p;
         FR_TRY(c, hipMemcpy2DAsync(dimg, rowb, img, img_stride, rowb, H, hipMemcpyHostToDevice, s));
     }
     // Tracking.cc:227: convertTo unless the map is already 32F and mDepthMapFactor == 1
     const int dcopy = depth_type == COEB_DEPTH_F32 && !(fabsf(depth_scale - 1.0f) > 1e-5f);
     if (depth) {
-        if ((rc = coeb_internal_scratch(c, "pp_dsrc", dbytes * W * H, &dd)) ||
-            (rc = coeb_internal_scratch(c, "pp_dep", (size_t)W * H * 4, &ddep)))
-            return rc;
+        if ((rc = ensure(c, hl.pp_dsrc, dbytes * W * H)) || (rc = ensure(c, hl.pp_dep, (size_t)W * H))) return rc;
+        dd = hl.pp_dsrc.p;
+        ddep = hl.pp_dep.p;
         FR_TRY(c, hipMemcpy2DAsync(dd, dbytes * W, depth, depth_stride, dbytes * W, H, hipMemcpyHostToDevice, s));
     }
     hipLaunchKernelGGL(k_rgbd, dim3((W + 63) / 64, (H + 3) / 4), dim3(256), 0, s, (const uint8_t*)dimg, (int)rowb, channels,
-                       rgb_order, (const uint8_t*)dd, (int)(dbytes * W), depth_type, depth_scale, dcopy, W, H,
-                       (uint8_t*)dgray, (float*)ddep);
+                       rgb_order, (const uint8_t*)dd, (int)(dbytes * W), depth_type, depth_scale, dcopy, W, H, dgray, ddep);
     FR_TRY(c, hipGetLastError());
     if (img) FR_TRY(c, hipMemcpyAsync(gray_out, dgray, (size_t)W * H, hipMemcpyDeviceToHost, s));
     if (depth) FR_TRY(c, hipMemcpyAsync(depth_out, ddep, (size_t)W * H * 4, hipMemcpyDeviceToHost, s));
@@ -351,18 +339,16 @@ extern "C" int coeb_rgbd_preprocess_batch_device(coeb_ctx* c, const uint8_t* d_i
     if (!c || F <= 0 || W <= 0 || H <= 0 || (!d_img && !d_depth) ||
         (d_img && (!d_gray || (channels != 1 && channels != 3 && channels != 4))) ||
         (d_depth && (!d_depth_out || (depth_type != COEB_DEPTH_U16 && depth_type != COEB_DEPTH_F32))))
-        return coeb_internal_error(c, COEB_EINVAL, "coeb_rgbd_preprocess_batch_device: invalid arguments");
-    if (W % 4) return coeb_internal_error(c, COEB_EINVAL, "coeb_rgbd_preprocess_batch_device: width must be a multiple of 4");
+        return set_err(c, COEB_EINVAL, "coeb_rgbd_preprocess_batch_device: invalid arguments");
+    if (W % 4) return set_err(c, COEB_EINVAL, "coeb_rgbd_preprocess_batch_device: width must be a multiple of 4");
     if ((d_img && (reinterpret_cast<uintptr_t>(d_img) | reinterpret_cast<uintptr_t>(d_gray)) % 4) ||
         (d_depth && (reinterpret_cast<uintptr_t>(d_depth) | reinterpret_cast<uintptr_t>(d_depth_out)) % 16))
-        return coeb_internal_error(c, COEB_EINVAL, "coeb_rgbd_preprocess_batch_device: misaligned device buffers");
-    hipStream_t s;
-    int dev;
-    if (coeb_internal_stream(c, &s, &dev)) return COEB_EINVAL;
-    (void)hipSetDevice(dev);
+        return set_err(c, COEB_EINVAL, "coeb_rgbd_preprocess_batch_device: misaligned device buffers");
+    hipStream_t s = main_stream(c);
+    (void)hipSetDevice(c->device);
     const int dcopy = depth_type == COEB_DEPTH_F32 && !(fabsf(depth_scale - 1.0f) > 1e-5f);   // Tracking.cc:227
     const int64_t npix = (int64_t)W * H;
-    ProfileHook* prof = coeb_internal_prof(c);
+    ProfileHook* prof = &c->hook;
     const bool wide = npix % 16 == 0 &&
                       ((reinterpret_cast<uintptr_t>(d_img) | reinterpret_cast<uintptr_t>(d_gray) |
                         reinterpret_cast<uintptr_t>(d_depth) | reinterpret_cast<uintptr_t>(d_depth_out)) & 15) == 0;
@@ -387,21 +373,17 @@ extern "C" int coeb_undistort_keypoints(coeb_ctx* c, const coeb_camera* cam, con
                                         int n, coeb_keypoint* out)
 {
     if (!c || !cam || !dist || n < 0 || (n > 0 && (!kps || !out)))
-        return coeb_internal_error(c, COEB_EINVAL, "coeb_undistort_keypoints: invalid arguments");
+        return set_err(c, COEB_EINVAL, "coeb_undistort_keypoints: invalid arguments");
     if (n == 0) return COEB_OK;
     if (dist[0] == 0.0f) {                                           // Frame.cc:581-585
         if (out != kps) memmove(out, kps, (size_t)n * sizeof(coeb_keypoint));
         return COEB_OK;
     }
-    hipStream_t s;
-    int dev;
-    if (coeb_internal_stream(c, &s, &dev)) return COEB_EINVAL;
-    (void)hipSetDevice(dev);
-    void *din, *dout;
+    hipStream_t s = main_stream(c);
+    (void)hipSetDevice(c->device);
     int rc;
-    if ((rc = coeb_internal_scratch(c, "ud_in", (size_t)n * sizeof(coeb_keypoint), &din)) ||
-        (rc = coeb_internal_scratch(c, "ud_out", (size_t)n * sizeof(coeb_keypoint), &dout)))
-        return rc;
+    if ((rc = ensure(c, c->hl.ud_in, (size_t)n)) || (rc = ensure(c, c->hl.ud_out, (size_t)n))) return rc;
+    coeb_keypoint *din = c->hl.ud_in.p, *dout = c->hl.ud_out.p;
     DistK d;
     for (int q = 0; q < 12; q++) d.k[q] = q < 5 ? (double)dist[q] : 0.0;
     d.fx = cam->fx; d.fy = cam->fy; d.cx = cam->cx; d.cy = cam->cy;

@@ -206,6 +206,11 @@ struct SideStream { hipStream_t s; hipEvent_t fork, mid, join, pyr_done, join2; 
 int launch_extract(const Plan& plan, const Plan* d_plan, const ExtractBufs& b, int F, hipStream_t s,
                    ProfileHook* prof, const SideStream* side = nullptr);
 
+// Matcher limits shared by the kernels (coeb_match.hip) and the buffers the C-ABI sizes for them
+constexpr int kCQ = 64;         // candidate-list entries per query (LastFrame point / local-map point)
+constexpr int kMaxSplit = 8;    // split-list workgroups per pair (k_match_lists): qn rows hold that many flags
+constexpr int kCurMax = 4095;   // current keypoints per frame (12-bit indices in the candidate lists)
+
 struct MatchCam {
     float fx, fy, cx, cy, bf, mb;
     float min_x, max_x, min_y, max_y;
@@ -236,7 +241,7 @@ struct MatchBufs {
     int* nmatch;               // [P]
     int* scratch;              // [P][scratch_stride]
     int scratch_stride;
-    int* qn;                   // optional [P][qn_stride >= last_stride + 8]: split-list counts + flags
+    int* qn;                   // optional [P][qn_stride >= last_stride + kMaxSplit]: split-list counts + flags
     int qn_stride;
     long long* timing;         // optional [P][16] phase clocks (COEB_MATCH_TIMING), else nullptr
     int* err;
@@ -260,7 +265,6 @@ struct LocalBufsHost {
 };
 int launch_match_local(const MatchCam& cam, const LocalBufsHost& b, float th, float nnratio, hipStream_t s,
                        ProfileHook* prof);
-int match_list_cap();   // candidate-list entries per query (kCQ)
 
 // Optimizer::PoseOptimization (coeb_pose.hip): per frame f, keypoints [f][stride]
 struct PoseEdgeRec { float x, y, z, u, v, ur, w; int stereo, kp; };

@@ -88,10 +88,10 @@ __global__ __launch_bounds__(kThreads) void k_prep(PrepBufs b)
 // A pair whose candidate list overflows kCQ, or that does not converge in kMaxIter
 // iterations, runs the literal sequential loop instead (exact, slower).
 constexpr int kMThreads = 1024;
-constexpr int kCQ = 64;
 
 constexpr int kMaxIter = 64;
 constexpr int kIdxBits = 12;
+static_assert(kCurMax < (1 << kIdxBits), "a current keypoint index must fit kIdxBits");
 // Lanes per LastFrame query in the candidate phase: a grid column range holds a few
 // candidates (10-px cells), so few lanes per query waste least (round 1: 16 -> 8 lanes, 0.171 ->
 // 0.147 ms/step; round 3: 8 -> 4 lanes, lists 174k -> 160k cycles per pair, k_match 0.314 ->
@@ -749,8 +749,7 @@ __device__ void build_lists(const MatchCam& cam, const PairView& v, const MatchL
 // idle): workgroup (p, s) stages pair p's grid and builds the lists of every S-th query group
 // (s, s + S, ...), writing the counts to b.qn (pair p's row; entry last_stride + s = s's
 // overflow flag).  k_match then starts at phase 2 with those lists (its own phases 0-1 run only
-// for the sequential fallback or the retry).
-constexpr int kMaxSplit = 8;
+// for the sequential fallback or the retry).  At most kMaxSplit workgroups per pair.
 
 template <bool kLds, int NT>
 __global__ __launch_bounds__(NT) void k_match_lists(MatchCam cam, MatchBufs b, float th0, int bmono)
@@ -1574,8 +1573,6 @@ int launch_match_local(const MatchCam& cam, const LocalBufsHost& h, float th, fl
     prof_end(prof, s);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
-
-int match_list_cap() { return kCQ; }
 
 int launch_match_kf(const MatchCam& cam, const KfBufsHost& h, float th, int orb_dist, int check_ori, hipStream_t s,
                     ProfileHook* prof)

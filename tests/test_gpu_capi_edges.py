@@ -474,3 +474,41 @@ def test_pipeline_frame_without_match_raises():
             bp.frame(1)
     finally:
         bp.close()
+
+
+# ------------------------------------------------------------------ 8. call order of the batch entry points
+def test_batch_call_order_guards():
+    """The call-order checks of the device-batch entry points, on one 320x240 context with
+    max_batch = 2: each refusal is a host-side argument check that returns before any launch, and
+    asking for results that do not exist yet changes nothing about what the next call may do."""
+    from coeb_front.pipeline import BatchPipeline
+    F, W, H = 2, 320, 240
+    bp = BatchPipeline(W, H, F)
+    c = bp.ctx
+
+    def refused(text, fn, *args):
+        with pytest.raises(cf.CoebError) as e:
+            fn(*args)
+        assert text in str(e.value), str(e.value)
+
+    try:
+        bp.load(synth.make_frames(W, H, F, seed=77), Tcw=np.stack([np.eye(4, dtype=np.float32), synth.motion_pose()]))
+        c.extract_batch_device(bp.gray.ptr, F, W, H)
+        assert c.batch_match_results() == (None, None)
+        refused("must follow", c.pose_batch_device, bp.cam, F, bp.dTcw.ptr)      # the read above made no match
+        refused("no batch pose yet", c.batch_pose_results)
+        refused("no batch TrackLocalMap yet", c.batch_track_results)
+        refused("no frame batch yet", c.batch_frame_results, F)
+        refused("rc=%d" % COEB_EINVAL, c.debug_read, "search_path")
+        c.match_batch_device_tcw(bp.depth.ptr, F, W, H, bp.cam, bp.dTcw.ptr)
+        m, n = c.batch_match_results()
+        assert m and n
+        refused("must follow", c.track_local_map_batch_device, bp.cam, F)
+        c.pose_batch_device(bp.cam, F, bp.dTcw.ptr)
+        assert all(c.batch_pose_results())
+        c.track_local_map_batch_device(bp.cam, F)
+        refused("already run", c.track_local_map_batch_device, bp.cam, F)
+        assert all(c.batch_track_results())
+        c.synchronize()
+    finally:
+        bp.close()
