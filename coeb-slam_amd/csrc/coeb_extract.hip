@@ -435,8 +435,8 @@ __global__ __launch_bounds__(kThreads) void k_pyr_rows(const uint8_t* __restrict
 // (sum_ij k_i k_j p_ij + 2^15) >> 16.  OpenCV's horizontal-then-vertical
 // order has no intermediate rounding, so the same integer is computed vertical-first:
 //   * vertical 7-tap on packed u16 column pairs (sums <= 255*256 fit 16 bits): 7 v_pk ops
-//     per 2 columns, the 7 source rows slide through registers (row loop unrolled by 7, so
-//     the ring never moves);
+//     per 2 columns, the 7 source rows slide through an 8-deep register ring (row loop
+//     unrolled by 8 = one tile row, so the ring never moves and the tile flush is static);
 //   * horizontal 7-tap as four v_dot2_u32_u16 per output on the packed vertical sums, the
 //     3-column halo coming from the neighbouring lanes by DPP row shifts;
 //   * the rounded result is byte 2 of the 24-bit accumulator: v_perm packs 4 outputs.
@@ -493,7 +493,7 @@ __device__ __forceinline__ uint32_t dpp_shl1(uint32_t v)   // lane i <- lane i+1
 // k_blur_rows: a wave item is 4 ADJACENT 56-column strips (one per 16-lane group) of one band of
 // brows rows, so every row index, its REFLECT_101 and the row
 // pointers are scalar (SGPR base + the lane's constant column offset, no per-row 64-bit address
-// VALU), the band halo is 6 rows per brows instead of per 16, and the next 7-row block's loads
+// VALU), the band halo is 6 rows per brows instead of per 16, and the next 8-row block's loads
 // are issued before the current block is filtered.
 __device__ __forceinline__ int reflect_row(int r, int h)
 {
@@ -505,12 +505,14 @@ __device__ __forceinline__ int reflect_row(int r, int h)
 }
 
 constexpr int kBlurQuad = 4 * kBlurCols;     // columns of one k_blur_rows wave item (14 tiles of 16)
+constexpr int kBlurPitch = kBlurQuad + 16;   // LDS row of the item's tile: the columns + 4 dummy dwords
 static_assert(kBlurQuad % 16 == 0, "a wave item must cover whole 16-column tiles");
 
 __global__ __launch_bounds__(kThreads) void k_blur_rows(const Plan* __restrict__ P, ExtractBufs b, BlurWork bw)
 {
-    // 8 output rows of the wave item, transposed through LDS into whole 128-B tile lines
-    __shared__ __attribute__((aligned(16))) uint8_t s_tile[kWaves][8 * kBlurQuad];
+    // 8 output rows of the wave item, transposed through LDS into whole 128-B tile lines; each LDS
+    // row ends in 16 dummy bytes that take the stores of the lanes with no output
+    __shared__ __attribute__((aligned(16))) uint8_t s_tile[kWaves][8 * kBlurPitch];
     const int2 bxy = block_xy();
     const int f = bxy.y;
     const int item = bw.item0 + bxy.x * kWaves + wave_id();
@@ -551,81 +553,139 @@ __global__ __launch_bounds__(kThreads) void k_blur_rows(const Plan* __restrict__
     const us2 W_l23_2 = pk2(0, k0), W_c01_2 = pk2(k1, k2), W_c23_2 = pk2(k3, k2), W_r01_2 = pk2(k1, k0);
     const us2 W_c01_3 = pk2(k0, k1), W_c23_3 = pk2(k2, k3), W_r01_3 = pk2(k2, k1), W_r23_3 = pk2(k0, 0);
     const uint32_t rnd = 1u << 15;
-    const int n_rows = (y1 - y0) + 6;          // source rows y0-3 .. y1+2
-    auto load_row = [&](int i) -> uint32_t {   // source row y0 - 3 + i (uniform), REFLECT_101
-        const int so = __builtin_amdgcn_readfirstlane(reflect_row(y0 - 3 + i, h) * sp);
-        return __builtin_amdgcn_raw_buffer_load_b32(rs, a, so, 0);
+    // Band structure: 6 prologue rows fill an 8-deep register ring, then every block of 8 source
+    // rows gives the 8 output rows of one tile row and ends with the tile flush.  The block is
+    // unrolled, so ring slots, LDS rows and the flush position are static: the steady state has no
+    // per-row scalar control, one loop branch per 8 rows.  A last block of 1..7 rows (only the last
+    // band of a level has one) runs behind per-row uniform tests.
+    const int nfull = (y1 - y0) >> 3, tail = (y1 - y0) & 7;
+    uint32_t R0[8], R1[8];
+    auto take = [&](int s, uint32_t raw) {
+        R0[s] = __builtin_amdgcn_perm(0u, raw, sel0);
+        R1[s] = __builtin_amdgcn_perm(0u, raw, sel1);
     };
-    uint32_t nxt[7];
+    // Lanes with no output (the halo lanes 0 and 15 of a group, columns past the level) store too,
+    // into the dummy dwords at the end of the row: no exec-mask change and no branch per row, so
+    // the 8 rows of a block are one basic block and their dot chains interleave.  Of a 32-lane
+    // half (2 groups) the halo lanes get 4 different dwords.
+    typedef __attribute__((address_space(3))) uint32_t* lds_u32;
+    lds_u32 trow = (lds_u32)(tl + (produce ? x - xbase : kBlurQuad + 8 * (grp & 1) + 4 * (gl & 1)));
+    asm volatile("" : "+v"(trow));                                 // one address VGPR, rows by immediate offset
+    // output row from the ring whose newest source row sits in slot s -> LDS row k of the item's tile
+    auto out_row = [&](int s, int k) {
+        const int s0 = (s + 2) & 7, s1 = (s + 3) & 7, s2 = (s + 4) & 7, s3 = (s + 5) & 7, s4 = (s + 6) & 7,
+                  s5 = (s + 7) & 7, s6 = s;
+        const us2 v01 = K3 * as_us2(R0[s3]) + K2 * (as_us2(R0[s2]) + as_us2(R0[s4])) +
+                        K1 * (as_us2(R0[s1]) + as_us2(R0[s5])) + K0 * (as_us2(R0[s0]) + as_us2(R0[s6]));
+        const us2 v23 = K3 * as_us2(R1[s3]) + K2 * (as_us2(R1[s2]) + as_us2(R1[s4])) +
+                        K1 * (as_us2(R1[s1]) + as_us2(R1[s5])) + K0 * (as_us2(R1[s0]) + as_us2(R1[s6]));
+        const uint32_t V01 = as_u32(v01), V23 = as_u32(v23);
+        const us2 L01 = as_us2(dpp_shr1(V01)), L23 = as_us2(dpp_shr1(V23));
+        const us2 R01 = as_us2(dpp_shl1(V01)), R23 = as_us2(dpp_shl1(V23));
+        uint32_t a0 = __builtin_amdgcn_udot2(L01, W_l01_0, rnd, false);
+        a0 = __builtin_amdgcn_udot2(L23, W_l23_0, a0, false);
+        a0 = __builtin_amdgcn_udot2(v01, W_c01_0, a0, false);
+        a0 = __builtin_amdgcn_udot2(v23, W_c23_0, a0, false);
+        uint32_t a1 = __builtin_amdgcn_udot2(L23, W_l23_1, rnd, false);
+        a1 = __builtin_amdgcn_udot2(v01, W_c01_1, a1, false);
+        a1 = __builtin_amdgcn_udot2(v23, W_c23_1, a1, false);
+        a1 = __builtin_amdgcn_udot2(R01, W_r01_1, a1, false);
+        uint32_t a2 = __builtin_amdgcn_udot2(L23, W_l23_2, rnd, false);
+        a2 = __builtin_amdgcn_udot2(v01, W_c01_2, a2, false);
+        a2 = __builtin_amdgcn_udot2(v23, W_c23_2, a2, false);
+        a2 = __builtin_amdgcn_udot2(R01, W_r01_2, a2, false);
+        uint32_t a3 = __builtin_amdgcn_udot2(v01, W_c01_3, rnd, false);
+        a3 = __builtin_amdgcn_udot2(v23, W_c23_3, a3, false);
+        a3 = __builtin_amdgcn_udot2(R01, W_r01_3, a3, false);
+        a3 = __builtin_amdgcn_udot2(R23, W_r23_3, a3, false);
+        const uint32_t p01 = __builtin_amdgcn_perm(a1, a0, 0x0c0c0602u);
+        const uint32_t p23 = __builtin_amdgcn_perm(a3, a2, 0x06020c0cu);
+        trow[k * (kBlurPitch / 4)] = p01 | p23;
+    };
+    // the tile row's 8 LDS rows leave as whole tile lines, 16 B per lane, consecutive lanes
+    // consecutive bytes (a tile row's tiles are adjacent), 1.75 KiB in two instructions.
+    // Storing each row straight into the tiles (14 partial lines per instruction) took
+    // k_blur_rows 0.487 -> 0.829 ms per 1025-frame launch (profiles/r05/s4).
+    const int c1 = lane + 64;                                      // chunk: tile c >> 3, row c & 7
+    const bool st0 = xbase + 16 * (lane >> 3) < dp;
+    const bool st1 = c1 < kBlurQuad / 2 && xbase + 16 * (c1 >> 3) < dp;
+    const uint8_t* const tsrc0 = tl + (lane & 7) * kBlurPitch + 16 * (lane >> 3);
+    const uint8_t* const tsrc1 = tl + (c1 & 7) * kBlurPitch + 16 * (c1 >> 3);
+    const int tdst = (xbase >> 4) * 128 + 16 * lane;
+    int so_d = __builtin_amdgcn_readfirstlane((int)blur_tile_off(0, y0, dp));   // tile row y0 / 8
+    const int so_dstep = __builtin_amdgcn_readfirstlane((dp >> 4) * 128);
+    auto flush = [&]() {
+        wave_sync_lds();
+        if (st0) __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(tsrc0), rd, tdst, so_d, 0);
+        if (st1)
+            __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(tsrc1), rd, tdst + 16 * 64, so_d, 0);
+        wave_sync_lds();
+        so_d += so_dstep;
+    };
+    // kReflect: the band's source rows y0 - 3 .. y1 + 2 leave the level (first and last band), so
+    // every row index goes through REFLECT_101; interior bands advance a scalar offset by the pitch.
+    auto band_rows = [&](auto reflect) {
+        constexpr bool kReflect = decltype(reflect)::value;
+        int r = y0 - 3;
+        int so = __builtin_amdgcn_readfirstlane((y0 - 3) * sp);
+        auto load_row = [&]() -> uint32_t {                        // next source row (uniform)
+            int o;
+            if constexpr (kReflect) {
+                o = __builtin_amdgcn_readfirstlane(reflect_row(r, h) * sp);
+                r++;
+            } else {
+                o = so;
+                so += sp;
+            }
+            return __builtin_amdgcn_raw_buffer_load_b32(rs, a, o, 0);
+        };
+        uint32_t pro[6], nxt[8];
 #pragma unroll
-    for (int ph = 0; ph < 7; ph++) nxt[ph] = load_row(ph);
-    uint32_t R0[7], R1[7];
-    for (int i0 = 0; i0 < n_rows; i0 += 7) {
-        uint32_t raw[7];
+        for (int s = 0; s < 6; s++) pro[s] = load_row();
 #pragma unroll
-        for (int ph = 0; ph < 7; ph++) raw[ph] = nxt[ph];
-        if (i0 + 7 < n_rows) {
+        for (int k = 0; k < 8; k++) nxt[k] = 0u;
+        if (nfull > 0) {
 #pragma unroll
-            for (int ph = 0; ph < 7; ph++) nxt[ph] = load_row(i0 + 7 + ph);
+            for (int k = 0; k < 8; k++) nxt[k] = load_row();
+        } else {
+#pragma unroll
+            for (int k = 0; k < 7; k++)
+                if (k < tail) nxt[k] = load_row();
         }
 #pragma unroll
-        for (int ph = 0; ph < 7; ph++) {
-            const int i = i0 + ph;
-            if (i >= n_rows) break;
-            R0[ph] = __builtin_amdgcn_perm(0u, raw[ph], sel0);
-            R1[ph] = __builtin_amdgcn_perm(0u, raw[ph], sel1);
-            if (i < 6) continue;
-            const int s0 = (ph + 1) % 7, s1 = (ph + 2) % 7, s2 = (ph + 3) % 7, s3 = (ph + 4) % 7,
-                      s4 = (ph + 5) % 7, s5 = (ph + 6) % 7, s6 = ph;
-            const us2 v01 = K3 * as_us2(R0[s3]) + K2 * (as_us2(R0[s2]) + as_us2(R0[s4])) +
-                            K1 * (as_us2(R0[s1]) + as_us2(R0[s5])) + K0 * (as_us2(R0[s0]) + as_us2(R0[s6]));
-            const us2 v23 = K3 * as_us2(R1[s3]) + K2 * (as_us2(R1[s2]) + as_us2(R1[s4])) +
-                            K1 * (as_us2(R1[s1]) + as_us2(R1[s5])) + K0 * (as_us2(R1[s0]) + as_us2(R1[s6]));
-            const uint32_t V01 = as_u32(v01), V23 = as_u32(v23);
-            const us2 L01 = as_us2(dpp_shr1(V01)), L23 = as_us2(dpp_shr1(V23));
-            const us2 R01 = as_us2(dpp_shl1(V01)), R23 = as_us2(dpp_shl1(V23));
-            uint32_t a0 = __builtin_amdgcn_udot2(L01, W_l01_0, rnd, false);
-            a0 = __builtin_amdgcn_udot2(L23, W_l23_0, a0, false);
-            a0 = __builtin_amdgcn_udot2(v01, W_c01_0, a0, false);
-            a0 = __builtin_amdgcn_udot2(v23, W_c23_0, a0, false);
-            uint32_t a1 = __builtin_amdgcn_udot2(L23, W_l23_1, rnd, false);
-            a1 = __builtin_amdgcn_udot2(v01, W_c01_1, a1, false);
-            a1 = __builtin_amdgcn_udot2(v23, W_c23_1, a1, false);
-            a1 = __builtin_amdgcn_udot2(R01, W_r01_1, a1, false);
-            uint32_t a2 = __builtin_amdgcn_udot2(L23, W_l23_2, rnd, false);
-            a2 = __builtin_amdgcn_udot2(v01, W_c01_2, a2, false);
-            a2 = __builtin_amdgcn_udot2(v23, W_c23_2, a2, false);
-            a2 = __builtin_amdgcn_udot2(R01, W_r01_2, a2, false);
-            uint32_t a3 = __builtin_amdgcn_udot2(v01, W_c01_3, rnd, false);
-            a3 = __builtin_amdgcn_udot2(v23, W_c23_3, a3, false);
-            a3 = __builtin_amdgcn_udot2(R01, W_r01_3, a3, false);
-            a3 = __builtin_amdgcn_udot2(R23, W_r23_3, a3, false);
-            const int y = y0 - 6 + i;                                  // uniform
-            // row y into the item's LDS rows; after every 8th row (tile rows start at multiples of 8:
-            // y0 is) the 8 rows leave as whole tile lines, 16 B per lane, consecutive lanes
-            // consecutive bytes (a tile row's tiles are adjacent), 1.75 KiB in two instructions.
-            // Storing each row straight into the tiles (14 partial lines per instruction) took
-            // k_blur_rows 0.487 -> 0.829 ms per 1025-frame launch (profiles/r05/s4).
-            if (produce) {
-                const uint32_t p01 = __builtin_amdgcn_perm(a1, a0, 0x0c0c0602u);
-                const uint32_t p23 = __builtin_amdgcn_perm(a3, a2, 0x06020c0cu);
-                *reinterpret_cast<uint32_t*>(tl + (y & 7) * kBlurQuad + (x - xbase)) = p01 | p23;
-            }
-            if ((y & 7) == 7 || y == y1 - 1) {
-                wave_sync_lds();
-                const int so = __builtin_amdgcn_readfirstlane((int)blur_tile_off(0, y & ~7, dp));
+        for (int s = 0; s < 6; s++) take(s, pro[s]);
+        for (int blk = 0; blk < nfull; blk++) {
+            uint32_t raw[8];
 #pragma unroll
-                for (int k = 0; k < 2; k++) {
-                    const int c = lane + 64 * k;                           // chunk: tile c >> 3, row c & 7
-                    if (c < kBlurQuad / 2 && xbase + 16 * (c >> 3) < dp) {
-                        const u32x4 v = *reinterpret_cast<const u32x4*>(tl + (c & 7) * kBlurQuad + 16 * (c >> 3));
-                        __builtin_amdgcn_raw_buffer_store_b128(v, rd, (xbase >> 4) * 128 + 16 * c, so, 0);
-                    }
-                }
-                wave_sync_lds();
+            for (int k = 0; k < 8; k++) raw[k] = nxt[k];
+            // the next block's rows are issued before this block is filtered
+            if (blk + 1 < nfull) {
+#pragma unroll
+                for (int k = 0; k < 8; k++) nxt[k] = load_row();
+            } else {
+#pragma unroll
+                for (int k = 0; k < 7; k++)
+                    if (k < tail) nxt[k] = load_row();
             }
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                take((6 + k) & 7, raw[k]);
+                out_row((6 + k) & 7, k);
+            }
+            flush();
         }
-    }
+        if (tail) {
+#pragma unroll
+            for (int k = 0; k < 7; k++) {
+                if (k >= tail) break;
+                take((6 + k) & 7, nxt[k]);
+                out_row((6 + k) & 7, k);
+            }
+            flush();
+        }
+    };
+    if (y0 >= 3 && y1 + 2 < h) band_rows(std::false_type());      // wave-uniform
+    else band_rows(std::true_type());
 }
 
 // ================================ k_fast ================================
