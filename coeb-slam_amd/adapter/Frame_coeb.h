@@ -1,6 +1,7 @@
 /*
  * Frame_coeb.h -- MI355X body for Frame::ProcessMovingObject(const cv::Mat &imgray,
- * std::vector<std::vector<float>> &box) (include/Frame.h, src/Frame.cc:311-393).
+ * std::vector<std::vector<float>> &box) (include/Frame.h, src/Frame.cc:311-393), and
+ * coeb::FrameRGBD, the RGB-D constructor's tail (src/Frame.cc:214-223; at the end of this file).
  *
  * Included from the reference's src/Frame.cc; the member function body becomes
  *
@@ -69,6 +70,34 @@ inline void ProcessMovingObject(const cv::Mat& imGrayPre, const cv::Mat& imgray,
         out.resize((size_t)n);
         T_M.swap(out);
     }
+}
+
+/*
+ * The RGB-D Frame constructor's tail, src/Frame.cc:214-223:
+ *
+ *     ExtractORB(0, imGray, img, imDepth, box, T_M, mask_result, blur_flag);
+ *     N = mvKeys.size();
+ *     if(mvKeys.empty()) return;
+ *     UndistortKeyPoints();
+ *     ComputeStereoFromRGBD(imDepth);
+ *
+ * collapses to
+ *
+ *     coeb::FrameRGBD(*this, mpORBextractorLeft, imGray, imDepth, box, T_M, blur_flag);
+ *     if(mvKeys.empty()) return;
+ *
+ * one device call (ORBextractor::ExtractRGBD -> coeb_frame_rgbd) that fills mvKeys, mDescriptors,
+ * N, mvKeysUn, mvuRight and mvDepth from mK, mDistCoef and mbf.  mvuRight follows :829-839 with a
+ * distorted calibration too: depth at mvKeys[i], x of mvKeysUn[i].  imDepth is the CV_32F map.
+ */
+template <class FrameT, class ExtractorT>
+inline void FrameRGBD(FrameT& F, ExtractorT* extractor, const cv::Mat& imGray, const cv::Mat& imDepth,
+                      std::vector<std::vector<float>>& box, const std::vector<cv::Point2f>& T_M,
+                      const std::vector<int>& blur_flag)
+{
+    extractor->ExtractRGBD(imGray, imDepth, F.mK, F.mDistCoef, F.mbf, box, T_M, blur_flag, F.mvKeys, F.mDescriptors,
+                           F.mvKeysUn, F.mvuRight, F.mvDepth);
+    F.N = (int)F.mvKeys.size();
 }
 
 }  // namespace coeb

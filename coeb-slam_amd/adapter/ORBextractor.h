@@ -11,6 +11,8 @@
  *              mask_result, blur_flag)                                     ORBextractor.h:73-75
  *   GetLevels / GetScaleFactor / GetScaleFactors / GetInverseScaleFactors /
  *   GetScaleSigmaSquares / GetInverseScaleSigmaSquares                     ORBextractor.h:77-99
+ *   ExtractRGBD(...)  (an addition: the Frame RGB-D ctor tail, Frame.cc:214-223, in one call;
+ *                      coeb::FrameRGBD of Frame_coeb.h wraps it)
  *
  * Behaviour kept from the reference: empty image -> return without touching the outputs
  * (:1096-1097); non-8UC1 -> assert (:1099); zero keypoints -> descriptors.release()
@@ -155,6 +157,63 @@ public:
         }
     }
 
+    // The RGB-D Frame constructor's tail (Frame.cc:214-223) in one device call (coeb_frame_rgbd):
+    // operator() as above, mvKeysUn = UndistortKeyPoints (:579-609) with K and distCoef (4 or 5
+    // CV_32F coefficients; distCoef(0) == 0 copies), and ComputeStereoFromRGBD (:820-842): depth
+    // at the raw keypoint, uRight from the undistorted x.  imDepth is the CV_32F map
+    // Tracking::GrabImageRGBD converted (Tracking.cc:227).  Same conventions as operator(): an
+    // empty image returns without touching the outputs, zero keypoints release the descriptors.
+    void ExtractRGBD(const cv::Mat& imGray, const cv::Mat& imDepth, const cv::Mat& K, const cv::Mat& distCoef, float bf,
+                     std::vector<std::vector<float>>& box, const std::vector<cv::Point2f>& T_M,
+                     const std::vector<int>& blur_flag, std::vector<cv::KeyPoint>& mvKeys, cv::Mat& mDescriptors,
+                     std::vector<cv::KeyPoint>& mvKeysUn, std::vector<float>& mvuRight, std::vector<float>& mvDepth)
+    {
+        if (imGray.empty()) return;
+        assert(imGray.type() == CV_8UC1);
+        if (imDepth.empty() || imDepth.type() != CV_32F || imDepth.rows != imGray.rows || imDepth.cols != imGray.cols)
+            throw std::invalid_argument("ORBextractor::ExtractRGBD: a CV_32F depth map of the image's size expected");
+        std::vector<coeb_box> boxes;
+        for (const auto& b : box) boxes.push_back(coeb_box{b[0], b[1], b[2], b[3]});
+        std::vector<float> tm;
+        for (const auto& p : T_M) { tm.push_back(p.x); tm.push_back(p.y); }
+        coeb_camera cam{};
+        cam.fx = K.at<float>(0, 0); cam.fy = K.at<float>(1, 1); cam.cx = K.at<float>(0, 2); cam.cy = K.at<float>(1, 2);
+        cam.bf = bf;
+        cam.max_x = (float)imGray.cols; cam.max_y = (float)imGray.rows;
+        float dist[5] = {0, 0, 0, 0, 0};
+        const int nd = distCoef.empty() ? 0 : std::min(5, distCoef.rows * distCoef.cols);
+        for (int i = 0; i < nd; i++) dist[i] = distCoef.at<float>(i);
+        coeb_ctx* ctx_ = coeb_detail::pooled_context(params_, device(), imGray.cols, imGray.rows);
+        const int cap = coeb_max_keypoints(ctx_, imGray.cols, imGray.rows);
+        if (cap < 0) throw std::runtime_error(coeb_last_error(ctx_));
+        std::vector<coeb_keypoint> kps((size_t)cap), kun((size_t)cap);
+        std::vector<float> ur((size_t)cap), dep((size_t)cap);
+        cv::Mat desc((int)cap, 32, CV_8U);
+        int n = 0;
+        const int rc = coeb_frame_rgbd(ctx_, imGray.data, imGray.cols, imGray.rows, imGray.step[0], imDepth.data,
+                                       imDepth.step[0], COEB_DEPTH_F32, 1.0f, &cam, nd ? dist : nullptr,
+                                       boxes.empty() ? nullptr : boxes.data(), (int)boxes.size(),
+                                       tm.empty() ? nullptr : tm.data(), (int)T_M.size(),
+                                       blur_flag.empty() ? nullptr : blur_flag.data(), (int)blur_flag.size(), kps.data(),
+                                       kun.data(), desc.data, ur.data(), dep.data(), cap, &n);
+        if (rc != COEB_OK) throw std::runtime_error(coeb_last_error(ctx_));
+        static_assert(sizeof(coeb_keypoint) == sizeof(cv::KeyPoint), "coeb_keypoint must mirror cv::KeyPoint");
+        mvKeys.resize((size_t)n);
+        mvKeysUn.resize((size_t)n);
+        if (n) {
+            std::memcpy(static_cast<void*>(&mvKeys[0]), kps.data(), sizeof(coeb_keypoint) * (size_t)n);
+            std::memcpy(static_cast<void*>(&mvKeysUn[0]), kun.data(), sizeof(coeb_keypoint) * (size_t)n);
+        }
+        mvuRight.assign(ur.begin(), ur.begin() + n);
+        mvDepth.assign(dep.begin(), dep.begin() + n);
+        if (n == 0) {
+            mDescriptors.release();
+        } else {
+            mDescriptors.create(n, 32, CV_8U);
+            desc.rowRange(0, n).copyTo(mDescriptors);
+        }
+    }
+
     int inline GetLevels() { return nlevels; }
     float inline GetScaleFactor() { return (float)scaleFactor; }
     std::vector<float> inline GetScaleFactors() { return mvScaleFactor; }
@@ -162,7 +221,10 @@ public:
     std::vector<float> inline GetScaleSigmaSquares() { return mvLevelSigma2; }
     std::vector<float> inline GetInverseScaleSigmaSquares() { return mvInvLevelSigma2; }
 
-    std::vector<cv::Mat> mvImagePyramid;   // RGB-D never reads it (Frame.cc:651,741,758 are stereo)
+    // Left empty (nlevels default-constructed Mats): the pyramid stays on the device.  The
+    // reference's readers of it, Frame.cc:651, 741 and 758, are all in ComputeStereoMatches, which
+    // the RGB-D constructor never calls.
+    std::vector<cv::Mat> mvImagePyramid;
 
 protected:
     static int device()

@@ -57,7 +57,7 @@ ABI_SYMBOLS = [
     "coeb_track_local_map_batch_device", "coeb_batch_track_results", "coeb_rgbd_preprocess_batch_device",
     "coeb_marker_create", "coeb_marker_destroy", "coeb_marker_record_ctx", "coeb_marker_record_copyq",
     "coeb_ctx_wait_marker", "coeb_copyq_wait_marker", "coeb_marker_synchronize",
-    "coeb_tum_read_list", "coeb_tum_associate",
+    "coeb_tum_read_list", "coeb_tum_associate", "coeb_frame_rgbd",
 ]
 # COEB_ABI_VERSION of the include/coeb_front.h these argtypes are written against; lib() refuses
 # a library that reports another (tests/test_capi_symbols.py keeps the two equal)
@@ -134,6 +134,10 @@ def lib():
         L.coeb_extract.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int,
                                    C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                    C.POINTER(C.c_int)]
+        L.coeb_frame_rgbd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t,
+                                      C.c_int, C.c_float, C.POINTER(Camera), C.c_void_p, C.c_void_p, C.c_int,
+                                      C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         L.coeb_extract_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.coeb_frame_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
@@ -300,6 +304,42 @@ class Context:
                                       nf, _p(kps), _p(desc), cap, C.byref(n)))
         n = n.value
         return kps[:n], (desc[:n] if n else None)
+
+    def frame_rgbd(self, gray, depth, cam, dist=None, boxes=None, tm=None, blur=None, depth_scale=1.0):
+        """The RGB-D Frame constructor's tail (Frame.cc:214-223) in one call: extraction,
+        UndistortKeyPoints with dist = mDistCoef (k1, k2, p1, p2[, k3]; None copies the keys) and
+        ComputeStereoFromRGBD on depth ((H, W) float32, or uint16 with depth_scale =
+        mDepthMapFactor).  Returns dict(kps, kps_un, desc, u_right, depth)."""
+        gray = np.ascontiguousarray(gray, np.uint8)
+        if gray.size == 0:
+            return dict(kps=np.zeros(0, KEYPOINT_DTYPE), kps_un=np.zeros(0, KEYPOINT_DTYPE), desc=None,
+                        u_right=np.zeros(0, np.float32), depth=np.zeros(0, np.float32))
+        h, w = gray.shape
+        depth = np.ascontiguousarray(depth)
+        if depth.shape != (h, w) or depth.dtype not in (np.uint16, np.float32):
+            raise ValueError("depth must be (H, W) uint16 or float32")
+        dtype = DEPTH_F32 if depth.dtype == np.float32 else DEPTH_U16
+        d = None
+        if dist is not None:
+            d = np.zeros(5, np.float32)
+            d[:len(dist)] = np.asarray(dist, np.float32)
+        boxes = None if boxes is None else np.ascontiguousarray(boxes, np.float32)
+        tm = None if tm is None else np.ascontiguousarray(tm, np.float32)
+        blur = None if blur is None else np.ascontiguousarray(blur, np.int32)
+        nb = 0 if boxes is None else len(boxes)
+        nt = 0 if tm is None else len(tm)
+        nf = 0 if blur is None else len(blur)
+        cap = self.max_keypoints(w, h)
+        kps, kun = np.empty(cap, KEYPOINT_DTYPE), np.empty(cap, KEYPOINT_DTYPE)
+        desc = np.empty((cap, 32), np.uint8)
+        ur, dep = np.empty(cap, np.float32), np.empty(cap, np.float32)
+        n = C.c_int()
+        self.check(lib().coeb_frame_rgbd(self.h, _p(gray), w, h, w, _p(depth), depth.strides[0], dtype,
+                                         C.c_float(depth_scale), C.byref(cam), _p(d), _p(boxes) if nb else None, nb,
+                                         _p(tm) if nt else None, nt, _p(blur) if nf else None, nf, _p(kps), _p(kun),
+                                         _p(desc), _p(ur), _p(dep), cap, C.byref(n)))
+        n = n.value
+        return dict(kps=kps[:n], kps_un=kun[:n], desc=(desc[:n] if n else None), u_right=ur[:n], depth=dep[:n])
 
     # ---- device-resident batch ----
     def extract_batch_device(self, d_gray_ptr, nframes, w, h, boxes=None, box_off=None, tm=None, tm_off=None,

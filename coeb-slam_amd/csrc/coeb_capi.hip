@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "coeb_ctx.hpp"
+#include "coeb_frame_rgbd_host.hpp"
 
 static const int8_t kPattern[1024] = {
 #include "../../data/orb_bit_pattern_31.inc"
@@ -336,6 +337,63 @@ __global__ __launch_bounds__(256) void k_out_pack(const int* counts, const uint3
     if (t == 0) *out_n = *counts;
     for (int i = t; i < 7 * n; i += T) out_k[i] = kps[i];          // 28-byte records
     for (int i = t; i < 2 * n; i += T) out_d[i] = desc[i];         // 32-byte rows
+}
+
+// k_out_pack's place in coeb_frame_rgbd: the rest of the Frame RGB-D constructor
+// (Frame.cc:216-223) on the records the extraction left on the device, written to the same
+// page-locked buffer.  Per keypoint: mvKeysUn (UndistortKeyPoints, :579-609; a copy when
+// mDistCoef[0] == 0), and ComputeStereoFromRGBD (:820-842) with the depth looked up at the RAW
+// keypoint and uRight formed from the UNDISTORTED x.  The depth rows stay in host memory (the
+// buffer's device alias): ~1000 of W*H values are read, each converted as
+// Tracking::GrabImageRGBD's convertTo would have (Tracking.cc:227).  The gather is issued before
+// the undistortion, whose ~200 double operations cover its PCIe round trip.
+struct FrameTail {
+    const int* counts; const uint32_t* kps; const uint4* desc; int guess;
+    int* out_n; uint32_t* out_k; uint4* out_d;
+    uint32_t* out_kun;          // null: kp_un_out not asked for
+    float* out_ur; float* out_dep;
+    const uint8_t* depth;       // W values per row, rows packed
+    int W, H, depth_u16, depth_copy, undistort;
+    float depth_scale, bf;
+    DistK dist;
+};
+
+__global__ __launch_bounds__(256) void k_frame_tail(FrameTail a)
+{
+    const int n = min(*a.counts, a.guess);
+    const int t = blockIdx.x * 256 + threadIdx.x, T = gridDim.x * 256;
+    if (t == 0) *a.out_n = *a.counts;
+    for (int i = t; i < n; i += T) {
+        uint32_t r[7];
+#pragma unroll
+        for (int q = 0; q < 7; q++) r[q] = a.kps[7 * i + q];
+        const float x = __uint_as_float(r[0]), y = __uint_as_float(r[1]);
+        // imDepth.at<float>(v, u) with v = kp.pt.y, u = kp.pt.x (:829-832); keypoints lie inside
+        // the image, the clamp only keeps a bad record from reading outside the staged rows
+        const int px = min(max((int)x, 0), a.W - 1), py = min(max((int)y, 0), a.H - 1);
+        const int64_t p = (int64_t)py * a.W + px;
+        float d;
+        if (a.depth_u16) {
+            d = (float)reinterpret_cast<const uint16_t*>(a.depth)[p] * a.depth_scale;
+        } else {
+            d = reinterpret_cast<const float*>(a.depth)[p];
+            if (!a.depth_copy) d = d * a.depth_scale;      // convertTo(CV_32F, scale): float product
+        }
+        float ux = x, uy = y;
+        if (a.undistort) undistort_point(a.dist, ux, uy);
+        if (a.out_kun) {
+            a.out_kun[7 * i] = __float_as_uint(ux);
+            a.out_kun[7 * i + 1] = __float_as_uint(uy);
+#pragma unroll
+            for (int q = 2; q < 7; q++) a.out_kun[7 * i + q] = r[q];
+        }
+        float ur = -1.f, dep = -1.f;
+        if (d > 0) { dep = d; ur = ux - a.bf / d; }        // NaN and d <= 0 fail `d > 0` (:834)
+        a.out_ur[i] = ur;
+        a.out_dep[i] = dep;
+    }
+    for (int i = t; i < 7 * n; i += T) a.out_k[i] = a.kps[i];          // 28-byte records
+    for (int i = t; i < 2 * n; i += T) a.out_d[i] = a.desc[i];         // 32-byte rows
 }
 
 // Inputs of one call packed at 16-byte aligned offsets of the pinned staging buffer, moved to
@@ -1067,6 +1125,95 @@ int coeb_extract(coeb_ctx* c, const uint8_t* gray, int W, int H, size_t stride, 
     }
     if (m > 0 && kp_out) memcpy(kp_out, c->pin + o_k, (size_t)m * sizeof(coeb_keypoint));
     if (m > 0 && desc_out) memcpy(desc_out, c->pin + o_d, (size_t)m * 32);
+    if (n > cap) return set_err(c, COEB_ERANGE, "keypoint output capacity too small");
+    return COEB_OK;
+}
+
+int coeb_frame_rgbd(coeb_ctx* c, const uint8_t* gray, int W, int H, size_t stride, const void* depth, size_t depth_stride,
+                    int depth_type, float depth_scale, const coeb_camera* cam, const float dist[5], const coeb_box* boxes,
+                    int nbox, const float* tm_xy, int ntm, const int32_t* blur_flag, int nblur, coeb_keypoint* kp_out,
+                    coeb_keypoint* kp_un_out, uint8_t* desc_out, float* u_right_out, float* depth_out, int cap, int* n_out)
+{
+    if (!c || !n_out) return set_err(c, COEB_EINVAL, "coeb_frame_rgbd: invalid arguments");
+    *n_out = 0;
+    const char* why = "";
+    int rc = frame_rgbd_check(gray, W, H, stride, depth, depth_stride, depth_type, cam, boxes, nbox, tm_xy, ntm, nblur, kp_out,
+                              desc_out, u_right_out, depth_out, &why);
+    if (rc == 1) return COEB_OK;                            // _image.empty() -> return (:1096-1097)
+    if (rc) return set_err(c, rc, std::string("coeb_frame_rgbd: ") + why);
+    (void)hipSetDevice(c->device);
+    if ((rc = ensure_plan(c, W, H))) return rc;
+    if ((rc = ensure(c, c->ex.gray_stage, (size_t)W * H))) return rc;
+    uint8_t* dgray = c->ex.gray_stage.p;
+    const int kcap = c->plan.kcap;
+    // the page-locked buffer is sized for the whole call up front: it must not move once the
+    // extraction has been enqueued
+    const FrameRgbdLayout L = frame_rgbd_layout(W, H, kcap, nbox, ntm, depth_type);
+    if ((rc = pinned(c, L.total))) return rc;
+    // 1. the gray rows and the extraction, as coeb_extract enqueues them
+    hipStream_t s = main_stream(c);
+    frame_rgbd_stage_rows(c->pin, gray, H, (size_t)W, stride);
+    HIP_TRY(c, hipMemcpyAsync(dgray, c->pin, (size_t)W * H, hipMemcpyHostToDevice, s));
+    int32_t* box_off = reinterpret_cast<int32_t*>(c->pin + L.o_bo);
+    int32_t* tm_off = reinterpret_cast<int32_t*>(c->pin + L.o_to);
+    int32_t* blur = reinterpret_cast<int32_t*>(c->pin + L.o_bl);
+    box_off[0] = 0; box_off[1] = nbox; tm_off[0] = 0; tm_off[1] = ntm;
+    for (int i = 0; i < nbox; i++)                      // missing flags (or a null array) read as 0
+        blur[i] = (blur_flag && i < nblur) ? blur_flag[i] : 0;
+    if (nbox) memcpy(c->pin + L.o_dyn, boxes, (size_t)nbox * sizeof(coeb_box));
+    if (ntm) memcpy(c->pin + L.o_tm, tm_xy, (size_t)ntm * 8);
+    ExtractBufs b;
+    if ((rc = extract_bufs(c, 1, b))) return rc;
+    if ((rc = upload_dyn(c, 1, nbox ? reinterpret_cast<const coeb_box*>(c->pin + L.o_dyn) : nullptr, box_off,
+                         ntm ? reinterpret_cast<const float*>(c->pin + L.o_tm) : nullptr, tm_off, nbox ? blur : nullptr, b)))
+        return rc;
+    b.gray = dgray;
+    if (launch_extract(c->plan, c->pl.plan.p, b, 1, s, &c->hook, nullptr))
+        return hip_err(c, hipGetLastError(), "launch_extract");
+    c->batch_frames = 1;
+    c->batch_gray = dgray;
+    // 2. while the device extracts, the host packs the depth rows into the buffer (16U as it is:
+    // half the bytes, and only the gathered values are ever converted)
+    frame_rgbd_stage_rows(c->pin + L.o_depth, depth, H, L.depth_row, depth_stride);
+    // 3. the tail kernel behind the extraction
+    FrameTail a;
+    memset(&a, 0, sizeof(a));
+    a.counts = b.counts; a.kps = static_cast<const uint32_t*>(b.kps); a.desc = reinterpret_cast<const uint4*>(b.desc);
+    a.guess = frame_rgbd_guess(kcap, cap);
+    a.out_n = reinterpret_cast<int*>(c->pin_dev + L.o_n);
+    a.out_k = reinterpret_cast<uint32_t*>(c->pin_dev + L.o_k);
+    a.out_d = reinterpret_cast<uint4*>(c->pin_dev + L.o_d);
+    a.out_kun = kp_un_out ? reinterpret_cast<uint32_t*>(c->pin_dev + L.o_kun) : nullptr;
+    a.out_ur = reinterpret_cast<float*>(c->pin_dev + L.o_ur);
+    a.out_dep = reinterpret_cast<float*>(c->pin_dev + L.o_dep);
+    a.depth = c->pin_dev + L.o_depth;
+    a.W = W; a.H = H;
+    a.depth_u16 = depth_type == COEB_DEPTH_U16;
+    a.depth_copy = frame_rgbd_depth_copy(depth_type, depth_scale);
+    a.depth_scale = depth_scale;
+    a.bf = cam->bf;
+    a.undistort = dist && dist[0] != 0.0f;                  // Frame.cc:581-585
+    for (int q = 0; q < 12; q++) a.dist.k[q] = (a.undistort && q < 5) ? (double)dist[q] : 0.0;
+    a.dist.fx = cam->fx; a.dist.fy = cam->fy; a.dist.cx = cam->cx; a.dist.cy = cam->cy;
+    prof_begin(&c->hook, "k_frame_tail", s);
+    hipLaunchKernelGGL(k_frame_tail, dim3(16), dim3(256), 0, s, a);
+    prof_end(&c->hook, s);
+    HIP_TRY(c, hipGetLastError());
+    // 4. the error word, and the call's one synchronisation
+    if ((rc = err_word_async(c, c->pin + L.o_n + 16))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if ((rc = err_word_seen(c, c->pin + L.o_n + 16))) return rc;
+    int n = 0;
+    memcpy(&n, c->pin + L.o_n, 4);
+    *n_out = n;
+    const int m = std::min(n, a.guess);                     // guess = min(kcap, cap) and n <= kcap
+    if (m > 0) {
+        memcpy(kp_out, c->pin + L.o_k, (size_t)m * sizeof(coeb_keypoint));
+        memcpy(desc_out, c->pin + L.o_d, (size_t)m * 32);
+        if (kp_un_out) memcpy(kp_un_out, c->pin + L.o_kun, (size_t)m * sizeof(coeb_keypoint));
+        memcpy(u_right_out, c->pin + L.o_ur, (size_t)m * 4);
+        memcpy(depth_out, c->pin + L.o_dep, (size_t)m * 4);
+    }
     if (n > cap) return set_err(c, COEB_ERANGE, "keypoint output capacity too small");
     return COEB_OK;
 }

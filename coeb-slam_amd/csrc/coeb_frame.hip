@@ -208,31 +208,15 @@ __global__ __launch_bounds__(256) void k_rgbd_batch16(const uint8_t* __restrict_
 }
 
 // Frame::UndistortKeyPoints (Frame.cc:579-609): cv::undistortPoints(.., mK, mDistCoef, Mat(), mK)
-// of OpenCV 3.4 (cvUndistortPointsInternal, 5 fixed iterations), one thread per keypoint, in
-// double with the oracle's operation order.  k = (k1, k2, p1, p2, k3); the remaining rational /
-// thin-prism terms of the 14-coefficient model are zero and kept so the sums match.
+// of OpenCV 3.4, one thread per keypoint; the arithmetic is undistort_point (coeb_internal.hpp).
 struct KpRec { float x, y, size, angle, response; int octave, class_id; };
-struct DistK { double k[12]; double fx, fy, cx, cy; };
 
 __global__ __launch_bounds__(256) void k_undistort(const KpRec* __restrict__ in, int n, DistK d, KpRec* __restrict__ out)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     KpRec kp = in[i];
-    const double* k = d.k;
-    const double ifx = 1. / d.fx, ify = 1. / d.fy;
-    double x = ((double)kp.x - d.cx) * ifx, y = ((double)kp.y - d.cy) * ify;
-    const double x0 = x, y0 = y;
-    for (int j = 0; j < 5; j++) {
-        const double r2 = x * x + y * y;
-        const double icdist = (1 + ((k[7] * r2 + k[6]) * r2 + k[5]) * r2) / (1 + ((k[4] * r2 + k[1]) * r2 + k[0]) * r2);
-        const double deltaX = ((((2 * k[2]) * x) * y + k[3] * (r2 + (2 * x) * x)) + k[8] * r2) + (k[9] * r2) * r2;
-        const double deltaY = ((k[2] * (r2 + (2 * y) * y) + ((2 * k[3]) * x) * y) + k[10] * r2) + (k[11] * r2) * r2;
-        x = (x0 - deltaX) * icdist;
-        y = (y0 - deltaY) * icdist;
-    }
-    kp.x = (float)(d.fx * x + d.cx);
-    kp.y = (float)(d.fy * y + d.cy);
+    undistort_point(d, kp.x, kp.y);
     out[i] = kp;
 }
 

@@ -156,6 +156,30 @@ static inline __host__ __device__ int key_x(uint32_t k) { return (int)(k & 0xFFF
 static inline __host__ __device__ int key_y(uint32_t k) { return (int)((k >> 12) & 0xFFFu); }
 static inline __host__ __device__ int key_s(uint32_t k) { return (int)(k >> 24); }
 
+// Frame::UndistortKeyPoints (Frame.cc:579-609) for one point: cv::undistortPoints(.., mK,
+// mDistCoef, Mat(), mK) of OpenCV 3.4 (cvUndistortPointsInternal, 5 fixed iterations) in double
+// with the oracle's operation order.  k = (k1, k2, p1, p2, k3); the remaining rational /
+// thin-prism terms of the 14-coefficient model are zero and kept so the sums match.  The one
+// copy of this arithmetic: k_undistort (coeb_frame.hip) and k_frame_tail (coeb_capi.hip) call it.
+struct DistK { double k[12]; double fx, fy, cx, cy; };
+__device__ __forceinline__ void undistort_point(const DistK& d, float& px, float& py)
+{
+    const double* k = d.k;
+    const double ifx = 1. / d.fx, ify = 1. / d.fy;
+    double x = ((double)px - d.cx) * ifx, y = ((double)py - d.cy) * ify;
+    const double x0 = x, y0 = y;
+    for (int j = 0; j < 5; j++) {
+        const double r2 = x * x + y * y;
+        const double icdist = (1 + ((k[7] * r2 + k[6]) * r2 + k[5]) * r2) / (1 + ((k[4] * r2 + k[1]) * r2 + k[0]) * r2);
+        const double deltaX = ((((2 * k[2]) * x) * y + k[3] * (r2 + (2 * x) * x)) + k[8] * r2) + (k[9] * r2) * r2;
+        const double deltaY = ((k[2] * (r2 + (2 * y) * y) + ((2 * k[3]) * x) * y) + k[10] * r2) + (k[11] * r2) * r2;
+        x = (x0 - deltaX) * icdist;
+        y = (y0 - deltaY) * icdist;
+    }
+    px = (float)(d.fx * x + d.cx);
+    py = (float)(d.fy * y + d.cy);
+}
+
 // ---- launch wrappers (coeb_extract.hip / coeb_match.hip) ----
 int oct_timing_read(long long* out);   // COEB_OCT_CLOCK builds: [4096][6] per-workgroup k_octree clocks
 int fast_timing_read(unsigned long long* out);   // COEB_FAST_CLOCK builds: per-cell k_fast phase sums

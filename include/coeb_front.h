@@ -19,6 +19,9 @@
  *   coeb_boxes_from_int64           <- ImageGrabber::GrabRGBD box copy
  *                                      Examples/ROS/ORB-SLAM2/src/ros_rgbd.cc:106-115
  *   coeb_stereo_from_rgbd           <- Frame::ComputeStereoFromRGBD  src/Frame.cc:820-842
+ *   coeb_frame_rgbd                 <- the RGB-D Frame constructor's tail  src/Frame.cc:214-223:
+ *                                      ExtractORB, N = mvKeys.size(), UndistortKeyPoints (:579-609)
+ *                                      and ComputeStereoFromRGBD (:820-842) on one host frame
  *   coeb_match_lastframe            <- ORBmatcher::SearchByProjection(Frame&, const Frame&,
  *                                      const float th, const bool bMono)
  *                                      include/ORBmatcher.h:52, src/ORBmatcher.cc:1329-1471
@@ -347,6 +350,27 @@ int coeb_rgbd_preprocess_batch_device(coeb_ctx* ctx, const uint8_t* d_img, int c
  * dist[0] == 0 copies (Frame.cc:581-585).  out may equal kps. */
 int coeb_undistort_keypoints(coeb_ctx* ctx, const coeb_camera* cam, const float dist[5], const coeb_keypoint* kps,
                              int n, coeb_keypoint* out);
+/* Frame RGB-D ctor tail on one host frame (src/Frame.cc:214-223): ORBextractor::operator(),
+ * UndistortKeyPoints (:579-609), ComputeStereoFromRGBD (:820-842), one synchronisation.
+ * gray / stride / boxes / tm_xy / blur_flag / cap / n_out as in coeb_extract (an empty image
+ * returns COEB_OK with *n_out = 0; n > cap returns COEB_ERANGE with the first cap entries of every
+ * output written); kp_out and desc_out are byte-identical to coeb_extract's.
+ * depth: width x height, depth_stride in bytes, depth_type / depth_scale as in
+ * coeb_rgbd_preprocess (a 32F map with |depth_scale - 1| <= 1e-5 is read unchanged); only the
+ * values under the keypoints are converted, so a 16U map needs no convertTo beforehand
+ * (Tracking.cc:227).  dist = (k1, k2, p1, p2, k3); NULL or dist[0] == 0 copies the keys
+ * (Frame.cc:581-585).  cam supplies fx, fy, cx, cy (undistortion) and bf.  Per keypoint i:
+ * d = depth(int(kp.y), int(kp.x)) at the RAW keypoint; depth_out[i] = d > 0 ? d : -1;
+ * u_right_out[i] = d > 0 ? kp_un.x - bf / d : -1 from the UNDISTORTED x (:829-839); NaN and
+ * negative depth give -1.  kp_un_out may be NULL; the other outputs are required.  The context
+ * holds the frame afterwards as after coeb_extract (coeb_debug_read). */
+int coeb_frame_rgbd(coeb_ctx* ctx, const uint8_t* gray, int width, int height, size_t stride,
+                    const void* depth, size_t depth_stride, int depth_type, float depth_scale,
+                    const coeb_camera* cam, const float dist[5],
+                    const coeb_box* boxes, int nbox, const float* tm_xy, int ntm,
+                    const int32_t* blur_flag, int nblur,
+                    coeb_keypoint* kp_out, coeb_keypoint* kp_un_out, uint8_t* desc_out,
+                    float* u_right_out, float* depth_out, int cap, int* n_out);
 /* yolov5_ros_msgs/BoundingBox (int64 xmin, ymin, xmax, ymax) -> coeb_box, as GrabRGBD converts */
 int coeb_boxes_from_int64(const int64_t* xyxy, int nbox, coeb_box* out);
 
