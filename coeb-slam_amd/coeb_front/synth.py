@@ -59,6 +59,62 @@ def make_depth(w, h, z=DEPTH_Z):
     return np.full((h, w), z, dtype=np.float32)
 
 
+HOLE_VALUES = (0.0, np.nan, -1.5)
+
+
+def depth_sequence(w, h, n, first=0, seed=900, holes=0.3):
+    """Depth maps (n, h, w) f32 of frames first .. first+n-1 that differ per frame and have
+    holes, as a TUM sequence does: frame k is the smooth surface
+    2.0 + 0.3 sin(x/97 + k) + 0.2 cos(y/61 - 0.5 k), with 16x16 tiles knocked out with
+    probability `holes`.  A knocked-out tile holds, chosen per tile, 0.0, NaN or -1.5: every
+    value ComputeStereoFromRGBD's `d > 0` rejects.  No +inf: the reference unprojects it to an
+    infinite MapPoint, which the single-frame special-value tests cover, not the batch chain.
+    Frame k depends on (w, h, k, seed) only, so shards of a sequence agree with the whole."""
+    yy, xx = np.indices((h, w)).astype(np.float64)
+    th, tw = (h + 15) // 16, (w + 15) // 16
+    vals = np.array(HOLE_VALUES, np.float32)
+    out = np.empty((n, h, w), np.float32)
+    for i in range(n):
+        k = first + i
+        d = (2.0 + 0.3 * np.sin(xx / 97.0 + k) + 0.2 * np.cos(yy / 61.0 - 0.5 * k)).astype(np.float32)
+        rng = np.random.default_rng(seed * 7919 + k + 1)
+        knocked = rng.random((th, tw)) < holes
+        kind = rng.integers(0, len(vals), (th, tw))
+        kn = np.repeat(np.repeat(knocked, 16, axis=0), 16, axis=1)[:h, :w]
+        fill = np.repeat(np.repeat(vals[kind], 16, axis=0), 16, axis=1)[:h, :w]
+        out[i] = np.where(kn, fill, d)
+    return out
+
+
+def raw_depth_u16(depth, factor=5000.0):
+    """Float depth maps as TUM 16UC1 raw depth: holes of every kind (0, NaN, negative) become 0,
+    the rest round(z * factor).  Returns (u16, f32): the raw maps and what GrabImageRGBD's
+    convertTo(CV_32F, 1 / factor) makes of them (Tracking.cc:227-228), i.e. the float maps a
+    reference chain over the same input must use."""
+    depth = np.asarray(depth, np.float32)
+    ok = depth > 0                                   # False for NaN
+    q = np.rint(np.where(ok, depth, 0).astype(np.float64) * factor)
+    u16 = np.clip(q, 0, 65535).astype(np.uint16)
+    return u16, u16.astype(np.float32) * np.float32(1.0 / factor)
+
+
+def perturbed_poses(n, first=0):
+    """Predicted poses (n, 4, 4) f32 of frames first .. first+n-1, a different full-rank one per
+    frame: motion_pose() left-multiplied by a small rotation (1, 1.25 or 1.5 degrees, about y on
+    even frames and x on odd ones, the sign flipping every second frame) plus a z translation of
+    +0.25 / -0.2 / 0 m on a 3-frame cycle (forward, backward and sideways level windows in
+    SearchByProjection).  Frame k depends on k only."""
+    out = np.empty((n, 4, 4), np.float32)
+    for i in range(n):
+        k = first + i
+        deg = (1.0 + 0.25 * (k % 3)) * (1.0 if (k // 2) % 2 == 0 else -1.0)
+        R = rotated_pose(deg, axis=1 if k % 2 == 0 else 0, t=(0, 0, 0))
+        T = (R.astype(np.float64) @ motion_pose().astype(np.float64)).astype(np.float32)
+        T[2, 3] += np.float32((0.25, -0.2, 0.0)[k % 3])
+        out[i] = T
+    return out
+
+
 def motion_pose(z=DEPTH_Z, fx=TUM_FX, fy=TUM_FY):
     """Tcw of frame k+1 relative to Tcw(k) = I for the synthetic (+2,+1) px motion."""
     T = np.eye(4, dtype=np.float32)

@@ -2073,7 +2073,8 @@ int coeb_marker_synchronize(coeb_marker* m)
 }
 
 /* Debug readback of intermediate buffers of frame f of the last batch (test support):
- * what = "pyr" | "blur" | "cand_n" | "lvl_n" | "lvl_kp" | "dyn"; copies min(bytes, size). */
+ * what = "pyr" | "blur" | "cand_n" | "lvl_n" | "lvl_kp" | "dyn" | "u_right" | "kp_depth"; copies
+ * min(bytes, size). */
 int coeb_debug_read(coeb_ctx* c, const char* what, int f, void* host, size_t bytes, size_t* size_out)
 {
     if (c) join_pose(c);
@@ -2159,6 +2160,12 @@ int coeb_debug_read(coeb_ctx* c, const char* what, int f, void* host, size_t byt
     else if (w == "lvl_n") { src = (const uint8_t*)c->ex.lvl_n.p + (size_t)f * P.L * 4; n = (size_t)P.L * 4; }
     else if (w == "lvl_kp") { src = (const uint8_t*)c->ex.lvl_kp.p + (size_t)f * P.lvl_stride * 4; n = (size_t)P.lvl_stride * 4; }
     else if (w == "dyn") { src = (const uint8_t*)c->ex.dyn.p + (size_t)f * sizeof(DynMask); n = sizeof(DynMask); }
+    else if (w == "u_right" || w == "kp_depth") {
+        // k_prep's mvuRight / mvDepth of frame f's kcap keypoint slots (the last batch matcher's)
+        const DevArr<float>& a = w == "u_right" ? c->bm.b_ur : c->bm.b_dep;
+        if (!a.p || a.bytes < (size_t)c->batch_frames * P.kcap * 4) return COEB_EINVAL;
+        src = (const uint8_t*)(a.p + (size_t)f * P.kcap); n = (size_t)P.kcap * 4;
+    }
     else if (w == "plan") { if (size_out) *size_out = sizeof(Plan); if (host) memcpy(host, &P, std::min(bytes, sizeof(Plan))); return COEB_OK; }
     else return COEB_EINVAL;
     if (size_out) *size_out = n;

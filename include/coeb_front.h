@@ -491,7 +491,9 @@ int coeb_device_count(void);
 /* Test support: copy an intermediate buffer of frame `frame` of the last batch to the host.
  * what: "pyr" (levels 1..L-1, packed), "blur" (levels 0..L-1), "cand_n" (FAST corners per
  * cell), "lvl_n" (keypoints per level), "lvl_kp" (packed level keypoints), "dyn" (mask
- * rectangles), "plan", "search_path" (int32 {path, iterations} of the last
+ * rectangles), "plan", "u_right" / "kp_depth" (float mvuRight / mvDepth of the frame's keypoint
+ * slots as the last coeb_match_batch_device* computed them from the frame's own depth map;
+ * COEB_EINVAL before any batch match), "search_path" (int32 {path, iterations} of the last
  * coeb_match_localmap / coeb_match_keyframe: 0 parallel claims, 1 forced sequential,
  * 2 candidate-list overflow, 3 no convergence; frame ignored; alias "localmap_path").  Copies min(bytes, size); *size_out = full size. */
 int coeb_debug_read(coeb_ctx* ctx, const char* what, int frame, void* host, size_t bytes, size_t* size_out);

@@ -821,3 +821,44 @@ def test_oracle_track_chain_properties(oracle_mod):
         assert np.all(lm["level"][lm["in_view"] > 0] < 8)
     assert res[1]["local_map"]["in_view"][:stride].sum() == 0          # frame 1 has no KeyFrame f-2
     assert res[3]["nlocal"] == 0 and res[3]["ninliers"] == 0
+
+
+def test_batch_depth_scenarios_reach_their_branches(oracle_mod):
+    """The scenarios of tests/test_gpu_batch_depth.py on the oracle alone: each still reaches the
+    branches it exists for (monocular and stereo edges, LastFrame keypoints without MapPoints,
+    empty neighbours, nobs = 0, re-levelled and rejected local-map points, real outliers) and
+    gives the state lists the GPU tests require.  A change to synth or to the oracle that empties
+    a scenario fails here, without a GPU."""
+    import chain_util as cu
+    from coeb_front import synth
+    O = oracle_mod
+    ex = O.Extractor()
+    isg = np.array(ex.p.inv_sigma2[:8], np.float32)
+    # the generators: deterministic per global frame (shards agree), holes of every kind, no +inf
+    d = synth.depth_sequence(640, 480, 8)
+    assert np.array_equal(synth.depth_sequence(640, 480, 3, first=4).view(np.uint32), d[4:7].view(np.uint32))
+    hole = ~(d > 0)
+    assert 0.2 < hole.mean() < 0.4 and not np.isinf(d).any()
+    assert np.isnan(d).any() and (d == 0).any() and (d < 0).any()
+    assert not np.array_equal(d[0], d[1]) and 1.4 < d[~hole].min() and d[~hole].max() < 2.6
+    u16, df = synth.raw_depth_u16(d)
+    assert u16.dtype == np.uint16 and np.array_equal(u16 == 0, hole)
+    assert np.array_equal(df[2].view(np.uint32), O.depth_to_float(u16[2], np.float32(1 / 5000.0)).view(np.uint32))
+    assert np.abs(df - d)[~hole].max() <= 0.5 / 5000 + 1e-6
+    P = synth.perturbed_poses(8)
+    assert np.array_equal(synth.perturbed_poses(3, first=5), P[5:8])
+    assert len({p.tobytes() for p in P}) == 8
+    for p in P:
+        R = p[:3, :3].astype(np.float64)
+        assert np.allclose(R @ R.T, np.eye(3), atol=1e-6) and 0.9995 < (np.trace(R) - 1) / 2 < 0.99986  # 1-1.5 deg
+    # the chains
+    for nkf in (2, 1):
+        _, res = cu.run_oracle(O, ex, cu.scenario_holes(), cu.KCAP, isg, nkf=nkf)
+        cu.assert_coverage_holes(res)
+    ext, res = cu.run_oracle(O, ex, cu.scenario_degenerate(), cu.KCAP, isg)
+    cu.assert_coverage_degenerate(ext, res)
+    s = cu.scenario_nobs_zero()
+    cu.assert_coverage_nobs_zero(cu.run_oracle(O, ex, s, cu.KCAP, isg)[1], s["Tcw"])
+    cu.assert_coverage_perturbed(cu.run_oracle(O, ex, cu.scenario_perturbed(), cu.KCAP, isg)[1], cu.KCAP)
+    cu.assert_coverage_lost_neighbours(cu.run_oracle(O, ex, cu.scenario_lost_neighbours(), cu.KCAP, isg)[1], cu.KCAP)
+    cu.assert_coverage_grab(cu.run_oracle(O, ex, cu.scenario_grab_rgbd(), cu.KCAP, isg)[1])
