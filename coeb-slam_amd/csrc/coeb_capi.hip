@@ -1,8 +1,9 @@
-// coeb_capi.hip -- context, host-side geometry plan and the C-ABI of include/coeb_front.h.
+// coeb_capi.hip -- context and the C-ABI of include/coeb_front.h.
 //
-// Host work here is O(levels + cells) per image size (cached), plus the per-call argument
-// marshalling.  All per-pixel / per-keypoint work runs in the kernels of coeb_extract.hip and
-// coeb_match.hip.  There is no CPU fallback: without a usable gfx950 device coeb_create fails.
+// Host work here is the per-call argument marshalling, plus the geometry plan of coeb_plan.cpp
+// once per image size (cached).  All per-pixel / per-keypoint work runs in the kernels of
+// coeb_extract.hip and coeb_match.hip.  There is no CPU fallback: without a usable gfx950 device
+// coeb_create fails.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,7 +15,7 @@
 #include <vector>
 
 #include "coeb_ctx.hpp"
-#include "coeb_frame_rgbd_host.hpp"
+#include "coeb_single_frame_host.hpp"
 
 static const int8_t kPattern[1024] = {
 #include "../../data/orb_bit_pattern_31.inc"
@@ -24,261 +25,7 @@ static const int8_t kPattern[1024] = {
 // the library concurrently; coeb_last_error(NULL) returns the calling thread's last message
 static thread_local std::string g_last_error;
 
-namespace {
-
-enum { PATCH_SIZE = 31, HALF_PATCH_SIZE = 15, EDGE_THRESHOLD = 19 };
-constexpr int kRoiMax = 64;
 constexpr int kFrameTmCap = 1024;     // T_M points per frame kept on the device (coeb_frame_batch_device)
-
-inline int cv_round(float v) { return (int)lrintf(v); }
-inline int cv_round_d(double v) { return (int)lrint(v); }
-inline int cv_floor(float v) { int i = (int)v; return i - (i > v); }
-inline int cv_ceil_d(double v) { int i = (int)v; return i + (i < v); }
-inline int64_t align256(int64_t v) { return (v + 255) & ~int64_t(255); }
-
-// ORBextractor::ORBextractor (src/ORBextractor.cc:418-477)
-bool make_tables(const coeb_orb_params& prm, Tables& t)
-{
-    if (prm.nlevels < 1 || prm.nlevels > COEB_MAXL || prm.nfeatures < 0 || !(prm.scale_factor > 0)) return false;
-    memset(&t, 0, sizeof(t));
-    t.nfeatures = prm.nfeatures;
-    t.scale_factor = prm.scale_factor;
-    t.nlevels = prm.nlevels;
-    t.scale[0] = 1.0f;
-    t.sigma2[0] = 1.0f;
-    for (int i = 1; i < t.nlevels; i++) {
-        t.scale[i] = (float)((double)t.scale[i - 1] * t.scale_factor);
-        t.sigma2[i] = t.scale[i] * t.scale[i];
-    }
-    for (int i = 0; i < t.nlevels; i++) {
-        t.inv_scale[i] = 1.0f / t.scale[i];
-        t.inv_sigma2[i] = 1.0f / t.sigma2[i];
-    }
-    const float factor = (float)(1.0f / t.scale_factor);
-    float ndesired = t.nfeatures * (1 - factor) / (1 - (float)std::pow((double)factor, (double)t.nlevels));
-    int sum = 0;
-    for (int l = 0; l < t.nlevels - 1; l++) {
-        t.nfeat[l] = cv_round(ndesired);
-        sum += t.nfeat[l];
-        ndesired *= factor;
-    }
-    t.nfeat[t.nlevels - 1] = std::max(t.nfeatures - sum, 0);
-    int v, v0;
-    const int vmax = cv_floor(HALF_PATCH_SIZE * sqrtf(2.f) / 2 + 1);
-    const int vmin = cv_ceil_d(HALF_PATCH_SIZE * sqrtf(2.f) / 2);
-    const double hp2 = HALF_PATCH_SIZE * HALF_PATCH_SIZE;
-    for (v = 0; v <= vmax; ++v) t.umax[v] = cv_round_d(std::sqrt(hp2 - v * v));
-    for (v = HALF_PATCH_SIZE, v0 = 0; v >= vmin; --v) {
-        while (t.umax[v0] == t.umax[v0 + 1]) ++v0;
-        t.umax[v] = v0;
-        ++v0;
-    }
-    return true;
-}
-
-// Gaussian 7-tap sigma 2, Q8 error-diffused
-void gauss_kernel7(int k[7])
-{
-    const int n = 7, n2 = 3;
-    const double scale2X = -0.125 / (2.0 * 2.0);
-    double values[3], sum = 0.0;
-    for (int i = 0, x = 1 - n; i < n2; i++, x += 2) {
-        const double t = std::exp((double)(x * x) * scale2X);
-        values[i] = t;
-        sum += t;
-    }
-    sum = sum * 2.0 + 1.0;
-    const double mul1 = 1.0 / sum;
-    double err = 0.0;
-    int64_t s = 0;
-    for (int i = 0; i < n2; i++) {
-        const double adj = values[i] * mul1 * 256.0 + err;
-        const int64_t q = cv_round_d(adj);
-        err = adj - (double)q;
-        k[i] = k[n - 1 - i] = (int)q;
-        s += q;
-    }
-    k[n2] = (int)(256 - 2 * s);
-}
-
-// cv::resize INTER_LINEAR coefficient tables (imgproc resize.cpp, 8U fixed point)
-int resize_tables(int sw, int sh, int dw, int dh, std::vector<int>& tab)
-{
-    const double scale_x = 1. / ((double)dw / sw), scale_y = 1. / ((double)dh / sh);
-    const size_t base = tab.size();
-    tab.resize(base + 2 * dw + 2 * dh);
-    int* xofs = tab.data() + base;
-    int* alpha = xofs + dw;
-    int* yofs = alpha + dw;
-    int* beta = yofs + dh;
-    int xmax = dw;
-    for (int dx = 0; dx < dw; dx++) {
-        float fx = (float)((dx + 0.5) * scale_x - 0.5);
-        int sx = cv_floor(fx);
-        fx -= sx;
-        if (sx < 0) { fx = 0; sx = 0; }
-        if (sx + 1 >= sw) {
-            xmax = std::min(xmax, dx);
-            if (sx >= sw - 1) { fx = 0; sx = sw - 1; }
-        }
-        xofs[dx] = sx;
-        const int a0 = std::max(-32768, std::min(32767, cv_round((1.f - fx) * 2048)));
-        const int a1 = std::max(-32768, std::min(32767, cv_round(fx * 2048)));
-        alpha[dx] = (a0 & 0xFFFF) | (a1 << 16);
-    }
-    for (int dy = 0; dy < dh; dy++) {
-        float fy = (float)((dy + 0.5) * scale_y - 0.5);
-        const int sy = cv_floor(fy);
-        fy -= sy;
-        yofs[dy] = sy;
-        const int b0 = std::max(-32768, std::min(32767, cv_round((1.f - fy) * 2048)));
-        const int b1 = std::max(-32768, std::min(32767, cv_round(fy * 2048)));
-        beta[dy] = (b0 & 0xFFFF) | (b1 << 16);
-    }
-    return xmax;
-}
-
-bool make_plan(const Tables& t, int W, int H, Plan& P, std::vector<int>& rtab, std::vector<CellDesc>& cells,
-               std::string& err)
-{
-    memset(&P, 0, sizeof(P));
-    P.W = W; P.H = H; P.L = t.nlevels;
-    rtab.clear();
-    cells.clear();
-    if (W > 4096 || H > 4096) { err = "image larger than 4096 px is not supported (12-bit key packing)"; return false; }
-    int64_t pyr = 0, blur = 0, node = 0;
-    int kcap_total = 0, out_total = 0, cell_cap = 1;
-    for (int l = 0; l < t.nlevels; l++) {
-        LevelGeom& g = P.lv[l];
-        g.w = cv_round((float)W * t.inv_scale[l]);     // ComputePyramid :1349
-        g.h = cv_round((float)H * t.inv_scale[l]);
-        g.scale = t.scale[l];
-        g.size_i = (int)(PATCH_SIZE * t.scale[l]);
-        g.pitch = l == 0 ? W : (g.w + 63) & ~63;
-        g.bpitch = (g.w + 63) & ~63;
-        if (l == 0) g.pyr_off = -1;
-        else { g.pyr_off = pyr; pyr = align256(pyr + (int64_t)g.pitch * g.h); }
-        g.blur_off = blur;
-        blur = align256(blur + (int64_t)g.bpitch * ((g.h + 7) & ~7));    // whole 8-row tiles
-        if (l > 0) {
-            while (rtab.size() % 4) rtab.push_back(0);     // 16-byte aligned table rows
-            g.rtab_off = (int)rtab.size();
-            g.xmax = resize_tables(P.lv[l - 1].w, P.lv[l - 1].h, g.w, g.h, rtab);
-            g.rows_ok = 1;
-            for (int c = 0; c < g.w; c += 2) {
-                const int* xofs = rtab.data() + g.rtab_off;
-                if (xofs[std::min(c + 1, g.w - 1)] - (xofs[c] & ~3) > 5) g.rows_ok = 0;
-            }
-            // k_pyr_rows' row descriptors: one 16-byte scalar load per output row
-            while (rtab.size() % 4) rtab.push_back(0);
-            g.yrow_off = (int)rtab.size();
-            const int sh = P.lv[l - 1].h, sp = P.lv[l - 1].pitch;
-            for (int dy = 0; dy < g.h; dy++) {
-                const int q0 = rtab[g.rtab_off + 2 * g.w + dy], bb = rtab[g.rtab_off + 2 * g.w + g.h + dy];
-                const int r0 = q0 >= 0 ? (q0 < sh ? q0 : sh - 1) : 0;
-                const int r1 = q0 + 1 >= 0 ? (q0 + 1 < sh ? q0 + 1 : sh - 1) : 0;
-                rtab.push_back(r0 * sp);
-                rtab.push_back(r1 * sp);
-                rtab.push_back(bb);
-                rtab.push_back(dy * g.pitch);
-            }
-        }
-        // FAST cells (ComputeKeyPointsOctTree :795-829)
-        const int minBorderX = EDGE_THRESHOLD - 3, minBorderY = minBorderX;
-        const int maxBorderX = g.w - EDGE_THRESHOLD + 3, maxBorderY = g.h - EDGE_THRESHOLD + 3;
-        const float width = (float)(maxBorderX - minBorderX), height = (float)(maxBorderY - minBorderY);
-        const float Wc = 30;
-        g.ncols = (int)(width / Wc);
-        g.nrows = (int)(height / Wc);
-        if (g.ncols <= 0 || g.nrows <= 0) { err = "pyramid level too small for the 30-px FAST grid"; return false; }
-        g.wcell = (int)ceilf(width / g.ncols);
-        g.hcell = (int)ceilf(height / g.nrows);
-        g.cell0 = (int)cells.size();
-        for (int i = 0; i < g.nrows; i++) {
-            const float iniY = (float)(minBorderY + i * g.hcell);
-            float maxY = iniY + g.hcell + 6;
-            if (iniY >= maxBorderY - 3) continue;
-            if (maxY > maxBorderY) maxY = (float)maxBorderY;
-            for (int j = 0; j < g.ncols; j++) {
-                const float iniX = (float)(minBorderX + j * g.wcell);
-                float maxX = iniX + g.wcell + 6;
-                if (iniX >= maxBorderX - 6) continue;
-                if (maxX > maxBorderX) maxX = (float)maxBorderX;
-                CellDesc c;
-                c.level = (int16_t)l; c.pad = 0;
-                c.x0 = (int16_t)(int)iniX; c.y0 = (int16_t)(int)iniY;
-                c.rw = (int16_t)((int)maxX - (int)iniX); c.rh = (int16_t)((int)maxY - (int)iniY);
-                c.i = (int16_t)i; c.j = (int16_t)j;
-                if (c.rw > kRoiMax || c.rh > kRoiMax) { err = "FAST cell ROI exceeds 64 px"; return false; }
-                const int ww = std::max(0, c.rw - 6), wh = std::max(0, c.rh - 6);
-                cell_cap = std::max(cell_cap, ((ww + 1) / 2) * ((wh + 1) / 2));
-                P.max_roi_w = std::max(P.max_roi_w, (int)c.rw);
-                P.max_roi_h = std::max(P.max_roi_h, (int)c.rh);
-                cells.push_back(c);
-            }
-        }
-        g.ncells = (int)cells.size() - g.cell0;
-        // DistributeOctTree constants (:549-552, :866-875)
-        g.nfeat = t.nfeat[l];
-        g.nfeat_area = (int)((double)t.nfeat[l] * 0.7);
-        g.maxX = maxBorderX - minBorderX;
-        g.maxY = maxBorderY - minBorderY;
-        g.nini = (int)roundf((float)g.maxX / g.maxY);
-        if (g.nini < 1 || g.nini > 4) { err = "aspect ratio gives an unsupported number of initial octree nodes"; return false; }
-        g.hx = (float)g.maxX / g.nini;
-        int b = 0;
-        for (int i = 0; i <= g.nini; i++) {
-            while (b <= g.maxX + 1 && (int)((float)b / g.hx) < i) b++;
-            g.ini_bound[i] = b;
-        }
-        g.ini_bound[g.nini] = 1 << 20;
-        // list size never exceeds max(N + 2, 4 * nIni)
-        g.out_cap = std::max(g.nfeat + 3, 4 * g.nini) + 5;
-        g.ncap = g.out_cap + 8;
-        g.node_off = node;
-        node += 2 * 8 * (int64_t)g.ncap;
-        g.out_off = out_total;
-        out_total += g.out_cap;
-    }
-    P.ncells = (int)cells.size();
-    P.cell_cap = cell_cap;
-    for (int l = 0; l < t.nlevels; l++) {
-        P.lv[l].kcap_off = kcap_total;
-        P.lv[l].kcap = P.lv[l].ncells * cell_cap;
-        kcap_total += P.lv[l].kcap;
-    }
-    P.pyr_stride = std::max<int64_t>(pyr, 256);
-    P.blur_stride = blur;
-    P.kbuf_stride = kcap_total;
-    P.node_stride = node;
-    P.lvl_stride = out_total;
-    P.kcap = out_total;
-    P.rtab_ints = (int)rtab.size();
-    P.oct_w = 0;
-    for (int l = 0; l < t.nlevels; l++) P.oct_w = std::max(P.oct_w, P.lv[l].ncap);
-    P.oct_w = (P.oct_w + 15) & ~15;
-    // keys kept in LDS per level (more candidates: global ping-pong buffers, slower but exact):
-    // the power of two >= 4.5 x the largest level's features (FAST leaves ~3.8 candidates per
-    // level-0 feature on the config-A frames: 818 median, 934 max for 217), so that config A's
-    // octree needs 31 KB of LDS and five workgroups share a CU (0.091 -> 0.075 ms per step; 768
-    // keys pushed level 0 to the global buffers, 0.102 ms); COEB_OCT_KL overrides
-    int nmax = 0;
-    for (int l = 0; l < t.nlevels; l++) nmax = std::max(nmax, P.lv[l].nfeat);
-    P.oct_kl = 512;
-    while (P.oct_kl < 4096 && P.oct_kl < (9 * nmax + 1) / 2) P.oct_kl *= 2;
-    if (const char* e = coeb_experiment("COEB_OCT_KL")) P.oct_kl = std::max(256, std::min(8192, atoi(e)));
-    P.oct_lds = P.oct_w * (4 + 16 + 4 + 4 + 4 + 1 + 64) + 8 * P.oct_kl;
-    if (P.oct_lds > 150 * 1024) { err = "octree LDS budget exceeded (features per level too large)"; return false; }
-    memcpy(P.umax, t.umax, sizeof(P.umax));
-    // k_describe folds the IC_Angle disc (umax for HALF_PATCH_SIZE 15) into constants
-    static const int kUmaxDisc[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
-    if (memcmp(t.umax, kUmaxDisc, sizeof(kUmaxDisc)) != 0) { err = "unexpected IC_Angle disc (umax)"; return false; }
-    gauss_kernel7(P.gauss);
-
-    return true;
-}
-
-}  // namespace
 
 void prof_begin(ProfileHook* p, const char* name, hipStream_t s)
 {
@@ -329,14 +76,21 @@ namespace {
 // alias): the keypoint count and the first min(count, guess) records and descriptors, so the
 // host reads them after one synchronisation with no copy operations in between (each D2H copy
 // op of the single-frame path cost 5-25 us plus its launch gap, profiles/r06/sf).
+// the delivered records and descriptors, common to k_out_pack and k_frame_tail
+__device__ __forceinline__ void out_pack_copy(const uint32_t* kps, const uint4* desc, int n, int t, int T, uint32_t* out_k,
+                                              uint4* out_d)
+{
+    for (int i = t; i < 7 * n; i += T) out_k[i] = kps[i];          // 28-byte records
+    for (int i = t; i < 2 * n; i += T) out_d[i] = desc[i];         // 32-byte rows
+}
+
 __global__ __launch_bounds__(256) void k_out_pack(const int* counts, const uint32_t* kps, const uint4* desc, int guess,
                                                   int* out_n, uint32_t* out_k, uint4* out_d)
 {
     const int n = min(*counts, guess);
     const int t = blockIdx.x * 256 + threadIdx.x, T = gridDim.x * 256;
     if (t == 0) *out_n = *counts;
-    for (int i = t; i < 7 * n; i += T) out_k[i] = kps[i];          // 28-byte records
-    for (int i = t; i < 2 * n; i += T) out_d[i] = desc[i];         // 32-byte rows
+    out_pack_copy(kps, desc, n, t, T, out_k, out_d);
 }
 
 // k_out_pack's place in coeb_frame_rgbd: the rest of the Frame RGB-D constructor
@@ -392,8 +146,7 @@ __global__ __launch_bounds__(256) void k_frame_tail(FrameTail a)
         a.out_ur[i] = ur;
         a.out_dep[i] = dep;
     }
-    for (int i = t; i < 7 * n; i += T) a.out_k[i] = a.kps[i];          // 28-byte records
-    for (int i = t; i < 2 * n; i += T) a.out_d[i] = a.desc[i];         // 32-byte rows
+    out_pack_copy(a.kps, a.desc, n, t, T, a.out_k, a.out_d);
 }
 
 // Inputs of one call packed at 16-byte aligned offsets of the pinned staging buffer, moved to
@@ -461,7 +214,8 @@ int ensure_plan(coeb_ctx* c, int W, int H)
         return set_err(c, COEB_EINVAL, "image size outside the context limits");
     std::string err;
     Plan P;
-    if (!make_plan(c->tab, W, H, P, c->rtab, c->cells, err)) return set_err(c, COEB_EINVAL, err);
+    const char* kl = coeb_experiment("COEB_OCT_KL");
+    if (!make_plan(c->tab, W, H, kl ? atoi(kl) : 0, P, c->rtab, c->cells, err)) return set_err(c, COEB_EINVAL, err);
     // the plan, rtab and cells are rewritten in place below: batches still in flight on the
     // context's streams (pyramid / FAST / octree / describe read them) must finish first
     int rc;
@@ -751,10 +505,9 @@ int err_word_async(coeb_ctx* c, uint8_t* dst)
     return 0;
 }
 
-int err_word_seen(coeb_ctx* c, const uint8_t* src)
+// h: the error word as read back.  Non-zero: the device word is reset and the call fails.
+int err_word_report(coeb_ctx* c, int h)
 {
-    int h = 0;
-    memcpy(&h, src, 4);
     if (!h) return 0;
     char msg[160];
     snprintf(msg, sizeof msg, "internal capacity exceeded (device error bits 0x%x)", h);
@@ -762,21 +515,100 @@ int err_word_seen(coeb_ctx* c, const uint8_t* src)
     return set_err(c, COEB_ERANGE, msg);
 }
 
+int err_word_seen(coeb_ctx* c, const uint8_t* src)
+{
+    int h = 0;
+    memcpy(&h, src, 4);
+    return err_word_report(c, h);
+}
+
+// the word fetched by a copy and a synchronisation of its own
 int check_err_word(coeb_ctx* c)
 {
     main_stream(c);
-    int* derr = c->ex.err.p;
-    if (!derr) return 0;
+    if (!c->ex.err.p) return 0;
     int h = 0;
-    HIP_TRY(c, hipMemcpyAsync(&h, derr, 4, hipMemcpyDeviceToHost, main_stream(c)));
+    HIP_TRY(c, hipMemcpyAsync(&h, c->ex.err.p, 4, hipMemcpyDeviceToHost, main_stream(c)));
     HIP_TRY(c, hipStreamSynchronize(main_stream(c)));
-    if (h) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "internal capacity exceeded (device error bits 0x%x)", h);
-        HIP_TRY(c, hipMemsetAsync(derr, 0, 4, main_stream(c)));
-        return set_err(c, COEB_ERANGE, msg);
-    }
+    return err_word_report(c, h);
+}
+
+// What coeb_extract and coeb_frame_rgbd enqueue on the context stream between pinned() and their
+// output kernel: the gray rows through the page-locked buffer into gray_stage, the dynamic-mask
+// inputs staged at L's offsets, and the extraction of the one frame; b holds its buffers.
+// Pinned staging at both ends: the image rows go through the page-locked buffer (one DMA, no
+// runtime pinning of the caller's pages), and the results come back into it behind the kernels
+// (a pageable round trip each cost 120-170 us on the box, profiles/r06/sf).
+int enqueue_single_frame(coeb_ctx* c, const SingleFrameLayout& L, const uint8_t* gray, int W, int H, size_t stride,
+                         const coeb_box* boxes, int nbox, const float* tm_xy, int ntm, const int32_t* blur_flag, int nblur,
+                         ExtractBufs& b)
+{
+    uint8_t* dgray = c->ex.gray_stage.p;
+    hipStream_t s = main_stream(c);
+    single_frame_stage_rows(c->pin, gray, H, (size_t)W, stride);
+    HIP_TRY(c, hipMemcpyAsync(dgray, c->pin, (size_t)W * H, hipMemcpyHostToDevice, s));
+    int32_t* box_off = reinterpret_cast<int32_t*>(c->pin + L.o_bo);
+    int32_t* tm_off = reinterpret_cast<int32_t*>(c->pin + L.o_to);
+    int32_t* blur = reinterpret_cast<int32_t*>(c->pin + L.o_bl);
+    box_off[0] = 0; box_off[1] = nbox; tm_off[0] = 0; tm_off[1] = ntm;
+    for (int i = 0; i < nbox; i++)                      // missing flags (or a null array) read as 0
+        blur[i] = (blur_flag && i < nblur) ? blur_flag[i] : 0;
+    if (nbox) memcpy(c->pin + L.o_dyn, boxes, (size_t)nbox * sizeof(coeb_box));
+    if (ntm) memcpy(c->pin + L.o_tm, tm_xy, (size_t)ntm * 8);
+    int rc;
+    if ((rc = extract_bufs(c, 1, b))) return rc;
+    if ((rc = upload_dyn(c, 1, nbox ? reinterpret_cast<const coeb_box*>(c->pin + L.o_dyn) : nullptr, box_off,
+                         ntm ? reinterpret_cast<const float*>(c->pin + L.o_tm) : nullptr, tm_off, nbox ? blur : nullptr, b)))
+        return rc;
+    b.gray = dgray;
+    // one frame on one stream: the side stream's fork / join cost more than the overlap it buys
+    // at F = 1 (0.389 vs 0.350 ms per single-frame step, profiles/r06/sf)
+    if (launch_extract(c->plan, c->pl.plan.p, b, 1, s, &c->hook, nullptr))
+        return hip_err(c, hipGetLastError(), "launch_extract");
+    c->batch_frames = 1;
+    c->batch_gray = dgray;
     return 0;
+}
+
+// Behind the output kernel: the error word, the call's one synchronisation, and the keypoint
+// count the kernel left at L.o_n.
+int finish_single_frame(coeb_ctx* c, const SingleFrameLayout& L, hipStream_t s, int* n)
+{
+    int rc;
+    if ((rc = err_word_async(c, c->pin + L.o_n + 16))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if ((rc = err_word_seen(c, c->pin + L.o_n + 16))) return rc;
+    memcpy(n, c->pin + L.o_n, 4);
+    return 0;
+}
+
+// the projection searches' result as the caller takes it: hout = match[cs], nmatch
+void match_copy_out(const int32_t* hout, int n, int cs, int32_t* match_out, int* nmatches)
+{
+    if (n && match_out) memcpy(match_out, hout, (size_t)n * 4);
+    *nmatches = hout[cs];
+}
+
+// device buffers of coeb_match_localmap / coeb_match_keyframe: cs current keypoints, qs points
+int projection_bufs(coeb_ctx* c, int cs, int qs)
+{
+    SingleFrameBufs& sf = c->sf;
+    int rc;
+    if ((rc = ensure(c, sf.l_out, (size_t)cs + 1)) || (rc = ensure(c, sf.l_list, (size_t)qs * kCQ)) ||
+        (rc = ensure(c, c->ex.err, 4)) || (rc = ensure(c, sf.l_path, 2)))
+        return rc;
+    return 0;
+}
+
+// their epilogue: one copy back of match[cs], nmatch, the synchronisation, the error word
+int projection_finish(coeb_ctx* c, hipStream_t s, int n, int cs, int32_t* match_out, int* nmatches)
+{
+    int32_t* hout = reinterpret_cast<int32_t*>(c->pin);
+    HIP_TRY(c, hipMemcpyAsync(hout, c->sf.l_out.p, ((size_t)cs + 1) * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (int rc = check_err_word(c)) return rc;
+    match_copy_out(hout, n, cs, match_out, nmatches);
+    return COEB_OK;
 }
 
 }  // namespace
@@ -1055,51 +887,17 @@ int coeb_extract(coeb_ctx* c, const uint8_t* gray, int W, int H, size_t stride, 
 {
     if (!c || !n_out) return set_err(c, COEB_EINVAL, "coeb_extract: invalid arguments");
     *n_out = 0;
-    if (!gray || W <= 0 || H <= 0) return COEB_OK;          // _image.empty() -> return (:1096-1097)
-    if (stride < (size_t)W) return set_err(c, COEB_EINVAL, "stride < width");
-    if (nbox < 0 || nbox > COEB_MAXBOX || ntm < 0 || nblur < 0) return set_err(c, COEB_EINVAL, "bad box/T_M counts");
-    if ((nbox && !boxes) || (ntm && !tm_xy)) return set_err(c, COEB_EINVAL, "coeb_extract: null box / T_M array");
+    const char* why = "";
+    int rc = single_frame_check(gray, W, H, stride, boxes, nbox, tm_xy, ntm, nblur, &why);
+    if (rc == 1) return COEB_OK;                            // _image.empty() -> return (:1096-1097)
+    if (rc) return set_err(c, rc, why == kWhyNullDynArrays ? std::string("coeb_extract: ") + why : why);
     (void)hipSetDevice(c->device);
-    int rc;
-    if ((rc = ensure_plan(c, W, H))) return rc;
-    if ((rc = ensure(c, c->ex.gray_stage, (size_t)W * H))) return rc;
-    uint8_t* dgray = c->ex.gray_stage.p;
-    // pinned staging at both ends: the image rows go through the context's page-locked buffer
-    // (one DMA, no runtime pinning of the caller's pages), and the results come back into it
-    // behind the kernels -- the count and the first `guess` records in one synchronisation
-    // (a pageable round trip each cost 120-170 us on the box, profiles/r06/sf)
-    const size_t img = ((size_t)W * H + 255) & ~(size_t)255;
+    if ((rc = ensure_plan(c, W, H)) || (rc = ensure(c, c->ex.gray_stage, (size_t)W * H))) return rc;
     const int kcap = c->plan.kcap;
-    const size_t o_n = img, o_k = img + 256, o_d = o_k + (((size_t)kcap * sizeof(coeb_keypoint) + 255) & ~(size_t)255);
-    // the dynamic-mask inputs (boxes, T_M, blur flags, their offsets) staged behind the results
-    const size_t o_dyn = o_d + (((size_t)kcap * 32 + 255) & ~(size_t)255);
-    const size_t o_bo = o_dyn + (size_t)nbox * sizeof(coeb_box), o_bl = o_bo + 16, o_to = o_bl + (size_t)nbox * 4 + 16,
-                 o_tm = o_to + 16;
-    if ((rc = pinned(c, o_tm + (size_t)ntm * 8))) return rc;
-    if (stride == (size_t)W) memcpy(c->pin, gray, (size_t)W * H);
-    else
-        for (int y = 0; y < H; y++) memcpy(c->pin + (size_t)y * W, gray + (size_t)y * stride, (size_t)W);
-    HIP_TRY(c, hipMemcpyAsync(dgray, c->pin, (size_t)W * H, hipMemcpyHostToDevice, main_stream(c)));
-    int32_t* box_off = reinterpret_cast<int32_t*>(c->pin + o_bo);
-    int32_t* tm_off = reinterpret_cast<int32_t*>(c->pin + o_to);
-    int32_t* blur = reinterpret_cast<int32_t*>(c->pin + o_bl);
-    box_off[0] = 0; box_off[1] = nbox; tm_off[0] = 0; tm_off[1] = ntm;
-    for (int i = 0; i < nbox; i++)                      // missing flags (or a null array) read as 0
-        blur[i] = (blur_flag && i < nblur) ? blur_flag[i] : 0;
-    if (nbox) memcpy(c->pin + o_dyn, boxes, (size_t)nbox * sizeof(coeb_box));
-    if (ntm) memcpy(c->pin + o_tm, tm_xy, (size_t)ntm * 8);
+    const SingleFrameLayout L = single_frame_layout(W, H, kcap, nbox, ntm);
+    if ((rc = pinned(c, L.total))) return rc;
     ExtractBufs b;
-    if ((rc = extract_bufs(c, 1, b))) return rc;
-    if ((rc = upload_dyn(c, 1, nbox ? reinterpret_cast<const coeb_box*>(c->pin + o_dyn) : nullptr, box_off,
-                         ntm ? reinterpret_cast<const float*>(c->pin + o_tm) : nullptr, tm_off, nbox ? blur : nullptr, b)))
-        return rc;
-    b.gray = dgray;
-    // one frame on one stream: the side stream's fork / join cost more than the overlap it buys
-    // at F = 1 (0.389 vs 0.350 ms per single-frame step, profiles/r06/sf)
-    if (launch_extract(c->plan, c->pl.plan.p, b, 1, main_stream(c), &c->hook, nullptr))
-        return hip_err(c, hipGetLastError(), "launch_extract");
-    c->batch_frames = 1;
-    c->batch_gray = dgray;
+    if ((rc = enqueue_single_frame(c, L, gray, W, H, stride, boxes, nbox, tm_xy, ntm, blur_flag, nblur, b))) return rc;
     // with both arrays set, k_out_pack delivers every record the caller can take in the same
     // synchronisation as the count: it copies min(count, guess) records and count <= kcap (kcap
     // sums the levels' out_cap, make_plan), so min(count, cap) <= guess and the second round trip
@@ -1107,24 +905,21 @@ int coeb_extract(coeb_ctx* c, const uint8_t* gray, int W, int H, size_t stride, 
     const int guess = (kp_out && desc_out) ? std::min(kcap, std::max(cap, 0)) : 0;
     hipStream_t s = main_stream(c);
     hipLaunchKernelGGL(k_out_pack, dim3(16), dim3(256), 0, s, b.counts, static_cast<const uint32_t*>(b.kps),
-                       reinterpret_cast<const uint4*>(b.desc), guess, reinterpret_cast<int*>(c->pin_dev + o_n),
-                       reinterpret_cast<uint32_t*>(c->pin_dev + o_k), reinterpret_cast<uint4*>(c->pin_dev + o_d));
+                       reinterpret_cast<const uint4*>(b.desc), guess, reinterpret_cast<int*>(c->pin_dev + L.o_n),
+                       reinterpret_cast<uint32_t*>(c->pin_dev + L.o_k), reinterpret_cast<uint4*>(c->pin_dev + L.o_d));
     HIP_TRY(c, hipGetLastError());
-    if ((rc = err_word_async(c, c->pin + o_n + 16))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if ((rc = err_word_seen(c, c->pin + o_n + 16))) return rc;
     int n = 0;
-    memcpy(&n, c->pin + o_n, 4);
+    if ((rc = finish_single_frame(c, L, s, &n))) return rc;
     *n_out = n;
     const int m = std::min(n, cap);
     if (m > guess) {                         // one output array only (guess = 0): fetch it by a copy
         if (kp_out)
-            HIP_TRY(c, hipMemcpyAsync(c->pin + o_k, b.kps, (size_t)m * sizeof(coeb_keypoint), hipMemcpyDeviceToHost, s));
-        if (desc_out) HIP_TRY(c, hipMemcpyAsync(c->pin + o_d, b.desc, (size_t)m * 32, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipMemcpyAsync(c->pin + L.o_k, b.kps, (size_t)m * sizeof(coeb_keypoint), hipMemcpyDeviceToHost, s));
+        if (desc_out) HIP_TRY(c, hipMemcpyAsync(c->pin + L.o_d, b.desc, (size_t)m * 32, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
     }
-    if (m > 0 && kp_out) memcpy(kp_out, c->pin + o_k, (size_t)m * sizeof(coeb_keypoint));
-    if (m > 0 && desc_out) memcpy(desc_out, c->pin + o_d, (size_t)m * 32);
+    if (m > 0 && kp_out) memcpy(kp_out, c->pin + L.o_k, (size_t)m * sizeof(coeb_keypoint));
+    if (m > 0 && desc_out) memcpy(desc_out, c->pin + L.o_d, (size_t)m * 32);
     if (n > cap) return set_err(c, COEB_ERANGE, "keypoint output capacity too small");
     return COEB_OK;
 }
@@ -1142,39 +937,19 @@ int coeb_frame_rgbd(coeb_ctx* c, const uint8_t* gray, int W, int H, size_t strid
     if (rc == 1) return COEB_OK;                            // _image.empty() -> return (:1096-1097)
     if (rc) return set_err(c, rc, std::string("coeb_frame_rgbd: ") + why);
     (void)hipSetDevice(c->device);
-    if ((rc = ensure_plan(c, W, H))) return rc;
-    if ((rc = ensure(c, c->ex.gray_stage, (size_t)W * H))) return rc;
-    uint8_t* dgray = c->ex.gray_stage.p;
+    if ((rc = ensure_plan(c, W, H)) || (rc = ensure(c, c->ex.gray_stage, (size_t)W * H))) return rc;
     const int kcap = c->plan.kcap;
     // the page-locked buffer is sized for the whole call up front: it must not move once the
     // extraction has been enqueued
     const FrameRgbdLayout L = frame_rgbd_layout(W, H, kcap, nbox, ntm, depth_type);
     if ((rc = pinned(c, L.total))) return rc;
     // 1. the gray rows and the extraction, as coeb_extract enqueues them
-    hipStream_t s = main_stream(c);
-    frame_rgbd_stage_rows(c->pin, gray, H, (size_t)W, stride);
-    HIP_TRY(c, hipMemcpyAsync(dgray, c->pin, (size_t)W * H, hipMemcpyHostToDevice, s));
-    int32_t* box_off = reinterpret_cast<int32_t*>(c->pin + L.o_bo);
-    int32_t* tm_off = reinterpret_cast<int32_t*>(c->pin + L.o_to);
-    int32_t* blur = reinterpret_cast<int32_t*>(c->pin + L.o_bl);
-    box_off[0] = 0; box_off[1] = nbox; tm_off[0] = 0; tm_off[1] = ntm;
-    for (int i = 0; i < nbox; i++)                      // missing flags (or a null array) read as 0
-        blur[i] = (blur_flag && i < nblur) ? blur_flag[i] : 0;
-    if (nbox) memcpy(c->pin + L.o_dyn, boxes, (size_t)nbox * sizeof(coeb_box));
-    if (ntm) memcpy(c->pin + L.o_tm, tm_xy, (size_t)ntm * 8);
     ExtractBufs b;
-    if ((rc = extract_bufs(c, 1, b))) return rc;
-    if ((rc = upload_dyn(c, 1, nbox ? reinterpret_cast<const coeb_box*>(c->pin + L.o_dyn) : nullptr, box_off,
-                         ntm ? reinterpret_cast<const float*>(c->pin + L.o_tm) : nullptr, tm_off, nbox ? blur : nullptr, b)))
-        return rc;
-    b.gray = dgray;
-    if (launch_extract(c->plan, c->pl.plan.p, b, 1, s, &c->hook, nullptr))
-        return hip_err(c, hipGetLastError(), "launch_extract");
-    c->batch_frames = 1;
-    c->batch_gray = dgray;
+    if ((rc = enqueue_single_frame(c, L, gray, W, H, stride, boxes, nbox, tm_xy, ntm, blur_flag, nblur, b))) return rc;
+    hipStream_t s = main_stream(c);
     // 2. while the device extracts, the host packs the depth rows into the buffer (16U as it is:
     // half the bytes, and only the gathered values are ever converted)
-    frame_rgbd_stage_rows(c->pin + L.o_depth, depth, H, L.depth_row, depth_stride);
+    single_frame_stage_rows(c->pin + L.o_depth, depth, H, L.depth_row, depth_stride);
     // 3. the tail kernel behind the extraction
     FrameTail a;
     memset(&a, 0, sizeof(a));
@@ -1200,13 +975,10 @@ int coeb_frame_rgbd(coeb_ctx* c, const uint8_t* gray, int W, int H, size_t strid
     prof_end(&c->hook, s);
     HIP_TRY(c, hipGetLastError());
     // 4. the error word, and the call's one synchronisation
-    if ((rc = err_word_async(c, c->pin + L.o_n + 16))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if ((rc = err_word_seen(c, c->pin + L.o_n + 16))) return rc;
     int n = 0;
-    memcpy(&n, c->pin + L.o_n, 4);
+    if ((rc = finish_single_frame(c, L, s, &n))) return rc;
     *n_out = n;
-    const int m = std::min(n, a.guess);                     // guess = min(kcap, cap) and n <= kcap
+    const int m = std::min(n, a.guess);                    // guess = min(kcap, cap) and n <= kcap
     if (m > 0) {
         memcpy(kp_out, c->pin + L.o_k, (size_t)m * sizeof(coeb_keypoint));
         memcpy(desc_out, c->pin + L.o_d, (size_t)m * 32);
@@ -1304,9 +1076,8 @@ int coeb_match_lastframe(coeb_ctx* c, const coeb_camera* cam, const coeb_curfram
     if ((rc = err_word_async(c, c->pin + o_err))) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
     if ((rc = err_word_seen(c, c->pin + o_err))) return rc;
-    const int32_t* hout = reinterpret_cast<const int32_t*>(c->pin + o_res);    // written by k_match in place
-    if (n && match_out) memcpy(match_out, hout, (size_t)n * 4);
-    *nmatches = hout[cs];
+    // written by k_match in place
+    match_copy_out(reinterpret_cast<const int32_t*>(c->pin + o_res), n, cs, match_out, nmatches);
     return COEB_OK;
 }
 
@@ -1332,14 +1103,12 @@ int coeb_match_localmap(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe
     int rc;
     uint8_t* dbase;
     SingleFrameBufs& sf = c->sf;
-    if ((rc = ensure(c, sf.l_out, (size_t)cs + 1)) || (rc = ensure(c, sf.l_list, (size_t)qs * kCQ)) ||
-        (rc = ensure(c, c->ex.err, 4)) || (rc = ensure(c, sf.l_path, 2)))
-        return rc;
+    if ((rc = projection_bufs(c, cs, qs))) return rc;
     int32_t* dout = sf.l_out.p;
     hipStream_t s = main_stream(c);
     Pack pk;
     const size_t o_k = pk.add(cur->keys_un, (size_t)n * sizeof(coeb_keypoint)), o_d = pk.add(cur->descriptors, (size_t)n * 32);
-    const size_t o_ur = pk.add(cur->u_right, (size_t)n * 4);
+    const size_t o_ur =pk.add(cur->u_right, (size_t)n * 4);
     const size_t o_co = cur_obs ? pk.add(cur_obs, (size_t)n * 4) : pk.fill(0xff, (size_t)n * 4);   // -1: all NULL
     const size_t o_v = pk.add(mp->in_view, (size_t)nq), o_px = pk.add(mp->proj_x, (size_t)nq * 4);
     const size_t o_py = pk.add(mp->proj_y, (size_t)nq * 4), o_pxr = pk.add(mp->proj_xr, (size_t)nq * 4);
@@ -1356,13 +1125,7 @@ int coeb_match_localmap(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe
     rc = launch_match_local(make_cam(c, cam), b, th, nnratio, s, &c->hook);
     if (rc == -2) return set_err(c, COEB_ERANGE, "coeb_match_localmap: frame and local map exceed the LDS budget");
     if (rc) return hip_err(c, hipGetLastError(), "launch_match_local");
-    int32_t* hout = reinterpret_cast<int32_t*>(c->pin);          // one copy back: match[cs], nmatch
-    HIP_TRY(c, hipMemcpyAsync(hout, dout, ((size_t)cs + 1) * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if ((rc = check_err_word(c))) return rc;
-    if (n && match_out) memcpy(match_out, hout, (size_t)n * 4);
-    *nmatches = hout[cs];
-    return COEB_OK;
+    return projection_finish(c, s, n, cs, match_out, nmatches);
 }
 
 int coeb_match_keyframe(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe* cur, const uint8_t* cur_has,
@@ -1382,14 +1145,12 @@ int coeb_match_keyframe(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe
     int rc;
     uint8_t* dbase;
     SingleFrameBufs& sf = c->sf;
-    if ((rc = ensure(c, sf.l_out, (size_t)cs + 1)) || (rc = ensure(c, sf.l_list, (size_t)qs * kCQ)) ||
-        (rc = ensure(c, c->ex.err, 4)) || (rc = ensure(c, sf.l_path, 2)))
-        return rc;
+    if ((rc = projection_bufs(c, cs, qs))) return rc;
     int32_t* dout = sf.l_out.p;
     hipStream_t s = main_stream(c);
     Pack pk;
     const size_t o_k = pk.add(cur->keys_un, (size_t)n * sizeof(coeb_keypoint)), o_d = pk.add(cur->descriptors, (size_t)n * 32);
-    const size_t o_h = cur_has ? pk.add(cur_has, (size_t)n) : pk.fill(0, (size_t)n);
+    const size_t o_h =cur_has ? pk.add(cur_has, (size_t)n) : pk.fill(0, (size_t)n);
     const size_t o_v = pk.add(kf->valid, (size_t)nq), o_x = pk.add(kf->world_pos, (size_t)nq * 12);
     const size_t o_qd = pk.add(kf->descriptor, (size_t)nq * 32), o_mx = pk.add(kf->max_distance, (size_t)nq * 4);
     const size_t o_mn = pk.add(kf->min_distance, (size_t)nq * 4), o_a = pk.add(kf->angle, (size_t)nq * 4);
@@ -1404,13 +1165,7 @@ int coeb_match_keyframe(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe
     rc = launch_match_kf(make_cam(c, cam), b, th, orb_dist, check_ori ? 1 : 0, s, &c->hook);
     if (rc == -2) return set_err(c, COEB_ERANGE, "coeb_match_keyframe: frame and keyframe exceed the LDS budget");
     if (rc) return hip_err(c, hipGetLastError(), "launch_match_kf");
-    int32_t* hout = reinterpret_cast<int32_t*>(c->pin);          // one copy back: match[cs], nmatch
-    HIP_TRY(c, hipMemcpyAsync(hout, dout, ((size_t)cs + 1) * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if ((rc = check_err_word(c))) return rc;
-    if (n && match_out) memcpy(match_out, hout, (size_t)n * 4);
-    *nmatches = hout[cs];
-    return COEB_OK;
+    return projection_finish(c, s, n, cs, match_out, nmatches);
 }
 
 int coeb_pose_optimization(coeb_ctx* c, const coeb_camera* cam, const coeb_pose_frame* fr, float Tcw[16],

@@ -1,5 +1,6 @@
 // coeb_ctx.hpp -- the context behind the C-ABI's coeb_ctx handle and the host helpers every
-// .hip file's entry points share (defined in coeb_capi.hip).  Host code only.
+// .hip file's entry points share (defined in coeb_capi.hip).  The plan the context caches per
+// image size is built by coeb_plan.cpp.  Host code only.
 #pragma once
 #include <algorithm>
 #include <string>
@@ -8,6 +9,7 @@
 
 #include "../../include/coeb_front.h"
 #include "coeb_internal.hpp"
+#include "coeb_plan.hpp"
 
 // One device allocation of a context, grown by ensure(); `name` is the text of its COEB_ENOMEM message.
 template <class T>
@@ -104,15 +106,6 @@ void each_buf(G& g, F f)
     static_assert(std::tuple_size<decltype(t)>::value * sizeof(DevArr<char>) == sizeof(G), "all() must list every buffer");
     std::apply([&](auto&... a) { (f(a), ...); }, t);
 }
-
-struct Tables {
-    int nfeatures;
-    double scale_factor;   // ORBextractor.h:114 `double scaleFactor`
-    int nlevels;
-    float scale[COEB_MAXL], inv_scale[COEB_MAXL], sigma2[COEB_MAXL], inv_sigma2[COEB_MAXL];
-    int nfeat[COEB_MAXL];
-    int umax[16];
-};
 
 struct ProfImpl {
     bool enabled = false;

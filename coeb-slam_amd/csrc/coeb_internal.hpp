@@ -21,6 +21,8 @@
 #include <set>
 #include <utility>
 
+#include "coeb_plan.hpp"     // LevelGeom, Plan, CellDesc: the geometry the kernels take as arguments
+
 // Runtime switches, the only environment reads of the library (coeb_capi.hip):
 //  * coeb_switch(name): a product switch -- one of kSwitches, each run by the GPU test suite
 //    against the oracle (side-stream modes, the matcher's sequential / split forms, the
@@ -69,67 +71,9 @@ __host__ __device__ inline int64_t blur_tile_off(int x, int y, int bpitch)
     return ((int64_t)(y >> 3) * (bpitch >> 4) + (x >> 4)) * 128 + (y & 7) * 16 + (x & 15);
 }
 
-#define COEB_MAXL 16
-#define COEB_MAXBOX 16
 #define COEB_GRID_COLS 64
 #define COEB_GRID_ROWS 48
 #define COEB_GRID_CELLS (COEB_GRID_COLS * COEB_GRID_ROWS)
-
-// Per-level geometry and offsets, computed on the host once per (W, H) and copied to the
-// device as one POD block (kernel argument).
-struct LevelGeom {
-    int w, h;
-    int pitch;             // row pitch of the level image (level 0: W; levels >= 1: 64-byte multiple)
-    int bpitch;            // row pitch of the blurred level (64-byte multiple)
-    int64_t pyr_off;       // into pyr frame block (-1 for level 0)
-    int64_t blur_off;      // into blur frame block
-    int rtab_off;          // into resize table (ints): xofs[w], alpha[w], yofs[h], beta[h]
-    int xmax;              // resize: columns >= xmax use S[sx]*2048
-    int rows_ok;           // k_pyr_rows applies: every even column pair's sources within 6 bytes of
-                           // the pair's 4-byte aligned window start (scale <= 2)
-    int yrow_off;          // into resize table (ints): per output row {r0 * sp, r1 * sp, beta, dy * pitch}
-                           // (the clamped source rows' byte offsets; sp = the source level's pitch)
-    int ncols, nrows, wcell, hcell;
-    int cell0, ncells;     // range in the cell table (row-major over non-skipped cells)
-    int kcap_off, kcap;    // octree key buffers: offset / capacity (u32 entries)
-    int nfeat, nfeat_area; // DistributeOctTree N: mnFeaturesPerLevel[l], (int)(N*0.7)
-    int nini;              // initial octree nodes
-    float hx;              // (maxX-minX)/nIni
-    int ini_bound[5];      // initial node i holds x_rel in [ini_bound[i], ini_bound[i+1])
-    int ncap;              // node record capacity per set
-    int64_t node_off;      // into node scratch (records) per frame
-    int out_cap, out_off;  // level keypoint capacity / offset into lvl_kp frame block
-    float scale;           // mvScaleFactor[l]
-    int size_i;            // (int)(PATCH_SIZE * scale)
-    int maxX, maxY;        // octree box: maxBorderX - minBorderX, maxBorderY - minBorderY
-};
-
-struct Plan {
-    int W, H, L;
-    LevelGeom lv[COEB_MAXL];
-    int ncells;            // all levels
-    int cell_cap;          // u32 entries per cell slot
-    int max_roi_w, max_roi_h;
-    int64_t pyr_stride, blur_stride;
-    int64_t kbuf_stride;   // u32 entries per key buffer (x2 per frame)
-    int64_t node_stride;   // node records per frame (all levels, both sets)
-    int lvl_stride;        // u32 entries per frame in lvl_kp
-    int kcap;              // output keypoints per frame (sum of out_cap)
-    int rtab_ints;
-    int umax[16];
-    int gauss[7];
-    int oct_w;             // k_octree: node records per set / work-list entries (max ncap)
-    int oct_kl;            // k_octree: keys kept in LDS when a level has <= oct_kl candidates
-    int oct_lds;           // k_octree dynamic LDS bytes
-};
-
-// FAST cell descriptor (ORBextractor.cc:811-829): ROI in level coordinates
-struct CellDesc {
-    int16_t level, pad;
-    int16_t x0, y0;        // iniX, iniY
-    int16_t rw, rh;        // maxX-iniX, maxY-iniY (ROI; detection window = inset 3)
-    int16_t i, j;          // cell row / column (for x_rel/y_rel offsets)
-};
 
 // Dynamic-object mask of one frame (ORBextractor.cc:1101-1195): the mask is the complement of
 // the union of these rectangles (x in [x0,x1), y in [y0,y1)), so the W x H byte mask never

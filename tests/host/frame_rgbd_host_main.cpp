@@ -1,11 +1,11 @@
-// The host part of coeb_frame_rgbd (coeb-slam_amd/csrc/coeb_frame_rgbd_host.hpp: argument check,
-// page-locked buffer layout, row staging) run without a device, built with ASan + UBSan by
-// tests/test_frame_rgbd_host.py.  Exit status 0 and "ok" on stdout: every check held.
+// The host part of coeb_extract and coeb_frame_rgbd (coeb-slam_amd/csrc/coeb_single_frame_host.hpp:
+// argument checks, page-locked buffer layout, row staging) run without a device, built with
+// ASan + UBSan by tests/test_frame_rgbd_host.py.  Exit status 0 and "ok" on stdout: every check held.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
-#include "coeb_frame_rgbd_host.hpp"
+#include "coeb_single_frame_host.hpp"
 
 static int g_fail = 0;
 #define CHECK(cond)                                                      \
@@ -39,11 +39,16 @@ static void check_layout(int W, int H, int kcap, int nbox, int ntm, int dtype)
     CHECK(L.o_k % 16 == 0 && L.o_d % 16 == 0);                       // k_frame_tail's uint4 descriptor stores
     CHECK(L.o_kun % 256 == 0 && L.o_depth % 256 == 0);
     CHECK(L.depth_row == (size_t)W * db);
-    // coeb_extract's own offsets for the same frame (coeb_capi.hip): its regions are where it left them
-    const size_t img = ((size_t)W * H + 255) & ~(size_t)255;
-    CHECK(L.o_n == img && L.o_k == img + 256);
-    CHECK(L.o_d == L.o_k + ((k * 28 + 255) & ~(size_t)255));
-    CHECK(L.o_dyn == L.o_d + ((k * 32 + 255) & ~(size_t)255));
+    // coeb_extract's layout for the same frame: a prefix of this one whatever the depth type, so
+    // either call finds the shared regions where the other left them, and coeb_extract's buffer
+    // ends with its T_M points
+    const SingleFrameLayout S = single_frame_layout(W, H, kcap, nbox, ntm);
+    const FrameRgbdLayout O = frame_rgbd_layout(W, H, kcap, nbox, ntm, dtype == COEB_DEPTH_F32 ? COEB_DEPTH_U16 : COEB_DEPTH_F32);
+    for (const SingleFrameLayout& q : {SingleFrameLayout(L), SingleFrameLayout(O)}) {
+        CHECK(q.o_n == S.o_n && q.o_k == S.o_k && q.o_d == S.o_d && q.o_dyn == S.o_dyn);
+        CHECK(q.o_bo == S.o_bo && q.o_bl == S.o_bl && q.o_to == S.o_to && q.o_tm == S.o_tm);
+    }
+    CHECK(S.total == S.o_tm + (size_t)ntm * 8 && S.total <= L.o_kun);
     // the staging writes of the call, on a buffer of exactly `total` bytes (ASan sees an overrun):
     // strided sources whose padding must not arrive
     std::vector<uint8_t> pin(L.total, 0xEE);
@@ -53,8 +58,8 @@ static void check_layout(int W, int H, int kcap, int nbox, int ntm, int dtype)
         for (int x = 0; x < W; x++) gray[y * gs + x] = (uint8_t)(x + 3 * y);
         for (size_t b = 0; b < L.depth_row; b++) dep[y * ds + b] = (uint8_t)(b + 5 * y);
     }
-    frame_rgbd_stage_rows(pin.data(), gray.data(), H, (size_t)W, gs);
-    frame_rgbd_stage_rows(pin.data() + L.o_depth, dep.data(), H, L.depth_row, ds);
+    single_frame_stage_rows(pin.data(), gray.data(), H, (size_t)W, gs);
+    single_frame_stage_rows(pin.data() + L.o_depth, dep.data(), H, L.depth_row, ds);
     bool ok = true;
     for (int y = 0; y < H && ok; y++) {
         for (int x = 0; x < W; x++) ok = ok && pin[(size_t)y * W + x] == (uint8_t)(x + 3 * y);
@@ -66,7 +71,7 @@ static void check_layout(int W, int H, int kcap, int nbox, int ntm, int dtype)
     CHECK(ok);
     // packed sources take the one-memcpy branch
     std::vector<uint8_t> pin2(L.total, 0xEE), g2((size_t)W * H, 7);
-    frame_rgbd_stage_rows(pin2.data(), g2.data(), H, (size_t)W, (size_t)W);
+    single_frame_stage_rows(pin2.data(), g2.data(), H, (size_t)W, (size_t)W);
     CHECK(pin2[0] == 7 && pin2[(size_t)W * H - 1] == 7 && (L.o_n == (size_t)W * H || pin2[(size_t)W * H] == 0xEE));
 }
 

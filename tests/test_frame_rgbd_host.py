@@ -1,5 +1,5 @@
 """coeb_frame_rgbd without a GPU: the host part of the entry point (argument check, page-locked
-buffer layout, row staging: csrc/coeb_frame_rgbd_host.hpp) as a stand-alone program under
+buffer layout, row staging: csrc/coeb_single_frame_host.hpp) as a stand-alone program under
 ASan + UBSan, the C++ adapter (ORBextractor::ExtractRGBD, coeb::FrameRGBD) as a compile check
 against the OpenCV stand-in, and the Python mirror's declaration of the entry point."""
 import ctypes

@@ -166,6 +166,58 @@ def test_extract_small_cap(ctx, frame31, short):
     expect_exact(rc, n, kps, desc, ref, "after ERANGE")
 
 
+def test_frame_rgbd_and_extract_alternate_on_one_context(frame31):
+    """coeb_frame_rgbd and coeb_extract share the page-locked buffer's layout and the enqueue of the
+    frame: alternated on one context (with and without boxes / T_M, the one-array second round
+    trip, a short cap), each call returns what a fresh context returns for it."""
+    W, H = 640, 480
+    fr_a, fr_b = synth.make_frames(W, H, 2, seed=77)
+    fr_c, ref_c = frame31
+    depth = synth.make_depth(W, H)
+    cam = cf.make_camera(synth.TUM_FX, synth.TUM_FY, synth.TUM_CX, synth.TUM_CY, synth.TUM_BF, W, H)
+    dyn = synth.dynamic_inputs(W, H)
+    cap = len(ref_c["kps"]) // 2
+
+    def rgbd(c):
+        return c.frame_rgbd(fr_a, depth, cam, dist=(0.2624, -0.9531, -0.0054, 0.0026, 1.1633), boxes=dyn[0], tm=dyn[1],
+                            blur=dyn[2])
+
+    calls = [rgbd,
+             lambda c: raw_extract(c, fr_b, W, want_kps=False),          # desc_out only: fetched by the second copy
+             lambda c: raw_extract(c, fr_c, W, dyn, cap=cap),            # COEB_ERANGE, the first cap records
+             rgbd]
+    want = []
+    for call in calls[:3]:
+        c = cf.Context(max_width=W, max_height=H, max_batch=1)
+        try:
+            want.append(call(c))
+        finally:
+            c.close()
+    want.append(want[0])
+    c = cf.Context(max_width=W, max_height=H, max_batch=1)
+    try:
+        got = [call(c) for call in calls]
+    finally:
+        c.close()
+    for i in (0, 3):
+        assert len(got[i]["kps"]) > 100
+        for name in ("kps", "kps_un", "desc", "u_right", "depth"):
+            a, b = got[i][name], want[i][name]
+            if name.startswith("kps"):
+                a, b = kp_bytes(a), kp_bytes(b)
+            same_bits(a, b, "call %d %s" % (i, name))
+    for i in (1, 2):
+        (rc, n, kps, desc), (rc_w, n_w, kps_w, desc_w) = got[i], want[i]
+        assert (rc, n) == (rc_w, n_w), (i, rc, n, rc_w, n_w)
+        assert np.array_equal(kp_bytes(kps), kp_bytes(kps_w)) and np.array_equal(desc, desc_w), i
+    rc, n, kps, desc = got[1]
+    assert rc == COEB_OK and n > 100 and (kp_bytes(kps) == SENTINEL).all() and (desc[:n] != SENTINEL).any()
+    assert (desc[n:] == SENTINEL).all()
+    rc, n, kps, desc = got[2]
+    assert rc == COEB_ERANGE and n > cap and untouched(kps, desc, cap)
+    assert (kp_bytes(kps[:cap]) != SENTINEL).any() and (desc[:cap] != SENTINEL).any()
+
+
 # ------------------------------------------------------------------ 3. coeb_stereo_from_rgbd
 def raw_stereo(ctx, kps, n, depth_view, w, h, dstride):
     ur = np.full(max(n, 1), np.float32(7.5))
