@@ -1,5 +1,5 @@
 /*
- * ORBmatcher_coeb.h -- MI355X bodies for two ORBmatcher::SearchByProjection overloads:
+ * ORBmatcher_coeb.h -- MI355X bodies for the ORBmatcher::SearchByProjection overloads and SearchByBoW:
  *   (Frame&, const Frame&, float th, bool bMono)  include/ORBmatcher.h:52, src/ORBmatcher.cc:1329-1471
  *   (Frame&, const vector<MapPoint*>&, float th)  include/ORBmatcher.h:46, src/ORBmatcher.cc:44-129
  *   (Frame&, KeyFrame*, const set<MapPoint*>&, float th, int ORBdist)
@@ -42,6 +42,16 @@
  * pKF->mvKeysUn[i].angle) and which keypoints of CurrentFrame already hold a MapPoint.
  * MapPoint::PredictScale reads the protected mfMaxDistance, so the integration adds two locked
  * getters to MapPoint (GetMaxDistance / GetMinDistance).
+ *
+ * SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&) (include/ORBmatcher.h:65,
+ * src/ORBmatcher.cc:159-288) becomes
+ *
+ *     return coeb::SearchByBoW(pKF, F, vpMapPointMatches, mfNNratio, mbCheckOrientation);
+ *
+ * It snapshots pKF->GetMapPointMatches() (valid = pMP && !isBad()), turns pKF->mFeatVec and
+ * F.mFeatVec (node id -> feature indices, filled by ComputeBoW) into a node id per feature, and
+ * reads pKF->mDescriptors, pKF->mvKeysUn[i].angle, F.mDescriptors and F.mvKeys[i].angle;
+ * vpMapPointMatches is resized to F.N and gets vpMapPointsKF[match[i]].
  *
  * All use a matcher context built with the frame's own pyramid (F.mnScaleLevels,
  * F.mfScaleFactor), so mvScaleFactors on the device are the frame's.
@@ -207,6 +217,47 @@ inline int SearchByProjectionKeyFrame(FrameT& CurrentFrame, KeyFrameT* pKF, cons
     if (rc != COEB_OK) throw std::runtime_error(coeb_last_error(ctx));
     for (int i = 0; i < CurrentFrame.N; ++i)
         if (match[i] >= 0) CurrentFrame.mvpMapPoints[i] = vpMPs[match[i]];
+    return nmatches;
+}
+
+// node id per feature from a FeatureVector (an ordered map NodeId -> vector<unsigned int>)
+template <class FeatureVectorT>
+inline std::vector<int32_t> feature_nodes(const FeatureVectorT& fv, int n)
+{
+    std::vector<int32_t> node((size_t)n, -1);
+    for (typename FeatureVectorT::const_iterator it = fv.begin(); it != fv.end(); ++it)
+        for (size_t j = 0; j < it->second.size(); ++j)
+            if ((int)it->second[j] < n) node[it->second[j]] = (int32_t)it->first;
+    return node;
+}
+
+template <class KeyFrameT, class FrameT, class MapPointT>
+inline int SearchByBoW(KeyFrameT* pKF, FrameT& F, std::vector<MapPointT*>& vpMapPointMatches, float mfNNratio,
+                       bool mbCheckOrientation, coeb_ctx* ctx = nullptr)
+{
+    if (!ctx) ctx = matcher_ctx(F.mnScaleLevels, F.mfScaleFactor);
+    const std::vector<MapPointT*> vpMapPointsKF = pKF->GetMapPointMatches();
+    vpMapPointMatches = std::vector<MapPointT*>(F.N, static_cast<MapPointT*>(nullptr));
+    const int nq = (int)vpMapPointsKF.size();
+    std::vector<uint8_t> valid(nq);
+    std::vector<float> kang(nq), fang((size_t)F.N);
+    for (int i = 0; i < nq; ++i) {
+        MapPointT* pMP = vpMapPointsKF[i];
+        valid[i] = pMP && !pMP->isBad();
+        kang[i] = pKF->mvKeysUn[i].angle;
+    }
+    for (int i = 0; i < F.N; ++i) fang[i] = F.mvKeys[i].angle;
+    const std::vector<int32_t> knode = feature_nodes(pKF->mFeatVec, nq), fnode = feature_nodes(F.mFeatVec, F.N);
+    cv::Mat kfDesc = pKF->mDescriptors.isContinuous() ? pKF->mDescriptors : pKF->mDescriptors.clone();
+    cv::Mat curDesc = F.mDescriptors.isContinuous() ? F.mDescriptors : F.mDescriptors.clone();
+    coeb_bow_keyframe kf{nq, valid.data(), kfDesc.empty() ? nullptr : kfDesc.ptr<uint8_t>(0), knode.data(), kang.data()};
+    coeb_bow_frame cur{F.N, curDesc.empty() ? nullptr : curDesc.ptr<uint8_t>(0), fnode.data(), fang.data()};
+    std::vector<int32_t> match((size_t)F.N);
+    int nmatches = 0;
+    const int rc = coeb_match_bow(ctx, &kf, &cur, mfNNratio, mbCheckOrientation ? 1 : 0, match.data(), &nmatches);
+    if (rc != COEB_OK) throw std::runtime_error(coeb_last_error(ctx));
+    for (int i = 0; i < F.N; ++i)
+        if (match[i] >= 0) vpMapPointMatches[i] = vpMapPointsKF[match[i]];
     return nmatches;
 }
 

@@ -14,6 +14,11 @@
   ORBmatcher(nnratio, checkOri).SearchByProjection(F, KeyFramePoints, sAlreadyFound, th, ORBdist)
       include/ORBmatcher.h:55, src/ORBmatcher.cc:1473-1600 (Tracking::Relocalization,
       src/Tracking.cc:1531,1545); assigns F.mvpMapPoints[i] = KeyFrame point index.
+  ORBmatcher(0.7, True).SearchByBoW(pKF: BowKeyFrame, F)
+      include/ORBmatcher.h:65, src/ORBmatcher.cc:159-288 (Tracking::TrackReferenceKeyFrame,
+      src/Tracking.cc:833, and Relocalization, :1456); F.ComputeBoW(ctx) first (src/Frame.cc:570-577);
+      assigns F.mvpMapPoints[i] = KeyFrame feature index and returns nmatches.
+  Vocabulary.from_text(text) / from_arrays(...)  ORBVocabulary::loadFromTextFile (src/System.cc:72)
   ORBmatcher.DescriptorDistance(a, b)  src/ORBmatcher.cc:1648-1664
   Optimizer.PoseOptimization(F, camera)  include/Optimizer.h:47, src/Optimizer.cc:239-451; reads
       F.mvpMapPoints (>= 0: has a MapPoint) and F.mvMapPointPos, sets F.mTcw and F.mvbOutlier.
@@ -58,6 +63,9 @@ ABI_SYMBOLS = [
     "coeb_marker_create", "coeb_marker_destroy", "coeb_marker_record_ctx", "coeb_marker_record_copyq",
     "coeb_ctx_wait_marker", "coeb_copyq_wait_marker", "coeb_marker_synchronize",
     "coeb_tum_read_list", "coeb_tum_associate", "coeb_frame_rgbd",
+    "coeb_voc_from_text", "coeb_voc_from_arrays", "coeb_voc_info", "coeb_voc_tables", "coeb_voc_destroy",
+    "coeb_bow_set_vocabulary", "coeb_bow_transform", "coeb_bow_batch_device", "coeb_batch_bow_results",
+    "coeb_match_bow",
 ]
 # COEB_ABI_VERSION of the include/coeb_front.h these argtypes are written against; lib() refuses
 # a library that reports another (tests/test_capi_symbols.py keeps the two equal)
@@ -104,6 +112,15 @@ class KeyFramePointsC(C.Structure):
 class PoseFrameC(C.Structure):
     _fields_ = [("n", C.c_int32), ("has_mappoint", C.c_void_p), ("world_pos", C.c_void_p), ("keys_un", C.c_void_p),
                 ("u_right", C.c_void_p)]
+
+
+class BowKeyFrameC(C.Structure):
+    _fields_ = [("n", C.c_int32), ("valid", C.c_void_p), ("descriptor", C.c_void_p), ("node_id", C.c_void_p),
+                ("angle", C.c_void_p)]
+
+
+class BowFrameC(C.Structure):
+    _fields_ = [("n", C.c_int32), ("descriptor", C.c_void_p), ("node_id", C.c_void_p), ("angle", C.c_void_p)]
 
 
 class CoebError(RuntimeError):
@@ -198,6 +215,20 @@ def lib():
                                          C.POINTER(C.c_int)]
         L.coeb_tum_associate.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double,
                                          C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.coeb_voc_from_text.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]
+        L.coeb_voc_from_arrays.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(C.c_void_p)]
+        L.coeb_voc_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4
+        L.coeb_voc_tables.argtypes = [C.c_void_p] * 9
+        L.coeb_voc_destroy.restype = None
+        L.coeb_voc_destroy.argtypes = [C.c_void_p]
+        L.coeb_bow_set_vocabulary.argtypes = [C.c_void_p, C.c_void_p]
+        L.coeb_bow_transform.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.coeb_bow_batch_device.argtypes = [C.c_void_p, C.c_int]
+        L.coeb_batch_bow_results.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        L.coeb_match_bow.argtypes = [C.c_void_p, C.POINTER(BowKeyFrameC), C.POINTER(BowFrameC), C.c_float, C.c_int,
+                                     C.c_void_p, C.POINTER(C.c_int)]
         L.coeb_profile_enable.argtypes = [C.c_void_p, C.c_int]
         L.coeb_profile_reset.argtypes = [C.c_void_p]
         L.coeb_profile_read.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
@@ -235,6 +266,68 @@ def lib():
 
 def _p(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+class Vocabulary:
+    """ORBVocabulary as plain data (host only, no device needed): a k-ary tree of 32-byte
+    descriptors with a weight per word.  Parity against DBoW2 itself is unpinned."""
+
+    def __init__(self, handle):
+        self.h = C.c_void_p(handle)
+
+    @classmethod
+    def from_text(cls, text):
+        """ORBvoc.txt's text (bytes or str); raises CoebError (COEB_EINVAL) on a malformed file."""
+        if isinstance(text, str):
+            text = text.encode()
+        h = C.c_void_p()
+        rc = lib().coeb_voc_from_text(text, len(text), C.byref(h))
+        if rc:
+            raise CoebError("coeb_voc_from_text rc=%d" % rc)
+        return cls(h.value)
+
+    @classmethod
+    def from_arrays(cls, k, L, parent, is_leaf, desc, weight):
+        """Node i + 1 = (parent[i], is_leaf[i], desc[i], weight[i]); node 0 is the root."""
+        parent = np.ascontiguousarray(parent, np.int32)
+        n = len(parent)
+        is_leaf = np.ascontiguousarray(is_leaf, np.uint8)
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(n, 32)
+        weight = np.ascontiguousarray(weight, np.float64)
+        if len(is_leaf) != n or len(weight) != n:
+            raise ValueError("Vocabulary arrays differ in length")
+        h = C.c_void_p()
+        rc = lib().coeb_voc_from_arrays(k, L, n, _p(parent), _p(is_leaf), _p(desc), _p(weight), C.byref(h))
+        if rc:
+            raise CoebError("coeb_voc_from_arrays rc=%d" % rc)
+        return cls(h.value)
+
+    def info(self):
+        """(k, L, nodes with the root, words)"""
+        v = [C.c_int() for _ in range(4)]
+        lib().coeb_voc_info(self.h, *[C.byref(x) for x in v])
+        return tuple(x.value for x in v)
+
+    def tables(self):
+        """The tables the device walks, by slot (include/coeb_front.h, coeb_voc_tables)."""
+        _, _, nn, nw = self.info()
+        t = dict(child_first=np.empty(nn, np.int32), child_count=np.empty(nn, np.int32), word=np.empty(nn, np.int32),
+                 node_id=np.empty(nn, np.int32), positive=np.empty(nn, np.uint8), desc=np.empty((nn, 32), np.uint8),
+                 word_weight=np.empty(nw, np.float64), word_node=np.empty(nw, np.int32))
+        lib().coeb_voc_tables(self.h, *[_p(t[k]) for k in ("child_first", "child_count", "word", "node_id", "positive",
+                                                            "desc", "word_weight", "word_node")])
+        return t
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().coeb_voc_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Context:
@@ -340,6 +433,36 @@ class Context:
                                          _p(desc), _p(ur), _p(dep), cap, C.byref(n)))
         n = n.value
         return dict(kps=kps[:n], kps_un=kun[:n], desc=(desc[:n] if n else None), u_right=ur[:n], depth=dep[:n])
+
+    # ---- bag of words ----
+    def set_vocabulary(self, voc):
+        self.check(lib().coeb_bow_set_vocabulary(self.h, voc.h))
+
+    def bow_transform(self, desc, levelsup=4):
+        """Frame::ComputeBoW (Frame.cc:570-577) for n x 32 descriptors: dict(word, node, weight,
+        fv_node, fv_off, fv_idx) -- word ids, FeatureVector node ids (-1: word weight not > 0),
+        word weights, and the FeatureVector as a CSR (node ids ascending, indices ascending)."""
+        desc = np.zeros((0, 32), np.uint8) if desc is None else np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        n = len(desc)
+        m = max(n, 1)
+        word, node, weight = np.empty(m, np.int32), np.empty(m, np.int32), np.empty(m, np.float64)
+        fv_node, fv_off, fv_idx = np.empty(m, np.int32), np.empty(m + 1, np.int32), np.empty(m, np.int32)
+        nfv = C.c_int()
+        self.check(lib().coeb_bow_transform(self.h, _p(desc) if n else None, n, levelsup, _p(word), _p(node),
+                                            _p(weight), _p(fv_node), _p(fv_off), _p(fv_idx), m, C.byref(nfv)))
+        nd = nfv.value
+        return dict(word=word[:n], node=node[:n], weight=weight[:n], fv_node=fv_node[:nd], fv_off=fv_off[:nd + 1],
+                    fv_idx=fv_idx[:int(fv_off[nd])])
+
+    def bow_batch_device(self, levelsup=4):
+        """The transform over the last extracted batch; results: batch_bow_results()."""
+        self.check(lib().coeb_bow_batch_device(self.h, levelsup))
+
+    def batch_bow_results(self):
+        """Device pointers (word ids, node ids), each [nframes][kcap] int32."""
+        w, nd = C.c_void_p(), C.c_void_p()
+        self.check(lib().coeb_batch_bow_results(self.h, C.byref(w), C.byref(nd)))
+        return w.value, nd.value
 
     # ---- device-resident batch ----
     def extract_batch_device(self, d_gray_ptr, nframes, w, h, boxes=None, box_off=None, tm=None, tm_off=None,
@@ -690,6 +813,14 @@ class Frame:
 
     # the fields below are allocated on first use (a per-frame cost of the Python binding the
     # drop-in latency in bench.py includes; the C++ Tracking thread owns them already)
+    def ComputeBoW(self, ctx, levelsup=4):
+        """Frame::ComputeBoW (Frame.cc:570-577) with the context's vocabulary: mBowWord / mBowWeight
+        per feature (mBowVec's entries before the caller's normalisation), mFeatNode (the
+        FeatureVector node of each feature, -1: none) and mFeatVec as (node ids, offsets, indices)."""
+        r = ctx.bow_transform(self.mDescriptors, levelsup)
+        self.mBowWord, self.mBowWeight, self.mFeatNode = r["word"], r["weight"], r["node"]
+        self.mFeatVec = (r["fv_node"], r["fv_off"], r["fv_idx"])
+
     @property
     def mvbOutlier(self):
         if self._outlier is None:
@@ -769,8 +900,24 @@ class KeyFramePoints:
                 raise ValueError("KeyFramePoints arrays differ in length")
 
 
+class BowKeyFrame:
+    """The KeyFrame fields SearchByBoW reads (ORBmatcher.cc:161-199, 234): per feature i, valid
+    (GetMapPointMatches()[i] && !isBad()), mDescriptors.row(i), the mFeatVec node that lists it
+    (-1: none) and mvKeysUn[i].angle."""
+
+    def __init__(self, valid, descriptor, node_id, angle):
+        self.valid = np.ascontiguousarray(valid, np.uint8)
+        self.N = len(self.valid)
+        self.descriptor = np.ascontiguousarray(descriptor, np.uint8).reshape(self.N, 32) if self.N else \
+            np.zeros((0, 32), np.uint8)
+        self.node_id = np.ascontiguousarray(node_id, np.int32)
+        self.angle = np.ascontiguousarray(angle, np.float32)
+        if len(self.node_id) != self.N or len(self.angle) != self.N:
+            raise ValueError("BowKeyFrame arrays differ in length")
+
+
 class ORBmatcher:
-    """Mirror of ORB_SLAM2::ORBmatcher for the tracking projection search."""
+    """Mirror of ORB_SLAM2::ORBmatcher for the tracking searches."""
     TH_HIGH = 100
     TH_LOW = 50
     HISTO_LENGTH = 30
@@ -798,6 +945,24 @@ class ORBmatcher:
         if isinstance(second, KeyFramePoints):
             return self._search_keyframe(CurrentFrame, second, *args, **kw)
         return self._search_last_frame(CurrentFrame, second, *args, **kw)
+
+    def SearchByBoW(self, pKF, F):
+        """SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) (ORBmatcher.cc:159-288): pKF a
+        BowKeyFrame, F a Frame after ComputeBoW.  F.mvpMapPoints[i] = the KeyFrame feature whose
+        MapPoint keypoint i takes, or -1; returns nmatches."""
+        if self.ctx is None:
+            self.ctx = Context()
+        node = np.ascontiguousarray(F.mFeatNode, np.int32)
+        angle = np.ascontiguousarray(F.mvKeysUn["angle"], np.float32)      # mvKeys[i].angle: undistortion keeps it
+        kc = BowKeyFrameC(pKF.N, *[C.c_void_p(a.ctypes.data) for a in (pKF.valid, pKF.descriptor, pKF.node_id,
+                                                                      pKF.angle)])
+        fc = BowFrameC(F.N, *[C.c_void_p(a.ctypes.data) for a in (F.mDescriptors, node, angle)])
+        out = np.empty(max(F.N, 1), np.int32)
+        nm = C.c_int()
+        self.ctx.check(lib().coeb_match_bow(self.ctx.h, C.byref(kc), C.byref(fc), self.mfNNratio,
+                                            int(self.mbCheckOrientation), _p(out), C.byref(nm)))
+        F.mvpMapPoints = out[:F.N]
+        return nm.value
 
     def _search_last_frame(self, CurrentFrame, LastFrame, th, bMono, camera):
         mp = LastFrame.map_points

@@ -149,22 +149,7 @@ __global__ __launch_bounds__(256) void k_frame_tail(FrameTail a)
     out_pack_copy(a.kps, a.desc, n, t, T, a.out_k, a.out_d);
 }
 
-// Inputs of one call packed at 16-byte aligned offsets of the pinned staging buffer, moved to
-// the device in one copy; fill() parts are constant bytes (absent optional arrays).
-struct Pack {
-    struct Part { const void* p; size_t n; int fill; };
-    std::vector<Part> parts;
-    size_t total = 0;
-    size_t add(const void* p, size_t n) { return put(Part{p, n, -1}); }
-    size_t fill(int byte, size_t n) { return put(Part{nullptr, n, byte}); }
-    size_t put(Part q)
-    {
-        const size_t off = total;
-        parts.push_back(q);
-        total = (total + q.n + 15) & ~(size_t)15;
-        return off;
-    }
-};
+}  // namespace
 
 int pinned(coeb_ctx* c, size_t bytes)
 {
@@ -206,6 +191,8 @@ int stage_in(coeb_ctx* c, const Pack& pk, uint8_t** dbase, hipStream_t s)
     HIP_TRY(c, hipMemcpyAsync(*dbase, c->pin, total, hipMemcpyHostToDevice, s));
     return 0;
 }
+
+namespace {
 
 int ensure_plan(coeb_ctx* c, int W, int H)
 {
@@ -712,6 +699,7 @@ void coeb_destroy(coeb_ctx* c)
     each_buf(c->pl, free_buf); each_buf(c->ex, free_buf); each_buf(c->fb, free_buf);
     each_buf(c->bm, free_buf); each_buf(c->bp, free_buf); each_buf(c->tl, free_buf);
     each_buf(c->sf, free_buf); each_buf(c->tim, free_buf); each_buf(c->hl, free_buf);
+    each_buf(c->bow, free_buf);
     c->prof.drain();
     for (auto e : c->prof.pool) (void)hipEventDestroy(e);
     for (size_t k = 0; k < c->subs.size(); k++) {

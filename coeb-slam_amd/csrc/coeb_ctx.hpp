@@ -10,6 +10,7 @@
 #include "../../include/coeb_front.h"
 #include "coeb_internal.hpp"
 #include "coeb_plan.hpp"
+#include "coeb_voc.hpp"
 
 // One device allocation of a context, grown by ensure(); `name` is the text of its COEB_ENOMEM message.
 template <class T>
@@ -98,6 +99,12 @@ struct HelperBufs {         // scratch of coeb_flow.hip (flow) and of coeb_frame
     DevArr<coeb_keypoint> ud_in{"ud_in"}, ud_out{"ud_out"};
     auto all() { return std::tie(flow, bf_img, pp_img, pp_gray, pp_dsrc, bf_box, pp_dep, bf_out, ud_in, ud_out); }
 };
+struct BowBufs {            // coeb_bow.hip: the vocabulary tables (v_*) and the scratch of its entry points
+    DevArr<VocRec> v_rec{"v_rec"};
+    DevArr<uint8_t> v_desc{"v_desc"};
+    DevArr<int32_t> w_out{"w_out"}, b_word{"b_word"}, b_node{"b_node"}, m_csr{"m_csr"}, m_out{"m_out"}, m_aux{"m_aux"};
+    auto all() { return std::tie(v_rec, v_desc, w_out, b_word, b_node, m_csr, m_out, m_aux); }
+};
 
 template <class G, class F>
 void each_buf(G& g, F f)
@@ -157,6 +164,11 @@ struct coeb_ctx {
     SingleFrameBufs sf;
     TimingBufs tim;
     HelperBufs hl;
+    BowBufs bow;
+    // the vocabulary of coeb_bow_set_vocabulary (k == 0: none): shape, and the word weights the
+    // single-frame transform gathers on the host
+    struct { int k = 0, L = 0, nnodes = 0; std::vector<double> word_weight; } voc;
+    int bow_frames = 0;        // frames of the last coeb_bow_batch_device
     std::string err;
     ProfImpl prof;
     ProfileHook hook;
@@ -240,6 +252,27 @@ int ensure(coeb_ctx* c, DevArr<T>& a, size_t count)
     a.bytes = bytes;
     return 0;
 }
+
+// Inputs of one call packed at 16-byte aligned offsets of the pinned staging buffer, moved to
+// the device in one copy; fill() parts are constant bytes (absent optional arrays).
+struct Pack {
+    struct Part { const void* p; size_t n; int fill; };
+    std::vector<Part> parts;
+    size_t total = 0;
+    size_t add(const void* p, size_t n) { return put(Part{p, n, -1}); }
+    size_t fill(int byte, size_t n) { return put(Part{nullptr, n, byte}); }
+    size_t put(Part q)
+    {
+        const size_t off = total;
+        parts.push_back(q);
+        total = (total + q.n + 15) & ~(size_t)15;
+        return off;
+    }
+};
+
+int pinned(coeb_ctx* c, size_t bytes);          // the page-locked buffer holds at least bytes afterwards
+// pack -> pinned -> one H2D copy into the "stage" device buffer; *dbase = its device address
+int stage_in(coeb_ctx* c, const Pack& pk, uint8_t** dbase, hipStream_t s);
 
 // coeb_flow.hip / coeb_frame.hip, called by coeb_capi.hip
 int pmo_batch(coeb_ctx* c, const uint8_t* d_gray, int F, int w, int h, float* tm_out, int* ntm_out, int tm_cap);

@@ -47,6 +47,21 @@
  *                                      (OpenCV goodFeaturesToTrack / cornerSubPix / calcOpticalFlowPyrLK /
  *                                      findFundamentalMat as called there)
  *   coeb_descriptor_distance        <- ORBmatcher::DescriptorDistance  src/ORBmatcher.cc:1648-1664
+ *   coeb_voc_from_text / _from_arrays <- ORBVocabulary::loadFromTextFile as System::System calls it
+ *                                      src/System.cc:66-76 (DBoW2's TemplatedVocabulary is not
+ *                                      vendored: the format and the transform are restated, parity
+ *                                      against DBoW2 UNPINNED)
+ *   coeb_bow_transform              <- Frame::ComputeBoW  src/Frame.cc:570-577 =
+ *                                      mpORBvocabulary->transform(vCurrentDesc, mBowVec, mFeatVec, 4),
+ *                                      per feature TemplatedVocabulary::transform(feature, word,
+ *                                      weight, &nid, levelsup); the calls in
+ *                                      Tracking::TrackReferenceKeyFrame  src/Tracking.cc:826 and
+ *                                      Tracking::Relocalization  src/Tracking.cc:1420
+ *   coeb_bow_batch_device           <- the same, over the last extracted device batch
+ *   coeb_match_bow                  <- ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&)
+ *                                      include/ORBmatcher.h:65, src/ORBmatcher.cc:159-288; the calls
+ *                                      in TrackReferenceKeyFrame  src/Tracking.cc:833 and
+ *                                      Relocalization  src/Tracking.cc:1456
  *   coeb_tum_read_list              <- associate.py read_file_list  associate.py:49-69
  *   coeb_tum_associate              <- associate.py associate  associate.py:71-102 (host only)
  *
@@ -301,6 +316,81 @@ int coeb_match_keyframe(coeb_ctx* ctx, const coeb_camera* cam, const coeb_curfra
                         const uint8_t* cur_has_mappoint, const coeb_keyframe_points* kf,
                         const float Tcw[16], float th, int orb_dist, int check_orientation,
                         int32_t* match_out, int* nmatches);
+
+/* ---- bag of words: vocabulary, Frame::ComputeBoW, ORBmatcher::SearchByBoW ----
+ * The vocabulary is host data (no context, no device).  coeb_voc_from_text parses ORB-SLAM2's
+ * ORBvoc.txt: first line "k L scoring weighting" (k 2..20, L 1..10, scoring 0..5, weighting 0..3),
+ * then one line "parent is_leaf d0 .. d31 weight" per node; node ids are 1, 2, .. in line order
+ * (0 is the root), a line appends its node to children[parent], leaves take word ids 0, 1, .. in
+ * line order.  COEB_EINVAL (never a crash) for an empty text, a header out of range, a short or
+ * over-long line, a byte outside 0..255, a parent that is not a node already defined or is a
+ * leaf, more than k children, a node below level L, an inner node without children.
+ * coeb_voc_from_arrays takes the same lines as arrays: node i + 1 = (parent[i], is_leaf[i],
+ * desc[32 i ..], weight[i]) for i < nlines.  coeb_voc_info: nnodes counts the root.
+ * coeb_voc_tables copies the tables the device walks (any pointer may be NULL): nodes renumbered
+ * into slots, slot 0 the root, the children of a slot contiguous in their original order from
+ * child_first[slot], child_count[slot] of them (0: a leaf); word[slot] (-1: inner node),
+ * node_id[slot], positive[slot] (leaf weight > 0), desc[slot][32]; per word its weight and node id. */
+typedef struct coeb_voc coeb_voc;
+int coeb_voc_from_text(const char* text, size_t len, coeb_voc** voc);
+int coeb_voc_from_arrays(int k, int L, int nlines, const int32_t* parent, const uint8_t* is_leaf,
+                         const uint8_t* desc, const double* weight, coeb_voc** voc);
+int coeb_voc_info(const coeb_voc* voc, int* k, int* L, int* nnodes, int* nwords);
+int coeb_voc_tables(const coeb_voc* voc, int32_t* child_first, int32_t* child_count, int32_t* word,
+                    int32_t* node_id, uint8_t* positive, uint8_t* desc, double* word_weight, int32_t* word_node);
+void coeb_voc_destroy(coeb_voc* voc);
+/* Uploads the vocabulary's tables to the context's device; a second call replaces them.  The
+ * context keeps nothing of `voc` afterwards. */
+int coeb_bow_set_vocabulary(coeb_ctx* ctx, const coeb_voc* voc);
+
+/* ---- Frame::ComputeBoW on one host frame ----
+ * desc: n x 32 (n <= 4095).  Per feature i, transform(desc[i], word, weight, &nid, levelsup):
+ * from the root, the child with the smallest DescriptorDistance (the first one on a tie) until a
+ * leaf; word_out[i] = its word id, weight_out[i] = its weight, nid = the id of the node passed at
+ * level L - levelsup (0 when levelsup >= L; the leaf itself when it lies above that level, where
+ * the reference leaves nid uninitialised).  As in BowVector / FeatureVector filling (`if (w > 0)`),
+ * a feature whose word weight is not > 0 keeps its word id but has node_out[i] = -1 and is not in
+ * the feature vector; the caller skips addWeight for it.  The feature vector is a CSR: fv_node
+ * [*nfv_out] distinct node ids ascending, fv_off[*nfv_out + 1], and under node j the feature
+ * indices fv_idx[fv_off[j] .. fv_off[j+1]) ascending (fv_node, fv_off, fv_idx hold fv_cap,
+ * fv_cap + 1 and n entries; all three NULL: not wanted; more than fv_cap nodes: COEB_ERANGE with
+ * *nfv_out set).  word_out / node_out / weight_out may be NULL.  COEB_EINVAL before
+ * coeb_bow_set_vocabulary. */
+int coeb_bow_transform(coeb_ctx* ctx, const uint8_t* desc, int n, int levelsup, int32_t* word_out,
+                       int32_t* node_out, double* weight_out, int32_t* fv_node, int32_t* fv_off,
+                       int32_t* fv_idx, int fv_cap, int* nfv_out);
+/* The same transform over the descriptors of the last extracted batch ([nframes][kcap][32] with
+ * their counts); coeb_batch_bow_results -> device pointers to word ids and node ids
+ * [nframes][kcap] (-1 past a frame's count; node id -1 as above).  Enqueued on the context stream. */
+int coeb_bow_batch_device(coeb_ctx* ctx, int levelsup);
+int coeb_batch_bow_results(coeb_ctx* ctx, const int32_t** d_word, const int32_t** d_node);
+
+/* The KeyFrame fields SearchByBoW reads (ORBmatcher.cc:161-199, 234). */
+typedef struct {
+    int32_t n;                        /* pKF->N */
+    const uint8_t* valid;             /* vpMapPointsKF[i] && !isBad() */
+    const uint8_t* descriptor;        /* n x 32, pKF->mDescriptors */
+    const int32_t* node_id;           /* the mFeatVec node that lists feature i, -1: none */
+    const float* angle;               /* pKF->mvKeysUn[i].angle */
+} coeb_bow_keyframe;
+/* ... and of the Frame (:176-212, 238). */
+typedef struct {
+    int32_t n;                        /* F.N */
+    const uint8_t* descriptor;        /* n x 32, F.mDescriptors */
+    const int32_t* node_id;           /* the F.mFeatVec node that lists feature i, -1: none */
+    const float* angle;               /* F.mvKeys[i].angle */
+} coeb_bow_frame;
+
+/* ---- ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) ----
+ * For every node in both feature vectors, the KeyFrame's valid features in index order, each
+ * against the node's frame features (index order) not yet given away: bestDist1 / bestIdxF the
+ * first strict minimum, bestDist2 the second smallest distance (both from 256); accepted when
+ * bestDist1 <= TH_LOW (50) and (float)bestDist1 < nnratio * (float)bestDist2; then the
+ * rotation-histogram filter when check_orientation.  match_out[i] (length cur->n) = the KeyFrame
+ * index whose MapPoint vpMapPointMatches[i] holds, or -1; *nmatches = the return value.
+ * At most 4095 features per side. */
+int coeb_match_bow(coeb_ctx* ctx, const coeb_bow_keyframe* kf, const coeb_bow_frame* cur, float nnratio,
+                   int check_orientation, int32_t* match_out, int* nmatches);
 
 /* The Frame fields Optimizer::PoseOptimization reads (Optimizer.cc:276-357). */
 typedef struct {
