@@ -18,6 +18,10 @@
       include/ORBmatcher.h:65, src/ORBmatcher.cc:159-288 (Tracking::TrackReferenceKeyFrame,
       src/Tracking.cc:833, and Relocalization, :1456); F.ComputeBoW(ctx) first (src/Frame.cc:570-577);
       assigns F.mvpMapPoints[i] = KeyFrame feature index and returns nmatches.
+  KeyFrameDatabase(ctx).add / erase / clear / DetectRelocalizationCandidates(F, neighbours) / SearchByBoW(slots, valids, F)
+      include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc:40-73, 199-309 and the SearchByBoW loop
+      of Tracking::Relocalization (src/Tracking.cc:1449-1470); keyframes are named by slot.
+      bow_vector(word, weight, node): BowVector::addWeight + normalize(L1).
   Vocabulary.from_text(text) / from_arrays(...)  ORBVocabulary::loadFromTextFile (src/System.cc:72)
   ORBmatcher.DescriptorDistance(a, b)  src/ORBmatcher.cc:1648-1664
   Optimizer.PoseOptimization(F, camera)  include/Optimizer.h:47, src/Optimizer.cc:239-451; reads
@@ -66,6 +70,8 @@ ABI_SYMBOLS = [
     "coeb_voc_from_text", "coeb_voc_from_arrays", "coeb_voc_info", "coeb_voc_tables", "coeb_voc_destroy",
     "coeb_bow_set_vocabulary", "coeb_bow_transform", "coeb_bow_batch_device", "coeb_batch_bow_results",
     "coeb_match_bow",
+    "coeb_bow_vector", "coeb_kfdb_create", "coeb_kfdb_destroy", "coeb_kfdb_add", "coeb_kfdb_erase", "coeb_kfdb_clear",
+    "coeb_kfdb_size", "coeb_kfdb_query", "coeb_match_bow_kfdb",
 ]
 # COEB_ABI_VERSION of the include/coeb_front.h these argtypes are written against; lib() refuses
 # a library that reports another (tests/test_capi_symbols.py keeps the two equal)
@@ -121,6 +127,11 @@ class BowKeyFrameC(C.Structure):
 
 class BowFrameC(C.Structure):
     _fields_ = [("n", C.c_int32), ("descriptor", C.c_void_p), ("node_id", C.c_void_p), ("angle", C.c_void_p)]
+
+
+class KfdbKeyFrameC(C.Structure):
+    _fields_ = [("n", C.c_int32), ("descriptor", C.c_void_p), ("node_id", C.c_void_p), ("angle", C.c_void_p),
+                ("bow_word", C.c_void_p), ("bow_value", C.c_void_p), ("nw", C.c_int32)]
 
 
 class CoebError(RuntimeError):
@@ -229,6 +240,19 @@ def lib():
         L.coeb_batch_bow_results.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         L.coeb_match_bow.argtypes = [C.c_void_p, C.POINTER(BowKeyFrameC), C.POINTER(BowFrameC), C.c_float, C.c_int,
                                      C.c_void_p, C.POINTER(C.c_int)]
+        L.coeb_bow_vector.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_int, C.POINTER(C.c_int)]
+        L.coeb_kfdb_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        L.coeb_kfdb_destroy.restype = None
+        L.coeb_kfdb_destroy.argtypes = [C.c_void_p]
+        L.coeb_kfdb_add.argtypes = [C.c_void_p, C.POINTER(KfdbKeyFrameC), C.POINTER(C.c_int)]
+        L.coeb_kfdb_erase.argtypes = [C.c_void_p, C.c_int]
+        L.coeb_kfdb_clear.argtypes = [C.c_void_p]
+        L.coeb_kfdb_size.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.coeb_kfdb_query.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.coeb_match_bow_kfdb.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(BowFrameC),
+                                          C.c_float, C.c_int, C.c_void_p, C.c_void_p]
         L.coeb_profile_enable.argtypes = [C.c_void_p, C.c_int]
         L.coeb_profile_reset.argtypes = [C.c_void_p]
         L.coeb_profile_read.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
@@ -914,6 +938,163 @@ class BowKeyFrame:
         self.angle = np.ascontiguousarray(angle, np.float32)
         if len(self.node_id) != self.N or len(self.angle) != self.N:
             raise ValueError("BowKeyFrame arrays differ in length")
+
+
+def bow_vector(word, weight, node, normalize_l1=True):
+    """DBoW2::BowVector of one frame from coeb_bow_transform's per-feature word / weight / node:
+    addWeight in feature order over the features with node >= 0, then normalize(L1) (host only).
+    -> (word ids ascending int32, values float64)."""
+    word = np.ascontiguousarray(word, np.int32)
+    weight = np.ascontiguousarray(weight, np.float64)
+    node = np.ascontiguousarray(node, np.int32)
+    n = len(word)
+    if len(weight) != n or len(node) != n:
+        raise ValueError("bow_vector arrays differ in length")
+    w_out, v_out = np.empty(max(n, 1), np.int32), np.empty(max(n, 1), np.float64)
+    nw = C.c_int()
+    rc = lib().coeb_bow_vector(_p(word), _p(weight), _p(node), n, int(bool(normalize_l1)), _p(w_out), _p(v_out), n,
+                               C.byref(nw))
+    if rc:
+        raise CoebError("coeb_bow_vector rc=%d" % rc)
+    return w_out[:nw.value].copy(), v_out[:nw.value].copy()
+
+
+class KeyFrameDatabase:
+    """ORB_SLAM2::KeyFrameDatabase for relocalisation, device resident (include/KeyFrameDatabase.h,
+    src/KeyFrameDatabase.cc:40-73, 199-309): a keyframe's descriptors, feature-vector nodes, angles
+    and BowVector are uploaded once by add(); query() counts common words and scores against every
+    keyframe in one call; SearchByBoW() matches a frame against many keyframes in one call.
+    Keyframes are named by the slot add() returns.  The scoring restates DBoW2's L1Scoring; parity
+    against DBoW2 itself is unpinned."""
+
+    def __init__(self, ctx, max_features=4095, initial_slots=64):
+        self.ctx = ctx
+        h = C.c_void_p()
+        ctx.check(lib().coeb_kfdb_create(ctx.h, max_features, initial_slots, C.byref(h)))
+        self.h = h
+        self.mnRelocQuery, self.mnRelocWords, self.mRelocScore = {}, {}, {}
+        self._query_id = 0
+        self._n = {}                    # features per slot
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().coeb_kfdb_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if getattr(self.ctx, "h", None):       # a closed context has released the storage already
+                self.close()
+        except Exception:
+            pass
+
+    def add(self, descriptor, node_id, angle, bow_word, bow_value):
+        """KeyFrameDatabase::add(pKF) -> slot.  bow_word strictly ascending (bow_vector())."""
+        node_id = np.ascontiguousarray(node_id, np.int32)
+        n = len(node_id)
+        descriptor = np.ascontiguousarray(descriptor, np.uint8).reshape(n, 32) if n else np.zeros((0, 32), np.uint8)
+        angle = np.ascontiguousarray(angle, np.float32)
+        bow_word = np.ascontiguousarray(bow_word, np.int32)
+        bow_value = np.ascontiguousarray(bow_value, np.float64)
+        if len(angle) != n or len(bow_value) != len(bow_word):
+            raise ValueError("KeyFrameDatabase.add arrays differ in length")
+        kc = KfdbKeyFrameC(n, _p(descriptor), _p(node_id), _p(angle), _p(bow_word), _p(bow_value), len(bow_word))
+        slot = C.c_int()
+        self.ctx.check(lib().coeb_kfdb_add(self.h, C.byref(kc), C.byref(slot)))
+        for d in (self.mnRelocQuery, self.mnRelocWords, self.mRelocScore):
+            d.pop(slot.value, None)
+        self._n[slot.value] = n
+        return slot.value
+
+    def erase(self, slot):
+        self.ctx.check(lib().coeb_kfdb_erase(self.h, int(slot)))
+
+    def clear(self):
+        self.ctx.check(lib().coeb_kfdb_clear(self.h))
+        self.mnRelocQuery, self.mnRelocWords, self.mRelocScore = {}, {}, {}
+
+    def size(self):
+        """(keyframes, slots: the length of query()'s arrays)"""
+        nk, ns = C.c_int(), C.c_int()
+        self.ctx.check(lib().coeb_kfdb_size(self.h, C.byref(nk), C.byref(ns)))
+        return nk.value, ns.value
+
+    def query(self, word, value):
+        """The query BowVector against every keyframe: dict(common [nslots] = mnRelocWords,
+        score [nslots] float32 (-1 where common <= min_common), order = lKFsSharingWords as slots,
+        max_common, min_common)."""
+        word = np.ascontiguousarray(word, np.int32)
+        value = np.ascontiguousarray(value, np.float64)
+        if len(word) != len(value):
+            raise ValueError("query arrays differ in length")
+        ns = self.size()[1]
+        common, score, order = np.zeros(max(ns, 1), np.int32), np.zeros(max(ns, 1), np.float32), \
+            np.zeros(max(ns, 1), np.int32)
+        nsh, mx, mn = C.c_int(), C.c_int(), C.c_int()
+        self.ctx.check(lib().coeb_kfdb_query(self.h, _p(word), _p(value), len(word), _p(common), _p(score), _p(order),
+                                             C.byref(nsh), C.byref(mx), C.byref(mn)))
+        return dict(common=common[:ns], score=score[:ns], order=order[:nsh.value].copy(), max_common=mx.value,
+                    min_common=mn.value)
+
+    def DetectRelocalizationCandidates(self, F, neighbours=None):
+        """KeyFrameDatabase::DetectRelocalizationCandidates(F) -> candidate slots.  F: a Frame after
+        ComputeBoW (F.mBowVec = (word, value) is filled from it when absent); F.mnId names the query
+        (a fresh id when absent).  neighbours(slot) -> the slots of GetBestCovisibilityKeyFrames(10);
+        the covisibility tail (:258-308) runs here on the host."""
+        if getattr(F, "mBowVec", None) is None:
+            F.mBowVec = bow_vector(F.mBowWord, F.mBowWeight, F.mFeatNode)
+        self._query_id += 1
+        fid = getattr(F, "mnId", ("query", self._query_id))
+        q = self.query(*F.mBowVec)
+        for s in q["order"]:
+            self.mnRelocQuery[int(s)] = fid
+            self.mnRelocWords[int(s)] = int(q["common"][s])
+        scored = [int(s) for s in q["order"] if q["common"][s] > q["min_common"]]
+        for s in scored:
+            self.mRelocScore[s] = q["score"][s]
+        acc, best_acc = [], np.float32(0)
+        for s in scored:
+            best_score = acc_score = q["score"][s]
+            best = s
+            for s2 in (neighbours(s) if neighbours else ()):
+                if self.mnRelocQuery.get(s2) != fid:
+                    continue
+                sc2 = np.float32(self.mRelocScore.get(s2, 0.0))
+                acc_score = np.float32(acc_score + sc2)
+                if sc2 > best_score:
+                    best, best_score = s2, sc2
+            acc.append((acc_score, best))
+            if acc_score > best_acc:
+                best_acc = acc_score
+        min_retain = np.float32(0.75) * best_acc
+        out = []
+        for si, s in acc:
+            if si > min_retain and s not in out:
+                out.append(s)
+        return out
+
+    def SearchByBoW(self, slots, valids, F, nnratio=0.75, checkOri=True):
+        """ORBmatcher(nnratio, checkOri).SearchByBoW(pKF, F, vpMapPointMatches) for every candidate
+        slot (Tracking.cc:1449-1470); valids[j]: GetMapPointMatches()[i] && !isBad() of candidate j.
+        -> (matches [ncand][F.N]: the keyframe feature whose MapPoint keypoint i takes or -1,
+        nmatches [ncand])."""
+        slots = np.ascontiguousarray(slots, np.int32)
+        nc = len(slots)
+        if len(valids) != nc:
+            raise ValueError("one valid mask per candidate")
+        valids = [np.ascontiguousarray(v, np.uint8) for v in valids]
+        for s, v in zip(slots, valids):
+            if int(s) in self._n and len(v) != self._n[int(s)]:
+                raise ValueError("valid mask of slot %d has %d entries, the keyframe %d" % (s, len(v), self._n[int(s)]))
+        vp = (C.c_void_p * max(nc, 1))(*[v.ctypes.data if len(v) else None for v in valids])
+        node = np.ascontiguousarray(F.mFeatNode, np.int32)
+        angle = np.ascontiguousarray(F.mvKeysUn["angle"], np.float32)
+        fc = BowFrameC(F.N, *[C.c_void_p(a.ctypes.data) for a in (F.mDescriptors, node, angle)])
+        out = np.full((nc, F.N), -1, np.int32)
+        nm = np.zeros(max(nc, 1), np.int32)
+        self.ctx.check(lib().coeb_match_bow_kfdb(self.h, _p(slots) if nc else None, nc, vp, C.byref(fc), nnratio,
+                                                 int(checkOri), _p(out) if out.size else None, _p(nm)))
+        return out, nm[:nc]
 
 
 class ORBmatcher:

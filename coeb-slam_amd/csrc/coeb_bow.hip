@@ -11,14 +11,9 @@
 #include <algorithm>
 #include <cstring>
 
-#include "coeb_ctx.hpp"
-#include "coeb_match_dev.hpp"
+#include "coeb_bow_dev.hpp"
 
 namespace {
-
-constexpr int kBowThreads = 256;
-constexpr int kBowMax = kCurMax;        // features per frame the CSR and the matcher take
-constexpr int TH_LOW = 50;
 
 // Minimum of v over the 16 lanes of a DPP row, in every lane: xor 1, xor 2 (quad permutes), then
 // the half-row and row mirrors (lane i <-> 7 - i, i <-> 15 - i), each of which pairs groups
@@ -102,14 +97,8 @@ __global__ __launch_bounds__(kBowThreads) void k_bow_transform(const VocRec* __r
 // (and valid[i], when given) sorted by (node id, index) with a counting (rank) sort -- the rank
 // of a feature is the number of features before it in that order, counted against the node ids
 // in LDS -- then the distinct node ids by a scan over the run heads.
-//   out[0] = nd distinct nodes, out[1] = m listed features,
-//   out + 4: node[cap] ascending, then off[cap + 1], then idx[cap]   (cap = max(n, 1))
-struct CsrSide { const int* node; const uint8_t* valid; int n; int* out; };
-struct CsrArgs { CsrSide side[2]; int* clear_m1; int clear_n; int* clear_0; int clear_0n; };
-
-constexpr int kCsrThreads = 1024;
+// The layout of `out`, CsrSide and CsrArgs: coeb_bow_dev.hpp.
 constexpr int kCsrSlots = 4096;         // >= kBowMax + 1
-inline int csr_ints(int n) { return 4 + 3 * std::max(n, 1) + 1; }
 
 __global__ __launch_bounds__(kCsrThreads) void k_bow_csr(CsrArgs a)
 {
@@ -178,103 +167,16 @@ __global__ __launch_bounds__(kCsrThreads) void k_bow_csr(CsrArgs a)
 }
 
 // ============================= k_match_bow =============================
-// One wave per node of the KeyFrame's FeatureVector; a node the frame does not have ends at once.
-// A frame feature lies under one node only, so the nodes are independent; within a node the
-// KeyFrame features are taken in order, each against the node's frame features not yet given
-// away (:205-226).  Lane l looks at list positions l, l + 64, ..: its "taken" bits are a private
-// 64-bit mask (a list holds at most kBowMax < 4096 features), the frame descriptors of a list of
-// up to kTile sit in LDS (word-major, so a wave reads consecutive banks), longer lists are read
-// from global memory.  best1 = min of (dist << 16 | position): the first strict minimum;
-// best2 = the second order statistic, merged as min(b2, b2', max(b1, b1')).
-struct BowSide { const uint8_t* desc; const float* angle; const int* csr; int n; };
+// One wave per node of the KeyFrame's FeatureVector (bow_match_node, coeb_bow_dev.hpp); the
+// KeyFrame's CSR holds its valid features only.
 struct BowMatch { BowSide kf, cur; float nnratio; int check_ori; int* match; int* bin; int* hist; };
-
-constexpr int kBowWaves = kBowThreads / 64;
-constexpr int kTile = 128;
 
 __global__ __launch_bounds__(kBowThreads) void k_match_bow(BowMatch a)
 {
     __shared__ uint32_t s_desc[kBowWaves][8][kTile];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int w = blockIdx.x * kBowWaves + wv;
-    const int kcap = max(a.kf.n, 1), ccap = max(a.cur.n, 1);
-    const int* k_node = a.kf.csr + 4;
-    const int* k_off = k_node + kcap;
-    const int* k_idx = k_off + kcap + 1;
-    const int* c_node = a.cur.csr + 4;
-    const int* c_off = c_node + ccap;
-    const int* c_idx = c_off + ccap + 1;
-    if (w >= a.kf.csr[0]) return;                  // wave-uniform from here on
-    const int node = k_node[w];
-    int lo = 0, hi = a.cur.csr[0];
-    while (lo < hi) {                              // lower bound of node among the frame's nodes
-        const int mid = (lo + hi) >> 1;
-        if (c_node[mid] < node) lo = mid + 1;
-        else hi = mid;
-    }
-    if (lo >= a.cur.csr[0] || c_node[lo] != node) return;
-    const int c0 = c_off[lo], len = c_off[lo + 1] - c0;
-    const int k0 = k_off[w], k1 = k_off[w + 1];
-    const int iters = (len + 63) >> 6;
-    const bool tile = len <= kTile;
-    if (tile) {
-        for (int p = lane; p < len; p += 64) {
-            const uint4* d = reinterpret_cast<const uint4*>(a.cur.desc + (int64_t)c_idx[c0 + p] * 32);
-            const uint4 d0 = d[0], d1 = d[1];
-            s_desc[wv][0][p] = d0.x; s_desc[wv][1][p] = d0.y; s_desc[wv][2][p] = d0.z; s_desc[wv][3][p] = d0.w;
-            s_desc[wv][4][p] = d1.x; s_desc[wv][5][p] = d1.y; s_desc[wv][6][p] = d1.z; s_desc[wv][7][p] = d1.w;
-        }
-    }
-    // no barrier: position p is written and read by lane p % 64 only
-    uint64_t taken = 0;
-    for (int kq = k0; kq < k1; kq++) {
-        const int ikf = __builtin_amdgcn_readfirstlane(k_idx[kq]);
-        uint32_t q[8];
-        {
-            const uint4* d = reinterpret_cast<const uint4*>(a.kf.desc + (int64_t)ikf * 32);
-            const uint4 d0 = d[0], d1 = d[1];
-            q[0] = d0.x; q[1] = d0.y; q[2] = d0.z; q[3] = d0.w;
-            q[4] = d1.x; q[5] = d1.y; q[6] = d1.z; q[7] = d1.w;
-        }
-        uint32_t b1 = (256u << 16) | 0xFFFFu, b2 = 256;
-        for (int it = 0; it < iters; it++) {
-            const int p = it * 64 + lane;
-            if (p >= len || ((taken >> it) & 1)) continue;
-            uint32_t c[8];
-            if (tile) {
-#pragma unroll
-                for (int k = 0; k < 8; k++) c[k] = s_desc[wv][k][p];
-            } else {
-                const uint4* d = reinterpret_cast<const uint4*>(a.cur.desc + (int64_t)c_idx[c0 + p] * 32);
-                const uint4 d0 = d[0], d1 = d[1];
-                c[0] = d0.x; c[1] = d0.y; c[2] = d0.z; c[3] = d0.w;
-                c[4] = d1.x; c[5] = d1.y; c[6] = d1.z; c[7] = d1.w;
-            }
-            const uint32_t dist = (uint32_t)hamming32(q, c);
-            if (dist < (b1 >> 16)) { b2 = b1 >> 16; b1 = (dist << 16) | (uint32_t)p; }   // p ascends per lane
-            else if (dist < b2) b2 = dist;
-        }
-#pragma unroll
-        for (int x = 1; x < 64; x <<= 1) {
-            const uint32_t o1 = (uint32_t)__shfl_xor((int)b1, x), o2 = (uint32_t)__shfl_xor((int)b2, x);
-            b2 = min(min(b2, o2), max(b1, o1) >> 16);
-            b1 = min(b1, o1);
-        }
-        const int d1 = (int)(b1 >> 16), p1 = (int)(b1 & 0xFFFFu);
-        if (d1 <= TH_LOW && (float)d1 < a.nnratio * (float)(int)b2) {
-            if ((p1 & 63) == lane) taken |= (uint64_t)1 << (p1 >> 6);
-            if (lane == 0) {
-                const int icur = c_idx[c0 + p1];
-                a.match[icur] = ikf;
-                if (a.check_ori) {
-                    int bin = rot_bin(a.kf.angle[ikf], a.cur.angle[icur]);
-                    if (bin < 0 || bin >= HISTO_LENGTH) bin = HISTO_LENGTH;      // the reference asserts; dropped below
-                    else atomicAdd(&a.hist[bin], 1);
-                    a.bin[icur] = bin;
-                }
-            }
-        }
-    }
+    bow_match_node<false>(a.kf, a.cur, nullptr, blockIdx.x * kBowWaves + wv, a.nnratio, a.check_ori, a.match, a.bin,
+                          a.hist, s_desc[wv], lane);
 }
 
 // The rotation-consistency filter over the whole frame (:267-285) and the match count:
@@ -283,26 +185,7 @@ __global__ __launch_bounds__(kCsrThreads) void k_bow_rot(int* inout, const int* 
                                                          int check_ori)
 {
     __shared__ int s_ind[3], s_cnt;
-    const int tid = threadIdx.x;
-    if (tid == 0) {
-        int i1 = -1, i2 = -1, i3 = -1;
-        if (check_ori) three_maxima(hist, i1, i2, i3);
-        s_ind[0] = i1; s_ind[1] = i2; s_ind[2] = i3;
-        s_cnt = 0;
-    }
-    __syncthreads();
-    int kept = 0;
-    for (int i = tid; i < n; i += kCsrThreads) {
-        int m = inout[i];
-        if (m >= 0 && check_ori) {
-            const int b = bin[i];
-            if (b != s_ind[0] && b != s_ind[1] && b != s_ind[2]) { m = -1; inout[i] = -1; }
-        }
-        kept += m >= 0;
-    }
-    if (kept) atomicAdd(&s_cnt, kept);
-    __syncthreads();
-    if (tid == 0) inout[cap] = s_cnt;
+    bow_rot_filter(inout, bin, hist, n, check_ori, inout + cap, s_ind, &s_cnt);
 }
 
 int launch_transform(coeb_ctx* c, const uint8_t* d_desc, const int* d_counts, int n_fixed, int stride, int F,
@@ -323,6 +206,13 @@ int launch_transform(coeb_ctx* c, const uint8_t* d_desc, const int* d_counts, in
 }
 
 }  // namespace
+
+void launch_bow_csr(coeb_ctx* c, const CsrArgs& a, int sides, hipStream_t s)
+{
+    prof_begin(&c->hook, "k_bow_csr", s);
+    hipLaunchKernelGGL(k_bow_csr, dim3(sides), dim3(kCsrThreads), 0, s, a);
+    prof_end(&c->hook, s);
+}
 
 extern "C" {
 
@@ -370,9 +260,7 @@ int coeb_bow_transform(coeb_ctx* c, const uint8_t* desc, int n, int levelsup, in
         return hip_err(c, hipGetLastError(), "k_bow_transform");
     CsrArgs ca{};
     ca.side[0] = CsrSide{d_node, nullptr, n, d_csr};
-    prof_begin(&c->hook, "k_bow_csr", s);
-    hipLaunchKernelGGL(k_bow_csr, dim3(1), dim3(kCsrThreads), 0, s, ca);
-    prof_end(&c->hook, s);
+    launch_bow_csr(c, ca, 1, s);
     HIP_TRY(c, hipGetLastError());
     const int32_t* h = reinterpret_cast<const int32_t*>(c->pin);
     HIP_TRY(c, hipMemcpyAsync(c->pin, d_word, nout * 4, hipMemcpyDeviceToHost, s));
@@ -462,9 +350,7 @@ int coeb_match_bow(coeb_ctx* c, const coeb_bow_keyframe* kf, const coeb_bow_fram
     ca.side[1] = CsrSide{(const int*)(dbase + o_cn), nullptr, n, csr_c};
     ca.clear_m1 = bw.m_out.p; ca.clear_n = cs + 1;
     ca.clear_0 = d_bin; ca.clear_0n = cs + 32;
-    prof_begin(&c->hook, "k_bow_csr", s);
-    hipLaunchKernelGGL(k_bow_csr, dim3(2), dim3(kCsrThreads), 0, s, ca);
-    prof_end(&c->hook, s);
+    launch_bow_csr(c, ca, 2, s);
     BowMatch bm;
     bm.kf = BowSide{dbase + o_kd, (const float*)(dbase + o_ka), csr_k, nq};
     bm.cur = BowSide{dbase + o_cd, (const float*)(dbase + o_ca), csr_c, n};

@@ -695,6 +695,7 @@ void coeb_destroy(coeb_ctx* c)
         (void)hipEventDestroy(c->ev_pose);
         if (c->ev_tlm) (void)hipEventDestroy(c->ev_tlm);
     }
+    kfdb_release_all(c);
     auto free_buf = [](auto& a) { if (a.p) (void)hipFree(a.p); };
     each_buf(c->pl, free_buf); each_buf(c->ex, free_buf); each_buf(c->fb, free_buf);
     each_buf(c->bm, free_buf); each_buf(c->bp, free_buf); each_buf(c->tl, free_buf);

@@ -169,6 +169,7 @@ struct coeb_ctx {
     // single-frame transform gathers on the host
     struct { int k = 0, L = 0, nnodes = 0; std::vector<double> word_weight; } voc;
     int bow_frames = 0;        // frames of the last coeb_bow_batch_device
+    std::vector<coeb_kfdb*> kfdbs;     // the keyframe databases alive on this context (coeb_kfdb.hip)
     std::string err;
     ProfImpl prof;
     ProfileHook hook;
@@ -230,6 +231,7 @@ hipStream_t main_stream(coeb_ctx* c);
 void join_pose(coeb_ctx* c);                    // the context stream waits for the last batch pose
 int quiesce(coeb_ctx* c);                       // nothing enqueued by the context is running afterwards
 const SideStream* side_stream(coeb_ctx* c);     // launch_extract's side stream, or null when disabled
+void kfdb_release_all(coeb_ctx* c);             // coeb_kfdb.hip: coeb_destroy frees the databases' device memory
 
 // a holds at least max(count * sizeof(T), 256) bytes afterwards; it only grows
 template <class T>

@@ -62,7 +62,16 @@
  *                                      include/ORBmatcher.h:65, src/ORBmatcher.cc:159-288; the calls
  *                                      in TrackReferenceKeyFrame  src/Tracking.cc:833 and
  *                                      Relocalization  src/Tracking.cc:1456
- *   coeb_tum_read_list              <- associate.py read_file_list  associate.py:49-69
+ *   coeb_bow_vector                 <- DBoW2 BowVector::addWeight / normalize(L1) as transform() fills
+ *                                      mBowVec (host only; restated, parity against DBoW2 UNPINNED)
+ *   coeb_kfdb_add / _erase / _clear <- KeyFrameDatabase::add / erase / clear
+ *                                      src/KeyFrameDatabase.cc:40-73
+ *   coeb_kfdb_query                 <- KeyFrameDatabase::DetectRelocalizationCandidates up to
+ *                                      lScoreAndMatch  src/KeyFrameDatabase.cc:199-253 (the
+ *                                      covisibility tail :258-308 stays on the host, in the adapters)
+ *   coeb_match_bow_kfdb             <- the SearchByBoW loop of Tracking::Relocalization
+ *                                      src/Tracking.cc:1449-1470
+ *   coeb_tum_read_list             <- associate.py read_file_list  associate.py:49-69
  *   coeb_tum_associate              <- associate.py associate  associate.py:71-102 (host only)
  *
  * Conventions: 0 on success, negative COEB_E* code on failure (the reference has no error
@@ -391,6 +400,62 @@ typedef struct {
  * At most 4095 features per side. */
 int coeb_match_bow(coeb_ctx* ctx, const coeb_bow_keyframe* kf, const coeb_bow_frame* cur, float nnratio,
                    int check_orientation, int32_t* match_out, int* nmatches);
+
+/* ---- BowVector filling: addWeight in feature order, then normalize(L1) (host only, no context) ----
+ * For every feature i < n with node[i] >= 0 (coeb_bow_transform's "weight > 0"), in order:
+ * value[word[i]] += weight[i] when the word is present (sequential double adds, not count * weight),
+ * else the word is inserted with weight[i].  With normalize_l1: norm = the sum of fabs(value) in
+ * ascending word order; when norm > 0.0 every value /= norm.  word_out / value_out (cap entries)
+ * get the words ascending; more than cap words: COEB_ERANGE with *nw_out set, nothing written. */
+int coeb_bow_vector(const int32_t* word, const double* weight, const int32_t* node, int n, int normalize_l1,
+                    int32_t* word_out, double* value_out, int cap, int* nw_out);
+
+/* ---- the keyframe database: KeyFrameDatabase::add / erase / clear and the query half of
+ * DetectRelocalizationCandidates (src/KeyFrameDatabase.cc:40-73, 199-253), SearchByBoW against
+ * many keyframes (the loop of Tracking::Relocalization, src/Tracking.cc:1449-1470) ----
+ * A database lives on its context's device and stream, holds per keyframe what never changes after
+ * KeyFrame::ComputeBoW and is bound by the context's non-reentrancy rule.  Destroy it before its
+ * context (coeb_destroy releases the device memory of the databases still alive; their handles
+ * then only take coeb_kfdb_destroy).  BowVector scoring restates DBoW2's L1Scoring; parity against
+ * DBoW2 itself is UNPINNED. */
+typedef struct coeb_kfdb coeb_kfdb;
+typedef struct {
+    int32_t n;                        /* pKF->N */
+    const uint8_t* descriptor;        /* n x 32, pKF->mDescriptors */
+    const int32_t* node_id;           /* the mFeatVec node that lists feature i, -1: none */
+    const float* angle;               /* pKF->mvKeysUn[i].angle */
+    const int32_t* bow_word;          /* pKF->mBowVec: nw word ids, strictly ascending */
+    const double* bow_value;          /* ... and their values */
+    int32_t nw;
+} coeb_kfdb_keyframe;
+/* max_features (1..4095) bounds n and nw of every keyframe and nw of a query; initial_slots >= 1. */
+int coeb_kfdb_create(coeb_ctx* ctx, int max_features, int initial_slots, coeb_kfdb** db);
+void coeb_kfdb_destroy(coeb_kfdb* db);
+/* One staged upload; the keyframe's feature-vector CSR is built once, over all features with
+ * node_id >= 0.  *slot_out = the lowest free slot; past the allocated slots the storage doubles
+ * (slot ids stay valid).  Every add takes the next insertion sequence number.  COEB_EINVAL when n
+ * or nw exceeds max_features or bow_word is not strictly ascending. */
+int coeb_kfdb_add(coeb_kfdb* db, const coeb_kfdb_keyframe* kf, int* slot_out);
+int coeb_kfdb_erase(coeb_kfdb* db, int slot);       /* COEB_EINVAL for an empty or out-of-range slot */
+int coeb_kfdb_clear(coeb_kfdb* db);
+/* nslots = one past the highest slot ever handed out (the length of the query's arrays). */
+int coeb_kfdb_size(const coeb_kfdb* db, int* nkeyframes, int* nslots);
+/* The query BowVector (word ascending, nw <= max_features) against every keyframe:
+ * common[slot] = |words(F) & words(KF)| = mnRelocWords (0 for empty slots); *max_common its
+ * maximum; *min_common = (int)(max_common * 0.8f); score[slot] = (float)L1Scoring::score(F, KF)
+ * where common[slot] > *min_common, -1.0f elsewhere; order[0 .. *n_sharing) = the slots with
+ * common > 0 as lKFsSharingWords lists them (ascending smallest common word, then insertion).
+ * common, score, order hold nslots entries.  An empty database or nw == 0: all three counts 0. */
+int coeb_kfdb_query(coeb_kfdb* db, const int32_t* word, const double* value, int nw, int32_t* common,
+                    float* score, int32_t* order, int* n_sharing, int* max_common, int* min_common);
+/* coeb_match_bow of `cur` against keyframes slots[0 .. ncand) (ncand <= 256; a slot may repeat),
+ * candidate j with valid[j] (n_kf bytes: vpMapPointsKF[i] && !isBad(), may be NULL when n_kf is 0):
+ * match_out[j][cur->n] and nmatches[j] are what coeb_match_bow returns for that keyframe.  One
+ * upload, one download, one synchronisation.  COEB_EINVAL (nothing written) for an empty or
+ * out-of-range slot or more than 256 candidates. */
+int coeb_match_bow_kfdb(coeb_kfdb* db, const int32_t* slots, int ncand, const uint8_t* const* valid,
+                        const coeb_bow_frame* cur, float nnratio, int check_orientation, int32_t* match_out,
+                        int32_t* nmatches);
 
 /* The Frame fields Optimizer::PoseOptimization reads (Optimizer.cc:276-357). */
 typedef struct {
