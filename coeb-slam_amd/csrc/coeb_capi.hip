@@ -201,8 +201,7 @@ int ensure_plan(coeb_ctx* c, int W, int H)
         return set_err(c, COEB_EINVAL, "image size outside the context limits");
     std::string err;
     Plan P;
-    const char* kl = coeb_experiment("COEB_OCT_KL");
-    if (!make_plan(c->tab, W, H, kl ? atoi(kl) : 0, P, c->rtab, c->cells, err)) return set_err(c, COEB_EINVAL, err);
+    if (!make_plan(c->tab, W, H, 0, P, c->rtab, c->cells, err)) return set_err(c, COEB_EINVAL, err);
     // the plan, rtab and cells are rewritten in place below: batches still in flight on the
     // context's streams (pyramid / FAST / octree / describe read them) must finish first
     int rc;
@@ -301,30 +300,7 @@ const char* coeb_switch(const char* name)
     return nullptr;            // not a product switch: never read
 }
 
-const char* coeb_experiment(const char* name)
-{
-    static const bool on = [] {
-        const char* e = getenv("COEB_EXPERIMENTS");
-        return e && e[0] == '1';
-    }();
-    return on ? getenv(name) : nullptr;
-}
-
 namespace {
-
-// A non-blocking stream whose priority the environment variable `env` may set ("high" / "low":
-// the device's greatest / least stream priority; unset: the default).  Experiment knob for the
-// multi-stream schedules (which queue the dispatcher serves first when CUs free up).
-static hipError_t make_stream(hipStream_t* s, const char* env)
-{
-    const char* e = env ? coeb_experiment(env) : nullptr;
-    if (e && (e[0] == 'h' || e[0] == 'l')) {
-        int least = 0, greatest = 0;
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess)
-            return hipStreamCreateWithPriority(s, hipStreamNonBlocking, e[0] == 'h' ? greatest : least);
-    }
-    return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
-}
 
 // The device's shared side stream (COEB_SIDE_SHARED=1): with P pipelines the P context streams
 // plus one side stream fill the 4 hardware queues exactly, instead of 2P streams sharing them.
@@ -337,7 +313,7 @@ static hipError_t shared_side_acquire(int device, hipStream_t* out)
     std::lock_guard<std::mutex> lk(g_shared_side_mu);
     auto& e = g_shared_side[device];
     if (!e.first) {
-        hipError_t r = make_stream(&e.first, "COEB_SIDE_PRIO");
+        hipError_t r = hipStreamCreateWithFlags(&e.first, hipStreamNonBlocking);
         if (r != hipSuccess) { e.first = nullptr; return r; }
     }
     ++e.second;
@@ -367,17 +343,11 @@ const SideStream* side_stream(coeb_ctx* c)
         c->side_init = true;
         const char* e = coeb_switch("COEB_SIDE_STREAM");
         if (e && e[0] == '0') return nullptr;
-        const char* sp = coeb_experiment("COEB_SIDE_SPLIT");          // first level left to the context stream
-        if (sp) c->side.split = atoi(sp);
-        const char* bl = coeb_experiment("COEB_SIDE_BLUR");           // 0: late levels' blur on the context stream
-        if (bl) c->side.blur_late = bl[0] == '1';
-        const char* so = coeb_experiment("COEB_SIDE_OCTREE");         // 1: early levels' octree on the side stream
-        if (so) c->side.side_octree = so[0] == '1';
         const char* sh = coeb_switch("COEB_SIDE_SHARED");         // 1: one side stream per device
         c->side_shared = sh && sh[0] == '1';
         hipError_t se = c->side_shared ? shared_side_acquire(c->device, &c->side.s)
-                                       : make_stream(&c->side.s, "COEB_SIDE_PRIO");
-        hipEvent_t* evs[] = {&c->side.fork, &c->side.mid, &c->side.pyr_done, &c->side.join2, &c->side.join};
+                                       : hipStreamCreateWithFlags(&c->side.s, hipStreamNonBlocking);
+        hipEvent_t* evs[] = {&c->side.fork, &c->side.mid, &c->side.pyr_done, &c->side.join};
         bool ok = se == hipSuccess;
         for (hipEvent_t* e : evs) {
             *e = nullptr;
@@ -638,7 +608,7 @@ coeb_ctx* coeb_create(const coeb_orb_params* params, int device, int max_width, 
     c->max_w = max_width;
     c->max_h = max_height;
     c->max_batch = max_batch;
-    if (hipSetDevice(device) != hipSuccess || make_stream(&c->stream, "COEB_MAIN_PRIO") != hipSuccess) {
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
         g_last_error = "coeb_create: stream creation failed";
         delete c;
         return nullptr;
@@ -670,11 +640,9 @@ void coeb_destroy(coeb_ctx* c)
     if (c->stream) (void)hipStreamSynchronize(main_stream(c));
     if (c->side.s) {
         if (c->side_shared) {
-            // this context's side work ends at its join events; the other contexts' work queued on
+            // this context's side work ends at its join event; the other contexts' work queued on
             // the shared stream is theirs to wait for (the last release synchronises the stream)
             (void)hipEventSynchronize(c->side.join);
-            (void)hipEventSynchronize(c->side.join2);
-            if (c->ev_fjoin) (void)hipEventSynchronize(c->ev_fjoin);
             shared_side_release(c->device);
         } else {
             (void)hipStreamSynchronize(c->side.s);
@@ -683,11 +651,8 @@ void coeb_destroy(coeb_ctx* c)
         (void)hipEventDestroy(c->side.fork);
         (void)hipEventDestroy(c->side.mid);
         (void)hipEventDestroy(c->side.pyr_done);
-        (void)hipEventDestroy(c->side.join2);
         (void)hipEventDestroy(c->side.join);
     }
-    if (c->ev_ffork) (void)hipEventDestroy(c->ev_ffork);
-    if (c->ev_fjoin) (void)hipEventDestroy(c->ev_fjoin);
     if (c->pose_stream) {
         (void)hipStreamSynchronize(c->pose_stream);
         (void)hipStreamDestroy(c->pose_stream);
@@ -1104,7 +1069,7 @@ int coeb_match_localmap(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe
     const size_t o_l = pk.add(mp->level, (size_t)nq * 4), o_c = pk.add(mp->view_cos, (size_t)nq * 4);
     const size_t o_qd = pk.add(mp->descriptor, (size_t)nq * 32), o_no = pk.add(mp->observations, (size_t)nq * 4);
     if ((rc = stage_in(c, pk, &dbase, s))) return rc;
-    LocalBufsHost b;
+    LocalBufs b;
     b.cur_kps = dbase + o_k; b.cur_desc = dbase + o_d; b.cur_ur = (const float*)(dbase + o_ur);
     b.cur_obs = (const int*)(dbase + o_co); b.cur_n = n;
     b.in_view = dbase + o_v; b.proj_x = (const float*)(dbase + o_px); b.proj_y = (const float*)(dbase + o_py);
@@ -1145,7 +1110,7 @@ int coeb_match_keyframe(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe
     const size_t o_mn = pk.add(kf->min_distance, (size_t)nq * 4), o_a = pk.add(kf->angle, (size_t)nq * 4);
     const size_t o_T = pk.add(Tcw, 64);
     if ((rc = stage_in(c, pk, &dbase, s))) return rc;
-    KfBufsHost b;
+    KfBufs b;
     b.cur_kps = dbase + o_k; b.cur_desc = dbase + o_d; b.cur_has = dbase + o_h; b.cur_n = n;
     b.valid = dbase + o_v; b.xw = (const float*)(dbase + o_x); b.desc = dbase + o_qd;
     b.maxd = (const float*)(dbase + o_mx); b.mind = (const float*)(dbase + o_mn); b.angle = (const float*)(dbase + o_a);
@@ -1271,7 +1236,7 @@ int match_batch_impl(coeb_ctx* c, const float* d_depth, int F, int W, int H, con
             mb.match = bm.b_match.p + q + K; mb.nmatch = bm.b_nm.p + p0 + 1; mb.scratch = bm.b_scr.p + q * kCQ;
             mb.scratch_stride = K * kCQ; mb.err = c->ex.err.p;
             mb.qn = bm.b_mqn.p + (int64_t)p0 * qs; mb.qn_stride = qs;
-            if (COEB_MATCH_CLOCK && coeb_experiment("COEB_MATCH_TIMING")) {
+            if (COEB_MATCH_CLOCK) {
                 if ((rc = ensure(c, c->tim.m_timing, (size_t)F * 16))) return rc;
                 mb.timing = c->tim.m_timing.p + (int64_t)p0 * 16;
             }
@@ -1343,7 +1308,7 @@ int coeb_pose_batch_device(coeb_ctx* c, const coeb_camera* cam, int F, const flo
         return rc;
     hipStream_t s = main_stream(c);                 // joins the matchers' chunk streams
     if (!c->pose_stream) {
-        HIP_TRY(c, make_stream(&c->pose_stream, "COEB_POSE_PRIO"));
+        HIP_TRY(c, hipStreamCreateWithFlags(&c->pose_stream, hipStreamNonBlocking));
         HIP_TRY(c, hipEventCreateWithFlags(&c->ev_tprep, hipEventDisableTiming));
         HIP_TRY(c, hipEventCreateWithFlags(&c->ev_pose, hipEventDisableTiming));
     }
@@ -1369,7 +1334,7 @@ int coeb_pose_batch_device(coeb_ctx* c, const coeb_camera* cam, int F, const flo
     b.inv_sigma2 = bp.t_isg.p; b.Tcw = bp.t_T.p + 16; b.outlier = bp.t_outl.p + o; b.result = bp.t_res.p + 1;
     b.edges = bp.t_edge.p + o; b.active = bp.t_act.p + o; b.chi2 = bp.t_chi.p + o; b.stride = K;
     b.timing = nullptr;
-    if (coeb_experiment("COEB_POSE_TIMING")) {               // diagnostic phase clocks, tools/_pose_timing.py
+    if (COEB_POSE_CLOCK) {                                   // diagnostic phase clocks, tools/_pose_timing.py
         if ((rc = ensure(c, c->tim.p_timing, (size_t)F * 8))) return rc;
         long long* tmb = c->tim.p_timing.p;
         HIP_TRY(c, hipMemsetAsync(tmb, 0, (size_t)F * 64, s));
@@ -1453,7 +1418,7 @@ int coeb_track_local_map_batch_device(coeb_ctx* c, const coeb_camera* cam, int F
     HIP_TRY(c, hipStreamWaitEvent(ps, c->ev_tlm, 0));
     const MatchCam mcam = make_cam(c, cam);
     if (launch_tlm_frustum(mcam, t, F, ps, &c->hook)) return hip_err(c, hipGetLastError(), "launch_tlm_frustum");
-    LocalBufsHost lb;
+    LocalBufs lb;
     lb.cur_kps = bp.t_kp.p + K;
     lb.cur_desc = s_desc + (int64_t)2 * K * 32;      // frame 1 = row 2
     lb.cur_ur = bp.t_ur.p + K;
@@ -1464,7 +1429,8 @@ int coeb_track_local_map_batch_device(coeb_ctx* c, const coeb_camera* cam, int F
     lb.desc = s_desc;                                // frame 1's local map: KF2 = frame -1 (row 0), KF1 = frame 0
     lb.match = lmatch + K; lb.nmatch = tl.tl_nlocal.p + 1; lb.lists = tl.tl_lists.p; lb.err = c->ex.err.p;
     lb.path = tl.tl_path.p + 2;
-    lb.cur_n_arr = s_cnt + 1; lb.active = act + 1; lb.npairs = F - 1; lb.cur_stride = K; lb.mp_desc_stride = K;
+    lb.cur_n_arr = s_cnt + 1; lb.active = act + 1; lb.npairs = F - 1; lb.cur_stride = K; lb.mp_stride = (int)M;
+    lb.mp_desc_stride = K;
     rc = launch_match_local(mcam, lb, th, nnratio, ps, &c->hook);
     if (rc == -2) return set_err(c, COEB_ERANGE, "coeb_track_local_map_batch_device: frame and local map exceed the LDS budget");
     if (rc) return hip_err(c, hipGetLastError(), "launch_match_local");
@@ -1851,7 +1817,7 @@ int coeb_debug_read(coeb_ctx* c, const char* what, int f, void* host, size_t byt
         return 0;
     }
     if (c && what && (std::string(what) == "pose_timing" || std::string(what) == "match_timing")) {
-        // [F][8] k_pose phase clocks (COEB_POSE_TIMING) / [F][16] k_match phase clocks (COEB_MATCH_TIMING)
+        // [F][8] k_pose phase clocks (COEB_POSE_CLOCK builds) / [F][16] k_match phase clocks (COEB_MATCH_CLOCK builds)
         const DevArr<long long>& t = what[0] == 'p' ? c->tim.p_timing : c->tim.m_timing;
         if (!t.p) return COEB_EINVAL;
         if (size_out) *size_out = t.bytes;

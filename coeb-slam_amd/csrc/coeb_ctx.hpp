@@ -88,7 +88,7 @@ struct SingleFrameBufs {    // coeb_match_lastframe (m_*), _localmap / _keyframe
     DevArr<double> p_chi{"p_chi"};
     auto all() { return std::tie(m_scr, m_qn, l_out, l_path, l_list, p_act, p_edge, p_chi); }
 };
-struct TimingBufs {         // diagnostic phase clocks (COEB_MATCH_TIMING / COEB_POSE_TIMING)
+struct TimingBufs {         // diagnostic phase clocks (COEB_MATCH_CLOCK / COEB_POSE_CLOCK builds)
     DevArr<long long> m_timing{"m_timing"}, p_timing{"p_timing"};
     auto all() { return std::tie(m_timing, p_timing); }
 };
@@ -195,10 +195,9 @@ struct coeb_ctx {
     // coeb_synchronize and coeb_destroy join it (join_pose()).
     hipStream_t pose_stream = nullptr;
     // level-0 blur + FAST beside the pyramid (launch_extract's SideStream); COEB_SIDE_STREAM=0 disables
-    SideStream side{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 2, true, false};
+    SideStream side{};
     bool side_init = false;
     bool side_shared = false;                 // side.s is the device's shared side stream
-    hipEvent_t ev_ffork = nullptr, ev_fjoin = nullptr;   // the moving-object batch's LK-pyramid fork / join
     hipEvent_t ev_tprep = nullptr, ev_pose = nullptr;
     bool pose_pending = false;
     // batch tracking state: Observations() the matcher gave the LastFrame points, the frames and

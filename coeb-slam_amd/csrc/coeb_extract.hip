@@ -1138,9 +1138,6 @@ __host__ __device__ inline int fast_wave_lds(const Plan& P, int rb)
     return kFastGuard + fast_slab(P, rb) + fast_ms_slab(P, rb) + 2 * (kFastLists + kFastCorners + kFastEnt);
 }
 
-#ifndef COEB_FAST_CLOCK
-#define COEB_FAST_CLOCK 0      // experiment builds: per-cell k_fast phase clocks (fast_timing)
-#endif
 #define FC_MARK(v) long long v = COEB_FAST_CLOCK ? (long long)clock64() : 0
 // per-cell slots spread over 256 copies (blockIdx.x & 255) so the counters do not contend
 __device__ unsigned long long g_fast_clk[256 * 8];
@@ -1579,9 +1576,6 @@ __device__ __forceinline__ void child_rect(const int4 p, int q, int4* out, int* 
     else *out = make_int4(mx, my, p.z, p.w);
 }
 
-#ifndef COEB_OCT_CLOCK
-#define COEB_OCT_CLOCK 0       // experiment builds: per-workgroup k_octree clocks (oct_timing)
-#endif
 // [wg][6]: level, K (candidates), start (wall clock), cycles: total, gather + initial nodes, main loop
 __device__ long long g_oct_clk[4096 * 6];
 
@@ -2554,10 +2548,10 @@ int launch_extract(const Plan& plan, const Plan* d_plan, const ExtractBufs& b, i
         prof_end(prof, st);
     };
     // level 0 (the input frame itself) needs no pyramid: with a side stream its blur and FAST
-    // overlap the cascaded pyramid launches, whose small late levels leave most CUs idle; levels
-    // 1..m-1 follow on the side stream as soon as the pyramid has built them
+    // overlap the cascaded pyramid launches, whose small late levels leave most CUs idle; level 1
+    // follows on the side stream as soon as the pyramid has built it
     const bool split = side && side->s && plan.L > 1;
-    const int m = split ? std::min(std::max(side->split, 1), plan.L) : 0;
+    const int m = split ? 2 : 0;        // the first level left to s
     if (split) {
         (void)hipEventRecord(side->fork, s);                 // after k_dynmask (area_flag -> FAST thresholds)
         (void)hipStreamWaitEvent(side->s, side->fork, 0);
@@ -2586,7 +2580,7 @@ int launch_extract(const Plan& plan, const Plan* d_plan, const ExtractBufs& b, i
                                g.pitch, g.w, g.h, b.rtab + g.rtab_off, g.xmax, resize_simd_end(g.w), tsw, tsh);
         }
         prof_end(prof, s);
-        if (split && m > 1 && l == m - 1) {
+        if (split && l == m - 1) {
             (void)hipEventRecord(side->mid, s);
             (void)hipStreamWaitEvent(side->s, side->mid, 0);
             blur(side->s, bw.item_off[1], bw.item_off[m]);
@@ -2608,7 +2602,6 @@ int launch_extract(const Plan& plan, const Plan* d_plan, const ExtractBufs& b, i
         oct_kl = kl;
         oct_lds = plan.oct_w * (4 + 16 + 4 + 4 + 4 + 1 + 64) + 8 * kl;
     }
-    if (const char* e = coeb_experiment("COEB_OCT_KL_SMALL")) if (atoi(e) == 0) { oct_kl = plan.oct_kl; oct_lds = plan.oct_lds; }
     lds_limit_max((const void*)k_octree<kOctThreads>);
     auto octree = [&](hipStream_t st, int l0, int l1) {
         if (l1 <= l0) return;
@@ -2617,31 +2610,21 @@ int launch_extract(const Plan& plan, const Plan* d_plan, const ExtractBufs& b, i
                            oct_kl);
         prof_end(prof, st);
     };
-    // the late blur goes to the side stream (beside FAST / octree, which do not read it) and the
-    // octree of the side levels follows their FAST there; s joins before the descriptors
-    const bool late = split && side->blur_late;
-    const bool soct = late && side->side_octree;
-    if (soct) octree(side->s, 0, m);
-    if (split) (void)hipEventRecord(side->join, side->s);
-    if (late) {
+    // the late blur goes to the side stream, beside FAST on s, which does not read it
+    if (split) {
         (void)hipEventRecord(side->pyr_done, s);
         (void)hipStreamWaitEvent(side->s, side->pyr_done, 0);
         blur(side->s, bw.item_off[m], items);
-        (void)hipEventRecord(side->join2, side->s);
+        (void)hipEventRecord(side->join, side->s);
     } else {
-        blur(s, split ? bw.item_off[m] : 0, items);
+        blur(s, 0, items);
     }
-    fast(s, split ? m : 0, plan.L);
+    fast(s, m, plan.L);
     // one cross-stream wait on the critical path instead of two: each costs a ~6 us gap between
     // the launches it separates (rocprofv3 timeline), and the late blur ends well before FAST
-    // does, so waiting for all of the side stream (join2) before the octree delays nothing
-    if (soct) {
-        octree(s, m, plan.L);
-        (void)hipStreamWaitEvent(s, late ? side->join2 : side->join, 0);
-    } else {
-        if (split) (void)hipStreamWaitEvent(s, late ? side->join2 : side->join, 0);
-        octree(s, 0, plan.L);
-    }
+    // does, so waiting for all of the side stream before the octree delays nothing
+    if (split) (void)hipStreamWaitEvent(s, side->join, 0);
+    octree(s, 0, plan.L);
     prof_begin(prof, "k_describe", s);
     const bool vec0 = plan.W % 16 == 0 && (reinterpret_cast<uintptr_t>(b.gray) & 15) == 0;
     // COEB_DESC_KP keypoints per wave (round 1's 32 let one XCD's resident waves span ~20 frames

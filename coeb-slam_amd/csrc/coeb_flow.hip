@@ -39,8 +39,6 @@
 
 namespace {
 
-__device__ int g_subpix_count_dev[4];   // {cornerSubPix iterations, corners, LK iterations, points}
-int* g_subpix_count = nullptr;    // device address of g_subpix_count_dev (COEB_SUBPIX_COUNT, A/B tool)
 
 constexpr int kMaxPts = 1024;        // corners / tracked points per call (reference: 1000)
 // k_gf_select's workgroup: 256 threads (a config-D pair has ~270 local maxima: its sort stages and
@@ -520,7 +518,7 @@ __global__ __launch_bounds__(64) void k_subpix(const uint8_t* __restrict__ img0,
                                                   float* __restrict__ xy0, const int* __restrict__ offs, int P,
                                                   const int* __restrict__ order, int* __restrict__ queue,
                                                   const float* __restrict__ mexp, int iters, double eps2, int64_t iz,
-                                                  int64_t pz, int* __restrict__ itcount)
+                                                  int64_t pz)
 {
     constexpr int WIN = 10, WW = 2 * WIN + 1, BW = WW + 2, NJ = (BW + 1) / 2;
     constexpr int NF = (G * NJ + 63) / 64, NT = (G * WW + 63) / 64, NL = 5 * G;
@@ -555,7 +553,6 @@ __global__ __launch_bounds__(64) void k_subpix(const uint8_t* __restrict__ img0,
     }
     // slot state on lane g < G
     int item = -1, it = 0, pidx = 0;
-    int nit = 0, ncorner = 0;                          // wave totals (COEB_SUBPIX_COUNT)
     float tx = 0.f, ty = 0.f, cx = 0.f, cy = 0.f;
     float* xy = nullptr;
     const uint8_t* simg = nullptr;
@@ -582,11 +579,9 @@ __global__ __launch_bounds__(64) void k_subpix(const uint8_t* __restrict__ img0,
                 }
                 need = false;
             }
-            ncorner += __popcll(__ballot(lane < G && item >= 0) & nm);
         }
         const uint64_t am = __ballot(lane < G && item >= 0);
         if (!am) break;
-        nit += __popcll(am);
         if (lane < G) {
             SpSlot sl;
             sl.img = item >= 0 ? simg : img0;           // idle slots: a valid address for the fill loads
@@ -740,7 +735,6 @@ __global__ __launch_bounds__(64) void k_subpix(const uint8_t* __restrict__ img0,
         }
         wave_order();
     }
-    if (itcount && lane == 0) { atomicAdd(itcount, nit); atomicAdd(itcount + 1, ncorner); }
 }
 
 // cornerSubPix work order: the corners whose window may leave the image (getRectSubPix's
@@ -982,7 +976,7 @@ __device__ __forceinline__ void tile_pairs_reflect(const uint8_t* img, int pitch
 #endif
 __global__ __launch_bounds__(256, COEB_LK_MINW) void k_lk(LkPyr pyr, const float* __restrict__ pxy0, const int* __restrict__ offs, int P,
                                             float* __restrict__ nxy0, uint8_t* __restrict__ status0, int win, int max_count,
-                                            double eps2, int64_t iz, int64_t pz, int* __restrict__ itcount)
+                                            double eps2, int64_t iz, int64_t pz)
 {
     const int lane = threadIdx.x & 63;
     const int R0 = (lane >> 3) * 3, C0 = (lane & 7) * 3;
@@ -1007,7 +1001,6 @@ __global__ __launch_bounds__(256, COEB_LK_MINW) void k_lk(LkPyr pyr, const float
     float nx = 0.f, ny = 0.f;
     const float px0 = pxy[2 * p], py0 = pxy[2 * p + 1];
     int gxv[9], gyv[9];
-    int nit = 0;
     for (int level = pyr.L - 1; level >= 0; level--) {
         const int lw = pyr.w[level], lh = pyr.h[level], pitch = pyr.pitch[level];
         const uint8_t* I = at_pair(pyr.P[level], level == 0 ? iz : pz, z);
@@ -1081,7 +1074,6 @@ __global__ __launch_bounds__(256, COEB_LK_MINW) void k_lk(LkPyr pyr, const float
         float lx = nx - hw, ly = ny - hw;
         float pdx = 0.f, pdy = 0.f;
         for (int j = 0; j < max_count; j++) {
-            nit++;
             const int inx = cv_floor(lx), iny = cv_floor(ly);
             if (inx < -win || inx >= lw || iny < -win || iny >= lh) {
                 if (level == 0) st = 0;
@@ -1127,7 +1119,6 @@ __global__ __launch_bounds__(256, COEB_LK_MINW) void k_lk(LkPyr pyr, const float
         nxy[2 * p] = nx;
         nxy[2 * p + 1] = ny;
         status[p] = (uint8_t)st;
-        if (itcount) { atomicAdd(itcount + 2, nit); atomicAdd(itcount + 3, 1); }
     }
     }
 }
@@ -1917,11 +1908,6 @@ int launch_subpix(const FlowDev* d, const uint8_t* img, int w, int h, int stride
 {
     const int iters = max_iter < 1 ? 1 : max_iter > 100 ? 100 : max_iter;
     const double e = eps > 0 ? eps : 0.;
-    int* itc = nullptr;
-    if (coeb_experiment("COEB_SUBPIX_COUNT")) {
-        if (!g_subpix_count) (void)hipGetSymbolAddress((void**)&g_subpix_count, HIP_SYMBOL(g_subpix_count_dev));
-        itc = g_subpix_count;
-    }
     launch_flow_index(d, s);
     (void)hipMemsetAsync(d->ocnt, 0, 12, s);            // {interior, border, corner queue}
     // interior: the window (23 x 23 around the corner, +1 for the interpolation) stays inside the
@@ -1929,16 +1915,16 @@ int launch_subpix(const FlowDev* d, const uint8_t* img, int w, int h, int stride
     hipLaunchKernelGGL(k_subpix_order, dim3(flow_grid(d, 256)), dim3(256), 0, s, d->pts, d->offs, d->npairs, w, h, 14,
                        d->pz, d->order, d->ocnt);
     FLOW_LAUNCH(d, "k_subpix", s, k_subpix<kSpSlots>, dim3(flow_grid(d, 8 * kSpSlots)), dim3(64), 0, s, img, w, h, stride,
-                d->pts, d->offs, d->npairs, d->order, d->ocnt + 2, d->mexp, iters, e * e, iz, d->pz, itc);
+                d->pts, d->offs, d->npairs, d->order, d->ocnt + 2, d->mexp, iters, e * e, iz, d->pz);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// LK pyramids of both frames (pyrDown levels and the Scharr derivatives of every level): they read
-// only the images, so a batch builds them on a second stream beside goodFeaturesToTrack and
-// cornerSubPix (pmo_batch); `pyr` is filled for launch_lk_track.
-int launch_lk_pyramids(const FlowDev* d, const uint8_t* prev, const uint8_t* cur, int w, int h, int stride, int win,
-                       int max_level, hipStream_t s, int64_t iz, LkPyr& pyr)
+// calcOpticalFlowPyrLK: the pyramids of both frames (pyrDown levels and the Scharr derivatives of
+// every level), then the LK iterations on them
+int launch_lk(const FlowDev* d, const uint8_t* prev, const uint8_t* cur, int w, int h, int stride, int win,
+              int max_level, int max_count, double eps, hipStream_t s, int64_t iz = 0)
 {
+    LkPyr pyr;
     const int P = d->npairs;
     memset(&pyr, 0, sizeof(pyr));
     const int L = lk_levels(w, h, win, max_level);
@@ -1970,32 +1956,10 @@ int launch_lk_pyramids(const FlowDev* d, const uint8_t* prev, const uint8_t* cur
     }
     const int sh_items = ((w + kShCols - 1) / kShCols) * ((h + kShRows - 1) / kShRows);   // level 0 is the largest
     FLOW_LAUNCH(d, "k_sharr", s, k_sharr, dim3((sh_items + 3) / 4, L, P), dim3(256), 0, s, pyr, iz, d->pz);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// The LK iterations on the pyramids launch_lk_pyramids built (ordered before this on `s`).
-int launch_lk_track(const FlowDev* d, const LkPyr& pyr, int win, int max_count, double eps, hipStream_t s,
-                    int64_t iz)
-{
-    const int P = d->npairs;
     launch_flow_index(d, s);            // the host LK entry point sets npts without cornerSubPix
-    int* itc = nullptr;
-    if (coeb_experiment("COEB_SUBPIX_COUNT")) {
-        if (!g_subpix_count) (void)hipGetSymbolAddress((void**)&g_subpix_count, HIP_SYMBOL(g_subpix_count_dev));
-        itc = g_subpix_count;
-    }
     FLOW_LAUNCH(d, "k_lk", s, k_lk, dim3(flow_grid(d, 4)), dim3(256), 0, s, pyr, d->pts, d->offs, P, d->nxt,
-                d->status, win, max_count, eps * eps, iz, d->pz, itc);
+                d->status, win, max_count, eps * eps, iz, d->pz);
     return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_lk(const FlowDev* d, const uint8_t* prev, const uint8_t* cur, int w, int h, int stride, int win,
-              int max_level, int max_count, double eps, hipStream_t s, int64_t iz = 0)
-{
-    LkPyr pyr;
-    const int rc = launch_lk_pyramids(d, prev, cur, w, h, stride, win, max_level, s, iz, pyr);
-    if (rc) return rc;
-    return launch_lk_track(d, pyr, win, max_count, eps, s, iz);
 }
 
 int launch_fm(const FlowDev* d, const uint8_t* prev, const uint8_t* cur, int w, int h, int stride, int edge, double limit,
@@ -2178,19 +2142,6 @@ extern "C" int coeb_moving_object_points(coeb_ctx* c, const uint8_t* prev, const
     return coeb_moving_object_points_device(c, fc.d.prev, fc.d.cur, w, h, w, tm_xy, tm_cap, n_tm, dbg);
 }
 
-// Frame::ProcessMovingObject for every consecutive pair of a device-resident batch (the Frame
-// constructor's T_M, Frame.cc:164-166): pair f-1 = frames (f-1, f) of d_gray (packed, w x h),
-// T_M of frame f into tm_out + f * tm_cap * 2 floats, |T_M| (or -1: F empty) into ntm_out[f];
-// ntm_out[0] = 0 (no previous frame).  Enqueued on the context stream, no synchronisation.
-// A/B tool hook: {iterations, corners} counted by the cornerSubPix variants under
-// COEB_SUBPIX_COUNT since the last read (then reset)
-extern "C" int coeb_internal_subpix_count(int* out)
-{
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_subpix_count_dev), 16) != hipSuccess) return COEB_EDEVICE;
-    const int z[4] = {0, 0, 0, 0};
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_subpix_count_dev), z, 16) == hipSuccess ? COEB_OK : COEB_EDEVICE;
-}
-
 // Per pair of the context's last moving-object batch: {Harris candidate keys, corners} (bench.py's
 // algorithmic bytes of k_gf_select / k_subpix / k_lk / k_fm).  Synchronises the context stream.
 int flow_counts(coeb_ctx* c, int* out, int cap, int* npairs)
@@ -2211,26 +2162,10 @@ int flow_counts(coeb_ctx* c, int* out, int cap, int* npairs)
     return COEB_OK;
 }
 
-// The side stream for the moving-object batch's LK pyramids, with the context's fork / join events
-// (created on first use), when COEB_FLOW_SIDE=1; null otherwise (also with the side stream off
-// or per-kernel profiling), and then everything stays on the context stream.  Off by default: config
-// D's step measured 13.30-13.37 ms with the fork against 13.10-13.30 without (profiles/r05/s24): the
-// step is bound by the kernels' combined demand for CUs, not by the context stream's chain.
-static hipStream_t flow_side(coeb_ctx* c)
-{
-    const char* e = coeb_experiment("COEB_FLOW_SIDE");
-    if (!(e && e[0] == '1')) return nullptr;
-    const SideStream* sd = side_stream(c);
-    if (!sd) return nullptr;
-    if (!c->ev_ffork && (hipEventCreateWithFlags(&c->ev_ffork, hipEventDisableTiming) != hipSuccess ||
-                         hipEventCreateWithFlags(&c->ev_fjoin, hipEventDisableTiming) != hipSuccess)) {
-        if (c->ev_ffork) (void)hipEventDestroy(c->ev_ffork);
-        c->ev_ffork = c->ev_fjoin = nullptr;
-        return nullptr;
-    }
-    return sd->s;
-}
-
+// Frame::ProcessMovingObject for every consecutive pair of a device-resident batch (the Frame
+// constructor's T_M, Frame.cc:164-166): pair f-1 = frames (f-1, f) of d_gray (packed, w x h),
+// T_M of frame f into tm_out + f * tm_cap * 2 floats, |T_M| (or -1: F empty) into ntm_out[f];
+// ntm_out[0] = 0 (no previous frame).  Enqueued on the context stream, no synchronisation.
 int pmo_batch(coeb_ctx* c, const uint8_t* d_gray, int F, int w, int h, float* tm_out, int* ntm_out, int tm_cap)
 {
     if (F < 1 || !d_gray || !tm_out || !ntm_out || tm_cap < 1 || tm_cap > kMaxPts)
@@ -2249,25 +2184,12 @@ int pmo_batch(coeb_ctx* c, const uint8_t* d_gray, int F, int w, int h, float* tm
     subpix_mask(10, mask);
     FL_TRY(c, hipMemcpyAsync(fc.d.mexp, mask, kSubpixMaskBytes, hipMemcpyHostToDevice, fc.s));
     const int64_t iz = (int64_t)w * h;
-    // COEB_FLOW_SIDE=1: the LK pyramids go to the context's side stream (idle until extraction)
-    // beside the corner detection, and the context stream joins them before k_lk (measured slower)
-    hipStream_t side = flow_side(c);
-    hipEvent_t fork = c->ev_ffork, join = c->ev_fjoin;
-    const bool split = side != nullptr;
-    LkPyr pyr;
-    if (split) {
-        FL_TRY(c, hipEventRecord(fork, fc.s));
-        FL_TRY(c, hipStreamWaitEvent(side, fork, 0));
-        if (launch_lk_pyramids(&fc.d, d_gray, d_gray + iz, w, h, w, 22, 5, side, iz, pyr))
-            return set_err(c, COEB_EDEVICE, "moving-object batch: launch failed");
-        FL_TRY(c, hipEventRecord(join, side));
-    }
+    // (the LK pyramids forked onto the extraction's side stream beside the corner detection:
+    // config D's step 13.30-13.37 ms against 13.10-13.30, profiles/r05/s24; the step is bound by
+    // the kernels' combined demand for CUs, not by the context stream's chain)
     if (launch_gf(&fc.d, d_gray, w, h, w, 1000, 0.01, 8.0, 0.04, fc.s, iz) ||
-        launch_subpix(&fc.d, d_gray, w, h, w, 20, 0.03, fc.s, iz))
-        return set_err(c, COEB_EDEVICE, "moving-object batch: launch failed");
-    if (split) FL_TRY(c, hipStreamWaitEvent(fc.s, join, 0));
-    if ((split ? launch_lk_track(&fc.d, pyr, 22, 20, 0.01, fc.s, iz)
-               : launch_lk(&fc.d, d_gray, d_gray + iz, w, h, w, 22, 5, 20, 0.01, fc.s, iz)) ||
+        launch_subpix(&fc.d, d_gray, w, h, w, 20, 0.03, fc.s, iz) ||
+        launch_lk(&fc.d, d_gray, d_gray + iz, w, h, w, 22, 5, 20, 0.01, fc.s, iz) ||
         launch_fm(&fc.d, d_gray, d_gray + iz, w, h, w, 5, 2120.0, fc.s, tm_cap, iz, tm_out + (size_t)tm_cap * 2,
                   ntm_out + 1))
         return set_err(c, COEB_EDEVICE, "moving-object batch: launch failed");

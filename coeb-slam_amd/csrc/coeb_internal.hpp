@@ -24,18 +24,25 @@
 #include "coeb_plan.hpp"     // LevelGeom, Plan, CellDesc: the geometry the kernels take as arguments
 
 // Runtime switches, the only environment reads of the library (coeb_capi.hip):
-//  * coeb_switch(name): a product switch -- one of kSwitches, each run by the GPU test suite
-//    against the oracle (side-stream modes, the matcher's sequential / split forms, the
-//    pyramid's byte form, the general FAST slab layout, k_fm's threads per pair);
-//  * coeb_experiment(name): a measurement-only switch (schedules and kernel forms measured and
-//    not kept, diagnostic clocks), read only when COEB_EXPERIMENTS=1, so a stray variable in a
-//    caller's environment cannot route the shipped library through an untested path.
-// Both return the value or nullptr.
+// coeb_switch(name) returns the value of a product switch -- one of kSwitches, each run by the
+// GPU test suite against the oracle (side-stream modes, the matcher's sequential / split forms,
+// the pyramid's byte form, the general FAST slab layout, k_fm's threads per pair) -- or nullptr;
+// a name that is no product switch is never read.
 const char* coeb_switch(const char* name);
-const char* coeb_experiment(const char* name);
 
+// Diagnostic phase clocks, compiled in only by the tools' own builds (-DCOEB_*_CLOCK=1): the
+// product build has no hook.  A clock build fills its timing buffer on every launch.
+#ifndef COEB_FAST_CLOCK
+#define COEB_FAST_CLOCK 0      // per-cell k_fast phase clocks (fast_timing)
+#endif
+#ifndef COEB_OCT_CLOCK
+#define COEB_OCT_CLOCK 0       // per-workgroup k_octree clocks (oct_timing)
+#endif
 #ifndef COEB_MATCH_CLOCK
-#define COEB_MATCH_CLOCK 0     // experiment builds: k_match phase clocks (COEB_MATCH_TIMING, tools/_match_timing.py)
+#define COEB_MATCH_CLOCK 0     // k_match phase clocks (match_timing, tools/_match_timing.py)
+#endif
+#ifndef COEB_POSE_CLOCK
+#define COEB_POSE_CLOCK 0      // k_pose phase clocks (pose_timing, tools/_pose_timing.py)
 #endif
 
 // Raise a kernel's dynamic-LDS limit once per (kernel, device), to the most any launch may use
@@ -165,12 +172,9 @@ void prof_begin(ProfileHook* p, const char* name, hipStream_t s);
 void prof_end(ProfileHook* p, hipStream_t s);
 
 // side (optional): blur + FAST of level 0 run on side.s while the pyramid builds levels 1..;
-// those of levels 1..split-1 follow there once the pyramid has built them, and s does levels
-// split..L-1 after the pyramid; s joins side.s before the octree.
-// With blur_late, the blur of levels split..L-1 also runs on side.s (after the pyramid, beside
-// FAST and the octree on s); s then joins it (join2) only before the descriptors.
-// With side_octree, the octree of levels < split follows their FAST on side.s.
-struct SideStream { hipStream_t s; hipEvent_t fork, mid, join, pyr_done, join2; int split; bool blur_late, side_octree; };
+// those of level 1 follow there once the pyramid has built it, and s does FAST of levels 2..L-1
+// after the pyramid, beside their blur on side.s; s joins side.s before the octree.
+struct SideStream { hipStream_t s; hipEvent_t fork, mid, pyr_done, join; };
 int launch_extract(const Plan& plan, const Plan* d_plan, const ExtractBufs& b, int F, hipStream_t s,
                    ProfileHook* prof, const SideStream* side = nullptr);
 
@@ -211,27 +215,29 @@ struct MatchBufs {
     int scratch_stride;
     int* qn;                   // optional [P][qn_stride >= last_stride + kMaxSplit]: split-list counts + flags
     int qn_stride;
-    long long* timing;         // optional [P][16] phase clocks (COEB_MATCH_TIMING), else nullptr
+    long long* timing;         // [P][16] phase clocks (COEB_MATCH_CLOCK builds), else nullptr
     int* err;
 };
 int launch_match(const MatchCam& cam, const MatchBufs& b, int P, float th, int bmono, int check_ori,
                  int retry_below, hipStream_t s, ProfileHook* prof);
 
 // local-map projection search (ORBmatcher::SearchByProjection(Frame&, vector<MapPoint*>, th))
-struct LocalBufsHost {
+// (k_match_local and k_match_kf take LocalBufs / KfBufs by value: the field order is their argument layout)
+struct LocalBufs {
     const void* cur_kps; const uint8_t* cur_desc; const float* cur_ur; const int* cur_obs; int cur_n;
     const uint8_t* in_view; const float* proj_x; const float* proj_y; const float* proj_xr;
     const int* level; const float* view_cos; const uint8_t* desc; const int* nobs; int mp_n;
     int* match; int* nmatch; uint32_t* lists; int* err;
     int* path;   // [0]: 0 parallel claims, 1 forced sequential, 2 list overflow, 3 no convergence; [1]: iterations
     // batch form: npairs workgroups, pair p reads cur_* + p*cur_stride (keypoint count
-    // cur_n_arr[p]), the local-map arrays + p*mp_n, desc + p*mp_desc_stride*32, lists + p*mp_n*kCQ,
-    // and writes match + p*cur_stride, nmatch[p], path[2p..]; active[p] == 0 skips the pair
-    // (no matches).  cur_n_arr == null: the single search above.
+    // cur_n_arr[p]), the local-map arrays + p*mp_stride, desc + p*mp_desc_stride*32,
+    // lists + p*mp_stride*kCQ, and writes match + p*cur_stride, nmatch[p], path[2p..];
+    // active[p] == 0 skips the pair (no matches).  cur_n_arr == null: the single search above.
     const int* cur_n_arr = nullptr; const uint8_t* active = nullptr;
-    int npairs = 1, cur_stride = 0, mp_desc_stride = 0;
+    int cur_stride = 0, mp_stride = 0, mp_desc_stride = 0;
+    int npairs = 1;   // read by the launcher only
 };
-int launch_match_local(const MatchCam& cam, const LocalBufsHost& b, float th, float nnratio, hipStream_t s,
+int launch_match_local(const MatchCam& cam, const LocalBufs& b, float th, float nnratio, hipStream_t s,
                        ProfileHook* prof);
 
 // Optimizer::PoseOptimization (coeb_pose.hip): per frame f, keypoints [f][stride]
@@ -250,7 +256,7 @@ struct PoseBufs {
     uint8_t* active;              // scratch [F][stride]
     double* chi2;                 // scratch [F][stride]
     int stride;
-    long long* timing;            // optional [F][8] phase clocks (COEB_POSE_TIMING), else null
+    long long* timing;            // [F][8] phase clocks (COEB_POSE_CLOCK builds), else null
 };
 int launch_pose(const PoseBufs& b, int F, double fx, double fy, double cx, double cy, double bf, hipStream_t s,
                 ProfileHook* prof);
@@ -305,15 +311,15 @@ int launch_tlm_frustum(const MatchCam& cam, const TlmBufs& t, int F, hipStream_t
 int launch_tlm_pose_prep(const TlmBufs& t, int F, hipStream_t s, ProfileHook* prof);
 
 // relocalisation projection search (ORBmatcher::SearchByProjection(Frame&, KeyFrame*, set, th, ORBdist))
-struct KfBufsHost {
+struct KfBufs {
     const void* cur_kps; const uint8_t* cur_desc; const uint8_t* cur_has; int cur_n;
     const uint8_t* valid; const float* xw; const uint8_t* desc; const float* maxd; const float* mind;
     const float* angle; int kf_n;
     const float* Tcw;   // device, 16 floats row-major
     int* match; int* nmatch; uint32_t* lists; int* err;
-    int* path;          // as LocalBufsHost::path
+    int* path;          // as LocalBufs::path
 };
-int launch_match_kf(const MatchCam& cam, const KfBufsHost& b, float th, int orb_dist, int check_ori, hipStream_t s,
+int launch_match_kf(const MatchCam& cam, const KfBufs& b, float th, int orb_dist, int check_ori, hipStream_t s,
                     ProfileHook* prof);
 
 // frame preparation for batch matching: u_right/depth per keypoint + LastFrame map snapshot

@@ -801,7 +801,7 @@ __global__ __launch_bounds__(NT, COEB_MATCH_MINWG) void k_match(MatchArgs args)
     cv.kp = L.kp; cv.desc = L.desc; cv.gkp = cur; cv.gur = cur_ur; cv.gdesc = cdesc;
 
     // ---- phase 0: stage CurrentFrame, grid CSR by a stable counting sort ----
-    // phase clocks: experiment builds only (-DCOEB_MATCH_CLOCK=1 with COEB_MATCH_TIMING set,
+    // phase clocks: experiment builds only (-DCOEB_MATCH_CLOCK=1,
     // tools/_match_timing.py); the product build has no hook (14 SGPRs)
     long long* tm = COEB_MATCH_CLOCK && b.timing ? b.timing + (int64_t)p * 16 : nullptr;
     if (tm && tid == 0) { tm[0] = clock64(); tm[13] = 0; tm[14] = 0x7fffffffffffffffll; tm[15] = 0; }
@@ -902,15 +902,6 @@ __global__ __launch_bounds__(NT, COEB_MATCH_MINWG) void k_match(MatchArgs args)
 //            Jacobi fixpoint as k_match (owner[c] = min such p), reaching the sequential answer
 //   phase 3  the last point assigned to a keypoint wins (F.mvpMapPoints[bestIdx] = pMP)
 // Overflowing lists or no convergence run the literal loop instead.
-struct LocalBufs {
-    const void* cur_kps; const uint8_t* cur_desc; const float* cur_ur; const int* cur_obs; int cur_n;
-    const uint8_t* in_view; const float* proj_x; const float* proj_y; const float* proj_xr;
-    const int* level; const float* view_cos; const uint8_t* desc; const int* nobs; int mp_n;
-    int* match; int* nmatch; uint32_t* lists; int* err; int* path;
-    // batch form (cur_n_arr != null): workgroup p searches frame p's arrays (LocalBufsHost)
-    const int* cur_n_arr; const uint8_t* active; int cur_stride, mp_stride, mp_desc_stride;
-};
-
 // workgroup p's view of a batch launch
 __device__ __forceinline__ LocalBufs local_at_pair(LocalBufs b, int p)
 {
@@ -1226,14 +1217,6 @@ __global__ __launch_bounds__(NT) void k_match_local(MatchCam cam, LocalBufs b0, 
 // [level-1, level+1], no stereo check.  A keypoint holding any MapPoint (at entry or given
 // earlier in this call) is skipped (:1545-1546), so every assignment blocks later points: the
 // same fixpoint as k_match with every query blocking.  Then the rotation histogram.
-struct KfBufs {
-    const void* cur_kps; const uint8_t* cur_desc; const uint8_t* cur_has; int cur_n;
-    const uint8_t* valid; const float* xw; const uint8_t* desc; const float* maxd; const float* mind;
-    const float* angle; int kf_n;
-    const float* Tcw;
-    int* match; int* nmatch; uint32_t* lists; int* err; int* path;
-};
-
 // MapPoint::PredictScale(dist, Frame*) (MapPoint.cc:402-417); log canonical as in the oracle
 __device__ __forceinline__ int predict_scale(const MatchCam& cam, float max_dist, float dist)
 {
@@ -1451,24 +1434,20 @@ int launch_match(const MatchCam& cam, const MatchBufs& b, int P, float th, int b
     bool lds_cur = lds_full <= 160 * 1024;
     if (!lds_cur && lds_min > 160 * 1024) return -2;
     if (nsplit) {
-        // the lists kernel stages the current frame in LDS (COEB_MATCH_LISTS_LDS=0: reads it from
-        // global memory); k_match then needs no staged frame (its phases 0-1 run only for the
-        // sequential fallback / the retry, then reading the frame from global memory), so it takes
-        // a fraction of the LDS and leaves the CU to the other pipeline's kernels
-        // (COEB_MATCH_SPLIT_FULL=1 keeps the staged form)
-        const char* le = coeb_experiment("COEB_MATCH_LISTS_LDS");
-        const bool lists_lds = lds_cur && !(le && atoi(le) == 0);
-        const size_t lds_l = match_lds_bytes(b.cur_stride, 0, lists_lds, nullptr);
+        // the lists kernel stages the current frame in LDS where it fits; k_match then needs no
+        // staged frame (its phases 0-1 run only for the sequential fallback / the retry, then
+        // reading the frame from global memory), so it takes a fraction of the LDS and leaves the
+        // CU to the other pipeline's kernels
+        const size_t lds_l = match_lds_bytes(b.cur_stride, 0, lds_cur, nullptr);
         auto gl = [&](auto kern) {
             lds_limit_max((const void*)kern);
             hipLaunchKernelGGL(kern, dim3(P, nsplit), dim3(1024), lds_l, s, cam, b, th, bmono);
         };
         prof_begin(prof, "k_match_lists", s);
-        if (lists_lds) gl(k_match_lists<true, 1024>);
+        if (lds_cur) gl(k_match_lists<true, 1024>);
         else gl(k_match_lists<false, 1024>);
         prof_end(prof, s);
-        const char* fe = coeb_experiment("COEB_MATCH_SPLIT_FULL");
-        if (!(fe && atoi(fe) != 0)) lds_cur = false;
+        lds_cur = false;
     }
     auto go = [&](auto kern, size_t lds) {
         lds_limit_max((const void*)kern);
@@ -1487,26 +1466,16 @@ int launch_match(const MatchCam& cam, const MatchBufs& b, int P, float th, int b
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int launch_match_local(const MatchCam& cam, const LocalBufsHost& h, float th, float nnratio, hipStream_t s, ProfileHook* prof)
+int launch_match_local(const MatchCam& cam, const LocalBufs& b, float th, float nnratio, hipStream_t s, ProfileHook* prof)
 {
-    LocalBufs b;
-    b.cur_kps = h.cur_kps; b.cur_desc = h.cur_desc; b.cur_ur = h.cur_ur; b.cur_obs = h.cur_obs; b.cur_n = h.cur_n;
-    b.in_view = h.in_view; b.proj_x = h.proj_x; b.proj_y = h.proj_y; b.proj_xr = h.proj_xr; b.level = h.level;
-    b.view_cos = h.view_cos; b.desc = h.desc; b.nobs = h.nobs; b.mp_n = h.mp_n;
-    b.match = h.match; b.nmatch = h.nmatch; b.lists = h.lists; b.err = h.err; b.path = h.path;
-    b.cur_n_arr = h.cur_n_arr; b.active = h.active;
-    b.cur_stride = h.cur_stride; b.mp_stride = h.mp_n; b.mp_desc_stride = h.mp_desc_stride;
-    const int P = h.cur_n_arr ? h.npairs : 1;
+    const int P = b.cur_n_arr ? b.npairs : 1;
     if (P <= 0) return 0;
-    if (h.cur_n_arr && h.cur_stride >= (1 << kIdxBits)) return -2;
+    if (b.cur_n_arr && b.cur_stride >= (1 << kIdxBits)) return -2;
     const int force_seq = coeb_switch("COEB_MATCH_SEQUENTIAL") ? 1 : 0;
-    const int cs = std::max(h.cur_n_arr ? h.cur_stride : h.cur_n, 1), qs = std::max(h.mp_n, 1);
+    const int cs = std::max(b.cur_n_arr ? b.cur_stride : b.cur_n, 1), qs = std::max(b.mp_n, 1);
     const size_t lds_full = match_lds_bytes(cs, qs, true, nullptr) + 256;
     const size_t lds_min = match_lds_bytes(cs, qs, false, nullptr) + 256;
     prof_begin(prof, "k_match_local", s);
-    // COEB_LOCAL_LDS=0: the current frame read from global memory (a third of the LDS, so the
-    // workgroup finds room beside the pose and flow kernels sooner)
-    const char* le = coeb_experiment("COEB_LOCAL_LDS");
     // a batch (the configs[4] loop's TrackLocalMap) takes 512 threads per frame: the kernel alone
     // runs longer (0.78 vs 0.51 ms per 1537 frames) but leaves room to the pose / flow kernels it
     // overlaps, and the config-D step is shorter (35.11 vs 35.45-35.60 ms, profiles/r06/s8); one
@@ -1520,7 +1489,7 @@ int launch_match_local(const MatchCam& cam, const LocalBufsHost& h, float th, fl
             hipLaunchKernelGGL(k1024, dim3(P), dim3(1024), lds - 256, s, cam, b, th, nnratio, force_seq);
         }
     };
-    if (lds_full <= 160 * 1024 && !(le && atoi(le) == 0)) {
+    if (lds_full <= 160 * 1024) {
         go(k_match_local<true, 1024>, k_match_local<true, 512>, lds_full);
     } else if (lds_min <= 160 * 1024) {
         go(k_match_local<false, 1024>, k_match_local<false, 512>, lds_min);
@@ -1532,16 +1501,11 @@ int launch_match_local(const MatchCam& cam, const LocalBufsHost& h, float th, fl
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int launch_match_kf(const MatchCam& cam, const KfBufsHost& h, float th, int orb_dist, int check_ori, hipStream_t s,
+int launch_match_kf(const MatchCam& cam, const KfBufs& b, float th, int orb_dist, int check_ori, hipStream_t s,
                     ProfileHook* prof)
 {
-    KfBufs b;
-    b.cur_kps = h.cur_kps; b.cur_desc = h.cur_desc; b.cur_has = h.cur_has; b.cur_n = h.cur_n;
-    b.valid = h.valid; b.xw = h.xw; b.desc = h.desc; b.maxd = h.maxd; b.mind = h.mind; b.angle = h.angle;
-    b.kf_n = h.kf_n; b.Tcw = h.Tcw; b.match = h.match; b.nmatch = h.nmatch; b.lists = h.lists; b.err = h.err;
-    b.path = h.path;
     const int force_seq = coeb_switch("COEB_MATCH_SEQUENTIAL") ? 1 : 0;
-    const int cs = std::max(h.cur_n, 1), qs = std::max(h.kf_n, 1);
+    const int cs = std::max(b.cur_n, 1), qs = std::max(b.kf_n, 1);
     const size_t lds_full = match_lds_bytes(cs, qs, true, nullptr) + 256;
     const size_t lds_min = match_lds_bytes(cs, qs, false, nullptr) + 256;
     prof_begin(prof, "k_match_kf", s);

@@ -531,14 +531,11 @@ __device__ void active_chi2(PoseLds& L, const PoseBufs& b, const PoseCam& cm, in
     block_reduce(L, acc, T);
 }
 
-// phase clocks of thread 0 (diagnostic, COEB_POSE_TIMING): [0] chi2 passes, [1] build passes,
+// phase clocks of thread 0 (diagnostic): [0] chi2 passes, [1] build passes,
 // [2] thread-0 solve + exp + bookkeeping, [3] classification, [4] total, [5] iterations, [6] trials
 // Compiled in only with -DCOEB_POSE_CLOCK=1 (tools/_pose_timing.py's builds): the runtime checks of
 // b.timing alone cost 19 SGPR and 2 VGPR spills in k_pose<5> (3.91 -> 3.85 ms per config-D step
 // without them, profiles/r05/s34).
-#ifndef COEB_POSE_CLOCK
-#define COEB_POSE_CLOCK 0
-#endif
 #if COEB_POSE_CLOCK
 #define PT_ON(b) ((b).timing)
 #else

@@ -13,7 +13,7 @@ import pytest
 
 import coeb_front as cf
 from coeb_front import KEYPOINT_DTYPE, synth
-from test_gpu_parity import assert_same, match_both
+from test_gpu_parity import assert_same, keyframe_both, localmap_both, match_both
 
 pytestmark = pytest.mark.gpu
 
@@ -564,3 +564,73 @@ def test_batch_call_order_guards():
         c.synchronize()
     finally:
         bp.close()
+
+
+# ------------------------------------------------------------------ 9. the matchers' unstaged forms
+GRID_CELLS, LDS_BUDGET, CUR_MAX, N_SECOND = 64 * 48, 160 * 1024, 4095, 64
+
+
+def match_lds_bytes(n, q, lds_cur):
+    """match_lds_bytes of csrc/coeb_match.hip: the LDS of one matcher workgroup with n current
+    keypoints and q second-side points, with or without the current frame staged."""
+    n4, q4 = (n + 3) & ~3, (q + 3) & ~3
+    return (((GRID_CELLS + 1) * 4 + 15) & ~15) + 2 * n4 * 4 + 2 * q4 * 4 + (n4 * (16 + 32) if lds_cur else 0)
+
+
+def smallest_unstaged_n(q):
+    """The fewest current keypoints at which the launchers can no longer stage the frame."""
+    n = next(n for n in range(1, CUR_MAX + 1) if match_lds_bytes(n, q, True) + 256 > LDS_BUDGET)
+    assert match_lds_bytes(n - 1, q, True) + 256 <= LDS_BUDGET < match_lds_bytes(n, q, True) + 256
+    assert match_lds_bytes(n, q, False) + 256 <= LDS_BUDGET and n <= CUR_MAX
+    return n
+
+
+@pytest.fixture(scope="module")
+def crowded_frame(oracle_mod):
+    """A synthetic current frame with just too many keypoints for the staged matcher forms (by
+    shape, the only way k_match_lists<false> + k_match<false>, k_match_local<false> and
+    k_match_kf<false> run): keypoints spread over 640x480 with random descriptors, and a second
+    side of N_SECOND points that are its first N_SECOND keypoints seen from the identity pose
+    with a few descriptor bits flipped."""
+    n = smallest_unstaged_n(N_SECOND)
+    rng = np.random.default_rng(2693)
+    k = np.zeros(n, KEYPOINT_DTYPE)
+    k["x"] = rng.uniform(16, 640 - 16, n).astype(np.float32)
+    k["y"] = rng.uniform(16, 480 - 16, n).astype(np.float32)
+    k["octave"] = rng.integers(0, 8, n)
+    k["size"] = (31 * np.float32(1.2) ** k["octave"]).astype(np.float32)
+    k["angle"] = rng.uniform(0, 360, n).astype(np.float32)
+    k["response"] = rng.uniform(20, 200, n).astype(np.float32)
+    k["class_id"] = -1
+    d = rng.integers(0, 256, (n, 32)).astype(np.uint8)
+    depth = synth.make_depth(640, 480)
+    ur, _ = oracle_mod.stereo_from_rgbd(k, depth, synth.TUM_BF)
+    d2 = d[:N_SECOND].copy()
+    for row in d2:                                       # 6 of 256 bits differ: far below TH_HIGH = 100
+        for b in rng.choice(256, 6, replace=False):
+            row[b >> 3] ^= np.uint8(1 << (b & 7))
+    second = oracle_mod.mapframe_from_extraction(k[:N_SECOND], d2, depth, synth.TUM_FX, synth.TUM_FY, synth.TUM_CX,
+                                                 synth.TUM_CY, synth.TUM_BF)
+    return k, d, ur, second
+
+
+def test_match_lastframe_unstaged_form(ctx, oracle_mod, ex, crowded_frame):
+    k, d, ur, last = crowded_frame
+    nm = match_both(ctx, oracle_mod, ex, k, d, ur, last, synth.motion_pose(), np.eye(4, dtype=np.float32))
+    assert nm >= N_SECOND // 2, nm
+
+
+def test_match_localmap_unstaged_form(ctx, oracle_mod, ex, crowded_frame):
+    k, d, ur, last = crowded_frame
+    mp = synth.make_local_map(last["xw"], last["mp_desc"], last["keys_un"]["octave"], synth.motion_pose(), 640, 480,
+                              seed=1, dup_frac=0.0, n_distract=0)
+    assert len(mp["in_view"]) == N_SECOND
+    assert localmap_both(ctx, oracle_mod, ex, k, d, ur, None, mp, th=5.0) >= N_SECOND // 4
+
+
+def test_match_keyframe_unstaged_form(ctx, oracle_mod, ex, crowded_frame):
+    k, d, _, last = crowded_frame
+    kf = synth.make_keyframe_points(last["xw"], last["mp_desc"], last["keys_un"]["octave"], last["keys_un"]["angle"],
+                                    seed=1, n_distract=0)
+    assert len(kf["valid"]) == N_SECOND
+    assert keyframe_both(ctx, oracle_mod, ex, k, d, None, kf, synth.motion_pose()) >= N_SECOND // 4

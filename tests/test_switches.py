@@ -1,8 +1,8 @@
 """Runtime switches of the shipped library: the library reads the environment
-only through coeb_switch() / coeb_experiment() (csrc/coeb_capi.hip); every product switch is on the
-kSwitches list and is set by at least one GPU test, and experiment switches are read only under
-COEB_EXPERIMENTS=1.  Also: the one -Wpass-failed diagnostic that coeb_flow.hip suppresses is the
-expected k_fm<128> occupancy target and nothing else (an unroll or other pass failure would show)."""
+only through coeb_switch() (csrc/coeb_capi.hip), every product switch is on the kSwitches list and
+is set by at least one GPU test, and there is no second gate for untested forms.  Also: the one
+-Wpass-failed diagnostic that coeb_flow.hip suppresses is the expected k_fm<128> occupancy target
+and nothing else (an unroll or other pass failure would show)."""
 import glob
 import os
 import re
@@ -23,12 +23,14 @@ def _sources():
 def test_environment_read_only_through_the_switch_helpers():
     src = _sources()
     calls = [(f, m.start()) for f, s in src.items() for m in re.finditer(r"\bgetenv\s*\(", s)]
-    assert len(calls) == 3 and {f for f, _ in calls} == {"coeb_capi.hip"}, calls
+    assert len(calls) == 1 and calls[0][0] == "coeb_capi.hip", calls
     capi = src["coeb_capi.hip"]
-    for _, pos in calls:
-        fn = capi.rfind("const char* coeb_", 0, pos)
-        assert capi[fn:fn + 40].startswith(("const char* coeb_switch(", "const char* coeb_experiment(")), \
-            capi[fn:fn + 60]
+    fn = capi.rfind("const char* coeb_", 0, calls[0][1])
+    assert capi[fn:fn + 40].startswith("const char* coeb_switch("), capi[fn:fn + 60]
+    for path in glob.glob(os.path.join(CSRC, "**", "*"), recursive=True):
+        if os.path.isfile(path) and "/build/" not in path:
+            text = open(path, errors="replace").read()
+            assert "coeb_experiment" not in text and "COEB_EXPERIMENTS" not in text, path
 
 
 def test_every_product_switch_is_listed_and_tested():

@@ -1,14 +1,13 @@
-"""k_match phase clocks over one bench-shaped batch (COEB_MATCH_TIMING=1): median cycles per
-phase across the batch's pairs.  Diagnostic only.  Optional arguments: W H F NFEATURES
-(default 640 480 257 1000; 1280 960 33 2000 is one pipeline of config B's 64-frame shard)."""
+"""k_match phase clocks over one bench-shaped batch: median cycles per phase across the batch's
+pairs.  Diagnostic only; needs a library built with the clocks compiled in: tools/_build_var.sh
+clock "-DCOEB_MATCH_CLOCK=1" and COEB_LIB_PATH=coeb-slam_amd/lib/var_clock.so.  Optional arguments:
+W H F NFEATURES (default 640 480 257 1000; 1280 960 33 2000 is one pipeline of config B's 64-frame
+shard)."""
 import os
 import sys
 
 import numpy as np
 
-os.environ["COEB_MATCH_TIMING"] = "1"
-os.environ["COEB_EXPERIMENTS"] = "1"     # experiment switches are read only under this gate
-# (and the library must be an experiment build: tools/_build_var.sh clock "-DCOEB_MATCH_CLOCK=1")
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "coeb-slam_amd"))
 from coeb_front import synth  # noqa: E402
 from coeb_front.pipeline import BatchPipeline  # noqa: E402

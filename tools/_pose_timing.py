@@ -1,4 +1,4 @@
-"""k_pose phase clocks over one config-D batch (COEB_POSE_TIMING=1): median clock64 cycles
+"""k_pose phase clocks over one config-D batch: median clock64 cycles
 per phase across the 256 frames.  Diagnostic only; needs a library built with the clocks compiled in:
 tools/_build_var.sh clock "-DCOEB_POSE_CLOCK=1" and COEB_LIB_PATH=coeb-slam_amd/lib/var_clock.so."""
 import os
@@ -6,8 +6,6 @@ import sys
 
 import numpy as np
 
-os.environ["COEB_POSE_TIMING"] = "1"
-os.environ["COEB_EXPERIMENTS"] = "1"     # experiment switches are read only under this gate
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "coeb-slam_amd"))
 from coeb_front import synth  # noqa: E402
 from coeb_front.pipeline import BatchPipeline  # noqa: E402
