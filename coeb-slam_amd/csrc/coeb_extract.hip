@@ -2588,20 +2588,13 @@ int launch_extract(const Plan& plan, const Plan* d_plan, const ExtractBufs& b, i
         }
     }
     constexpr int kOctThreads = 256;       // 512 / 1024 measured slower on large batches, 128 too (r06/s10)
-    // Small batches (per-rank shards: fewer workgroups than two per CU): the key capacity in LDS
-    // doubles (up to 4096 keys, within 150 KB), so a 1280x960 level 0 (~2 700 candidates) keeps
-    // its keys in LDS instead of the global ping-pong buffers; large batches keep the plan's
-    // capacity, which leaves more workgroups per CU.  (Level 0 as one 1024-thread workgroup and
-    // the short upper levels as one-wave workgroups were both measured slower)
+    // The key capacity in LDS depends on the batch size (oct_launch_keys, coeb_plan.cpp).  (Level 0
+    // as one 1024-thread workgroup and the short upper levels as one-wave workgroups were both
+    // measured slower)
     // One frame (the single-frame path) with 1024 / 512 threads per workgroup: 1024 adds 5 us to
     // the frame's extract, 512 is within noise of 256 (r06/s38), so one size serves every batch.
-    int oct_kl = plan.oct_kl, oct_lds = plan.oct_lds;
-    if (F * plan.L <= 2 * 256) {
-        int kl = oct_kl;
-        while (kl < 4096 && plan.oct_w * (4 + 16 + 4 + 4 + 4 + 1 + 64) + 8 * (2 * kl) <= 150 * 1024) kl *= 2;
-        oct_kl = kl;
-        oct_lds = plan.oct_w * (4 + 16 + 4 + 4 + 4 + 1 + 64) + 8 * kl;
-    }
+    int oct_kl, oct_lds;
+    oct_launch_keys(plan, F, &oct_kl, &oct_lds);
     lds_limit_max((const void*)k_octree<kOctThreads>);
     auto octree = [&](hipStream_t st, int l0, int l1) {
         if (l1 <= l0) return;

@@ -259,3 +259,16 @@ bool make_plan(const Tables& t, int W, int H, int oct_kl_override, Plan& P, std:
 
     return true;
 }
+
+void oct_launch_keys(const Plan& plan, int F, int* kl_out, int* lds_out)
+{
+    int oct_kl = plan.oct_kl, oct_lds = plan.oct_lds;
+    if (F * plan.L <= 2 * 256) {
+        int kl = oct_kl;
+        while (kl < 4096 && plan.oct_w * (4 + 16 + 4 + 4 + 4 + 1 + 64) + 8 * (2 * kl) <= 150 * 1024) kl *= 2;
+        oct_kl = kl;
+        oct_lds = plan.oct_w * (4 + 16 + 4 + 4 + 4 + 1 + 64) + 8 * kl;
+    }
+    *kl_out = oct_kl;
+    *lds_out = oct_lds;
+}

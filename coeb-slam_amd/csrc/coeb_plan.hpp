@@ -90,3 +90,9 @@ int resize_tables(int sw, int sh, int dw, int dh, std::vector<int>& tab);
 // keeps in LDS per level (clamped to [256, 8192]) in place of the computed count.
 bool make_plan(const Tables& t, int W, int H, int oct_kl_override, Plan& P, std::vector<int>& rtab,
                std::vector<CellDesc>& cells, std::string& err);
+// k_octree's key capacity of one launch over F frames: *kl keys per level in LDS (more
+// candidates: the global ping-pong buffers) and *lds dynamic LDS bytes.  Small batches (per-rank
+// shards: fewer workgroups than two per CU, F * L <= 512) double the plan's capacity up to 4096
+// keys within 150 KB, so a 1280x960 level 0 (~2 700 candidates) keeps its keys in LDS; large
+// batches keep the plan's capacity, which leaves more workgroups per CU.
+void oct_launch_keys(const Plan& plan, int F, int* kl, int* lds);

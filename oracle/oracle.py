@@ -143,6 +143,21 @@ class Extractor:
         return res
 
 
+def distribute_octree(xs, ys, score, min_x, max_x, min_y, max_y, n_keep):
+    """ORBextractor::DistributeOctTree (ORBextractor.cc:546-769) over keys (xs, ys, score) given
+    relative to (min_x, min_y): the kept keys' indices into the input, in vResultKeys order."""
+    xs = np.ascontiguousarray(xs, np.int32)
+    ys = np.ascontiguousarray(ys, np.int32)
+    score = np.ascontiguousarray(score, np.int32)
+    n = len(xs)
+    assert len(ys) == n and len(score) == n
+    out = np.zeros(n + 8, np.int32)
+    nk = lib().oc_distribute_octree(ptr(xs), ptr(ys), ptr(score), n, int(min_x), int(max_x), int(min_y), int(max_y),
+                                    int(n_keep), ptr(out), len(out))
+    assert 0 <= nk <= len(out)
+    return out[:nk].copy()
+
+
 def camera(ex, w, h, fx, fy, cx, cy, bf):
     c = Camera()
     lib().oc_camera_init(C.byref(c), C.c_float(fx), C.c_float(fy), C.c_float(cx), C.c_float(cy),

@@ -179,6 +179,45 @@ static void check_oct_kl_override()
     }
 }
 
+// The key capacity k_octree is launched with (oct_launch_keys).  tests/test_gpu_octree_layouts.py
+// places its level-0 candidate counts one below, at and one above these two capacities.
+static void check_oct_launch_keys()
+{
+    snprintf(g_case, sizeof g_case, "oct_launch_keys 640x480 default");
+    Tables t;
+    CHECK(make_tables(orb_params(Params{1000, 1.2f, 8}), t));
+    Plan P;
+    std::vector<int> rtab;
+    std::vector<CellDesc> cells;
+    std::string err;
+    CHECK(make_plan(t, 640, 480, 0, P, rtab, cells, err));
+    CHECK(P.oct_kl == 1024);
+    const int F[] = {1, 16, 64, 65, 256}, want[] = {4096, 4096, 4096, 1024, 1024};
+    for (int i = 0; i < 5; i++) {
+        int kl = -1, lds = -1;
+        oct_launch_keys(P, F[i], &kl, &lds);
+        CHECK(kl == want[i]);
+        CHECK(lds == P.oct_w * (4 + 16 + 4 + 4 + 4 + 1 + 64) + 8 * kl && lds <= 150 * 1024);
+        CHECK(kl >= P.oct_kl && (kl == P.oct_kl) == (F[i] * P.L > 512));
+    }
+    // a plan whose node records leave no room for 4096 keys stops doubling inside the budget
+    snprintf(g_case, sizeof g_case, "oct_launch_keys LDS budget");
+    const int sizes[][2] = {{640, 480}, {1280, 960}, {4096, 4096}};
+    const Params sets[] = {{1000, 1.2f, 8}, {2000, 1.2f, 8}, {500, 1.5f, 4}};
+    for (const auto& s : sizes)
+        for (const Params& q : sets) {
+            CHECK(make_tables(orb_params(q), t));
+            CHECK(make_plan(t, s[0], s[1], 0, P, rtab, cells, err));
+            for (int f : {1, 512 / q.nlevels, 512 / q.nlevels + 1}) {
+                int kl = -1, lds = -1;
+                oct_launch_keys(P, f, &kl, &lds);
+                CHECK(kl >= P.oct_kl && kl <= 4096 && (kl & (kl - 1)) == 0 && lds <= 150 * 1024);
+                CHECK(lds == P.oct_w * (4 + 16 + 4 + 4 + 4 + 1 + 64) + 8 * kl);
+                if (f * q.nlevels > 512) CHECK(kl == P.oct_kl && lds == P.oct_lds);
+            }
+        }
+}
+
 int main()
 {
     const int sizes[][2] = {{640, 480}, {1280, 960}, {752, 480}, {1241, 376}, {321, 243}, {4096, 4096}};
@@ -202,6 +241,7 @@ int main()
     CHECK(!make_tables(orb_params(Params{1000, -1.2f, 8}), t));
     CHECK(make_tables(orb_params(Params{0, 1.2f, 16}), t));
     check_oct_kl_override();
+    check_oct_launch_keys();
     if (g_fail) {
         fprintf(stderr, "%d check(s) failed\n", g_fail);
         return 1;
