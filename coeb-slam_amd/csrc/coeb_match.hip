@@ -8,9 +8,9 @@
 // One 1024-thread workgroup per frame (pair).  Phase 0 (stage_grid) stages the current frame
 // in LDS and builds the 64 x 48 keypoint grid as a CSR by a stable counting sort, so a cell
 // column ix over rows [iy0, iy1] is ONE contiguous range in the reference's enumeration order
-// (ix outer, iy inner, in-cell insertion order).  Phase 1: kQL lanes per query walk its
-// window (level, window, stereo checks, 256-bit Hamming via popcount) and write its candidate
-// list in that order.  Phase 2 resolves the sequential claim dependency (:1404-1406 / :86-88)
+// (ix outer, iy inner, in-cell insertion order).  Phase 1 (walk_window, with each matcher's own
+// candidate test): kQL lanes per query walk its window (level, window, stereo checks, 256-bit
+// Hamming via popcount) and write its candidate list in that order.  Phase 2 resolves the sequential claim dependency (:1404-1406 / :86-88)
 // as a Jacobi fixpoint, with the literal loop as fallback.  Phase 3 assigns (last writer
 // wins) and, for k_match, applies the rotation-histogram top-3 filter.
 #include <hip/hip_runtime.h>
@@ -182,17 +182,34 @@ __device__ __forceinline__ bool window_cells(const MatchCam& cam, QueryWin& w)
     return true;
 }
 
+// x3Dc = Rcw * x3Dw + tcw as the reference's cv::Mat small gemm rounds it: float products summed
+// left to right, the translation added in double.  T = Tcw, row-major.
+__device__ __forceinline__ void cam_point(const float* T, const float* X, float* p3)
+{
+    for (int k = 0; k < 3; k++) {
+        float t = T[k * 4 + 0] * X[0] + T[k * 4 + 1] * X[1];
+        t = t + T[k * 4 + 2] * X[2];
+        p3[k] = (float)((double)t + (double)T[k * 4 + 3]);
+    }
+}
+
+// Camera centre Ow = twc = -Rcw^T * tcw (double accumulation, ORBmatcher.cc:1339-1343 / :1479-1481)
+__device__ __forceinline__ void cam_centre(const float* T, float* Ow)
+{
+    for (int k = 0; k < 3; k++) {
+        double s = (double)T[0 * 4 + k] * T[3] + (double)T[1 * 4 + k] * T[7];
+        s = s + (double)T[2 * 4 + k] * T[11];
+        Ow[k] = (float)(s * -1.0);
+    }
+}
+
 __device__ __forceinline__ QueryWin query_window(const MatchCam& cam, const float* T, const float* scale, const float* X,
                                                  int octave, float th, bool fwd, bool bwd)
 {
     QueryWin w;
     w.ok = false;
     float p3[3];
-    for (int k = 0; k < 3; k++) {                  // x3Dc = Rcw*x3Dw + tcw (cv::Mat small gemm)
-        float t = T[k * 4 + 0] * X[0] + T[k * 4 + 1] * X[1];
-        t = t + T[k * 4 + 2] * X[2];
-        p3[k] = (float)((double)t + (double)T[k * 4 + 3]);
-    }
+    cam_point(T, X, p3);
     const float invzc = (float)(1.0 / (double)p3[2]);
     if (invzc < 0) return w;
     w.u = __builtin_fmaf(cam.fx * p3[0], invzc, cam.cx);   // fused in the reference binary
@@ -283,6 +300,31 @@ __host__ __device__ inline size_t match_lds_bytes(int nmax, int qmax, bool lds_c
     off[6] = o; if (lds_cur) o += n4 * 32;
     if (offs) for (int i = 0; i < 7; i++) offs[i] = off[i];
     return o;
+}
+
+// A workgroup's dynamic LDS carved at match_lds_bytes' offsets (L.kp / L.desc are meaningful in the
+// staged form only), and the CurView over it with the global arrays the unstaged form reads.
+__device__ __forceinline__ MatchLds match_lds(uint8_t* smem, int nmax, int qmax, bool lds_cur)
+{
+    size_t off[7];
+    match_lds_bytes(nmax, qmax, lds_cur, off);
+    MatchLds L;
+    L.cell = reinterpret_cast<int*>(smem + off[0]);
+    L.sort = reinterpret_cast<uint32_t*>(smem + off[1]);
+    L.owner = reinterpret_cast<int*>(smem + off[2]);
+    L.res = reinterpret_cast<int*>(smem + off[3]);
+    L.qn = reinterpret_cast<int*>(smem + off[4]);
+    L.kp = reinterpret_cast<float4*>(smem + off[5]);
+    L.desc = reinterpret_cast<uint32_t*>(smem + off[6]);
+    return L;
+}
+
+template <bool kLds>
+__device__ __forceinline__ CurView<kLds> cur_view(const MatchLds& L, const Kp* kps, const float* ur, const uint8_t* desc)
+{
+    CurView<kLds> cv;
+    cv.kp = L.kp; cv.desc = L.desc; cv.gkp = kps; cv.gur = ur; cv.gdesc = desc;
+    return cv;
 }
 
 // Phase 0 of both matchers: stage the CurrentFrame (x, y, uR, octave, descriptor) in LDS and
@@ -557,19 +599,10 @@ __device__ __forceinline__ PairView pair_view(const MatchCam& cam, const MatchBu
     v.lnobs = b.last_nobs + (int64_t)p * b.last_stride;
     v.lists = reinterpret_cast<uint32_t*>(b.scratch) + (int64_t)p * b.scratch_stride;
     v.T = b.Tcw_cur + (int64_t)p * 16;
-    const float* T = v.T;
     const float* Tl = b.Tcw_last + (int64_t)p * 16;
     float twc[3], tlc[3];
-    for (int k = 0; k < 3; k++) {
-        double s = (double)T[0 * 4 + k] * T[3] + (double)T[1 * 4 + k] * T[7];
-        s = s + (double)T[2 * 4 + k] * T[11];
-        twc[k] = (float)(s * -1.0);
-    }
-    for (int k = 0; k < 3; k++) {
-        float t = Tl[k * 4 + 0] * twc[0] + Tl[k * 4 + 1] * twc[1];
-        t = t + Tl[k * 4 + 2] * twc[2];
-        tlc[k] = (float)((double)t + (double)Tl[k * 4 + 3]);
-    }
+    cam_centre(v.T, twc);
+    cam_point(Tl, twc, tlc);                           // tlc = Rlw * twc + tlw
     v.fwd = tlc[2] > cam.mb && !bmono;
     v.bwd = -tlc[2] > cam.mb && !bmono;
     return v;
@@ -579,6 +612,56 @@ __device__ __forceinline__ bool pair_bad(const MatchBufs& b, const PairView& v)
 {
     return v.n > b.cur_stride || v.nl > b.last_stride || v.n >= (1 << kIdxBits);
 }
+
+// Phase 1 of every matcher, for one query: the candidate walk of a kQL-lane group (lane gl; gsh =
+// the group's first lane in its wave) over the window w, compacted into lst in enumeration order.
+// The window's columns are taken kQL at a time: lane gl holds column gx + gl's CSR range, a group
+// scan gives each column's offset in the concatenated (column-major) order, and the group walks
+// that concatenation kQL candidates at a time -- one pass per column group instead of one per
+// column.  test(e, i2, x, y, ur, oct, ent) is the matcher's own filter on candidate i2 (CSR
+// position e); where it passes it sets the list entry.  A ballot over the group gives every passing
+// lane its slot, so the list keeps the order.  Returns the number that passed; only the first kCQ
+// are stored, and the caller raises its overflow flag past that.  All lanes of a group call this
+// together.
+template <bool kLds, class Test>
+__device__ __forceinline__ int walk_window(const QueryWin& w, const MatchLds& L, const CurView<kLds>& cv, uint32_t* lst,
+                                           int gl, int gsh, Test&& test)
+{
+    int cnt = 0;
+    for (int gx = w.x0; gx <= w.x1; gx += kQL) {
+        int clo = 0, clen = 0;
+        if (gx + gl <= w.x1) {
+            clo = L.cell[(gx + gl) * COEB_GRID_ROWS + w.y0];
+            clen = L.cell[(gx + gl) * COEB_GRID_ROWS + w.y1 + 1] - clo;
+        }
+        const GroupCols gc = group_cols(clo, clen, gl);
+        for (int base = 0; base < gc.total; base += kQL) {
+            const int fi = base + gl;
+            const int e = gc.index(fi);
+            const int c1 = fi < gc.total ? e + 1 : e;      // e < c1 <=> fi < total
+            bool ok = false;
+            uint32_t ent = 0;
+            if (e < c1) {
+                const int i2 = (int)(L.sort[e] & ((1u << kIdxBits) - 1));
+                float x, y, ur;
+                int oct;
+                cv.get(e, i2, x, y, ur, oct);
+                ok = test(e, i2, x, y, ur, oct, ent);
+            }
+            const uint32_t gb = (uint32_t)(__ballot(ok) >> gsh) & ((1u << kQL) - 1u);
+            if (ok) {
+                const int pos = cnt + __popc(gb & ((1u << gl) - 1u));
+                if (pos < kCQ) lst[pos] = ent;
+            }
+            cnt += __popc(gb);
+        }
+    }
+    return cnt;
+}
+
+// A query's count word (L.qn): -1 without a window, else the stored length with 0x10000 set when
+// the query's assignment blocks later queries
+__device__ __forceinline__ int qn_word(int cnt, bool blocks) { return cnt < 0 ? -1 : (min(cnt, kCQ) | (blocks ? 0x10000 : 0)); }
 
 // Phase 1 of k_match for the queries q0 + grp, q0 = qbeg, qbeg + qstep, ...: candidate lists
 // (static filters) -> v.lists, counts -> qn_out[q] (-1: none; 0x10000 set when q blocks later
@@ -606,8 +689,7 @@ __device__ void build_lists(const MatchCam& cam, const PairView& v, const MatchL
     __syncthreads();
     const float* T = s_geo;
     const float* scale = s_geo + 12;
-    // one kQL-lane group per query; lanes take the candidates of a grid column range kQL at a
-    // time and ballot-compact them, so each list stays in enumeration order
+    // one kQL-lane group per query (walk_window)
     {
         const int grp = tid / kQL, gl = tid % kQL, gsh = (tid & 63) & ~(kQL - 1);
         // a query's inputs (flags, world point, octave, descriptor) are loaded one pass ahead
@@ -646,10 +728,8 @@ __device__ void build_lists(const MatchCam& cam, const PairView& v, const MatchL
                 qd[4] = qi.d1.x; qd[5] = qi.d1.y; qd[6] = qi.d1.z; qd[7] = qi.d1.w;
                 cnt = 0;
                 uint32_t* lst = lists + (int64_t)q * kCQ;
-                // the window's columns kQL at a time: lane gl holds column gx + gl's CSR range, a
-                // group scan gives each column's offset in the concatenated (column-major) order,
-                // and the group walks that concatenation kQL candidates at a time -- one pass per
-                // column group instead of one per column, same enumeration order
+                // walk_window, written out: as a call of the template this loop compiles to a
+                // different (and, measured, 0.3 % slower) k_match; keep the two in step
                 for (int gx = w.x0; gx <= w.x1; gx += kQL) {
                     int clo = 0, clen = 0;
                     if (gx + gl <= w.x1) {
@@ -692,7 +772,7 @@ __device__ void build_lists(const MatchCam& cam, const PairView& v, const MatchL
                 }
                 if (cnt > kCQ) s_flag[0] = 1;      // overflow -> sequential path
             }
-            if (q < nl && gl == 0) qn_out[q] = cnt < 0 ? -1 : (min(cnt, kCQ) | (qi.nobs > 0 ? 0x10000 : 0));
+            if (q < nl && gl == 0) qn_out[q] = qn_word(cnt, qi.nobs > 0);
             if (tm && tid == 0) tm[15] += 1;
         }
         if (tm && (tid & 63) == 0) {           // per-wave loop time: slowest / fastest wave
@@ -721,18 +801,10 @@ __global__ __launch_bounds__(NT) void k_match_lists(MatchCam cam, MatchBufs b, f
         if (threadIdx.x == 0) qn[b.last_stride + sl] = 1;        // k_match reports the error
         return;
     }
-    size_t off[7];
-    match_lds_bytes(b.cur_stride, 0, kLds, off);
-    MatchLds L;
-    L.cell = reinterpret_cast<int*>(smem + off[0]);
-    L.sort = reinterpret_cast<uint32_t*>(smem + off[1]);
-    L.owner = reinterpret_cast<int*>(smem + off[2]);
-    L.res = nullptr;
+    MatchLds L = match_lds(smem, b.cur_stride, 0, kLds);
+    L.res = nullptr;                                   // no claims here: the counts go to b.qn
     L.qn = nullptr;
-    L.kp = reinterpret_cast<float4*>(smem + off[5]);
-    L.desc = reinterpret_cast<uint32_t*>(smem + off[6]);
-    CurView<kLds> cv;
-    cv.kp = L.kp; cv.desc = L.desc; cv.gkp = v.cur; cv.gur = v.cur_ur; cv.gdesc = v.cdesc;
+    const CurView<kLds> cv = cur_view<kLds>(L, v.cur, v.cur_ur, v.cdesc);
     stage_grid<kLds, NT>(cam, v.cur, v.cur_ur, v.cdesc, v.n, L);
     if (threadIdx.x == 0) s_flag[0] = 0;
     __syncthreads();
@@ -775,16 +847,7 @@ __global__ __launch_bounds__(NT, COEB_MATCH_MINWG) void k_match(MatchArgs args)
     const int tid = threadIdx.x;
     const PairView v = pair_view(cam, b, p, bmono);
     const int n = v.n, nl = v.nl;
-    size_t off[7];
-    match_lds_bytes(b.cur_stride, b.last_stride, kLds, off);
-    MatchLds L;
-    L.cell = reinterpret_cast<int*>(smem + off[0]);
-    L.sort = reinterpret_cast<uint32_t*>(smem + off[1]);
-    L.owner = reinterpret_cast<int*>(smem + off[2]);
-    L.res = reinterpret_cast<int*>(smem + off[3]);
-    L.qn = reinterpret_cast<int*>(smem + off[4]);
-    L.kp = reinterpret_cast<float4*>(smem + off[5]);
-    L.desc = reinterpret_cast<uint32_t*>(smem + off[6]);
+    const MatchLds L = match_lds(smem, b.cur_stride, b.last_stride, kLds);
     const Kp* cur = v.cur;
     const uint8_t* cdesc = v.cdesc;
     const float* cur_ur = v.cur_ur;
@@ -797,8 +860,7 @@ __global__ __launch_bounds__(NT, COEB_MATCH_MINWG) void k_match(MatchArgs args)
         if (tid == 0) { atomicOr(b.err, 16); b.nmatch[p] = 0; }
         return;
     }
-    CurView<kLds> cv;
-    cv.kp = L.kp; cv.desc = L.desc; cv.gkp = cur; cv.gur = cur_ur; cv.gdesc = cdesc;
+    const CurView<kLds> cv = cur_view<kLds>(L, cur, cur_ur, cdesc);
 
     // ---- phase 0: stage CurrentFrame, grid CSR by a stable counting sort ----
     // phase clocks: experiment builds only (-DCOEB_MATCH_CLOCK=1,
@@ -937,6 +999,26 @@ __device__ __forceinline__ QueryWin local_window(const MatchCam& cam, const Loca
 
 constexpr int kLocKeyDist = 16, kLocKeyOct = 12;    // list entry: dist << 16 | octave << 12 | index
 
+// Best / second-best descriptor distance with their levels (ORBmatcher.cc:97-112) and the
+// acceptance (:115-121): TH_HIGH, and the ratio test when both sit on one level.
+struct BestTwo {
+    int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
+    __device__ __forceinline__ void add(int dist, int oct, int i2)
+    {
+        if (dist < bestDist) {
+            bestDist2 = bestDist; bestDist = dist;
+            bestLevel2 = bestLevel; bestLevel = oct; bestIdx = i2;
+        } else if (dist < bestDist2) {
+            bestLevel2 = oct; bestDist2 = dist;
+        }
+    }
+    __device__ __forceinline__ int pick(float nnratio) const
+    {
+        return bestDist <= TH_HIGH && !(bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2)
+                   ? bestIdx : -1;
+    }
+};
+
 template <bool kLds, int NT>
 __global__ __launch_bounds__(NT) void k_match_local(MatchCam cam, LocalBufs b0, float th, float nnratio,
                                                            int force_seq)
@@ -951,23 +1033,13 @@ __global__ __launch_bounds__(NT) void k_match_local(MatchCam cam, LocalBufs b0, 
         return;
     }
     const int n = b.cur_n, nq = b.mp_n;
-    size_t off[7];
-    match_lds_bytes(n, nq, kLds, off);
-    MatchLds L;
-    L.cell = reinterpret_cast<int*>(smem + off[0]);
-    L.sort = reinterpret_cast<uint32_t*>(smem + off[1]);
-    L.owner = reinterpret_cast<int*>(smem + off[2]);
-    L.res = reinterpret_cast<int*>(smem + off[3]);
-    L.qn = reinterpret_cast<int*>(smem + off[4]);
-    L.kp = reinterpret_cast<float4*>(smem + off[5]);
-    L.desc = reinterpret_cast<uint32_t*>(smem + off[6]);
+    const MatchLds L = match_lds(smem, n, nq, kLds);
     const Kp* cur = reinterpret_cast<const Kp*>(b.cur_kps);
     if (n >= (1 << kIdxBits)) {
         if (tid == 0) { atomicOr(b.err, 16); *b.nmatch = 0; }
         return;
     }
-    CurView<kLds> cv;
-    cv.kp = L.kp; cv.desc = L.desc; cv.gkp = cur; cv.gur = b.cur_ur; cv.gdesc = b.cur_desc;
+    const CurView<kLds> cv = cur_view<kLds>(L, cur, b.cur_ur, b.cur_desc);
     // the level scales, read by every point's window (from the kernel arguments each read is a
     // dependent global load)
     __shared__ float s_scale[COEB_MAXL];
@@ -976,7 +1048,7 @@ __global__ __launch_bounds__(NT) void k_match_local(MatchCam cam, LocalBufs b0, 
     if (tid == 0) { s_flag[0] = 0; s_flag[1] = 0; s_flag[2] = 0; }
     __syncthreads();
 
-    // ---- phase 1: candidate lists ----
+    // ---- phase 1: candidate lists (walk_window) ----
     {
         const int grp = tid / kQL, gl = tid % kQL, gsh = (tid & 63) & ~(kQL - 1);
         constexpr int qstep = NT / kQL;
@@ -1020,47 +1092,22 @@ __global__ __launch_bounds__(NT) void k_match_local(MatchCam cam, LocalBufs b0, 
                 uint32_t qd[8];
                 qd[0] = qi.d0.x; qd[1] = qi.d0.y; qd[2] = qi.d0.z; qd[3] = qi.d0.w;
                 qd[4] = qi.d1.x; qd[5] = qi.d1.y; qd[6] = qi.d1.z; qd[7] = qi.d1.w;
-                cnt = 0;
-                uint32_t* lst = b.lists + (int64_t)q * kCQ;
-                for (int gx = w.x0; gx <= w.x1; gx += kQL) {        // column groups, as in k_match
-                    int clo = 0, clen = 0;
-                    if (gx + gl <= w.x1) {
-                        clo = L.cell[(gx + gl) * COEB_GRID_ROWS + w.y0];
-                        clen = L.cell[(gx + gl) * COEB_GRID_ROWS + w.y1 + 1] - clo;
+                cnt = walk_window(w, L, cv, b.lists + (int64_t)q * kCQ, gl, gsh,
+                                  [&](int e, int i2, float x, float y, float ur, int oct, uint32_t& ent) {
+                    bool ok = !(oct < w.minL || oct > w.maxL);              // chk is always set here
+                    const float distx = x - w.u, disty = y - w.v;
+                    if (!(fabsf(distx) < w.radius && fabsf(disty) < w.radius)) ok = false;
+                    if (!kLds && b.cur_obs[i2] > 0) ok = false;  // :86-88, entry holder (LDS: kHeldOct)
+                    if (ur > 0 && fabsf(w.ur_q - ur) > w.radius) ok = false;   // :90-95
+                    if (ok) {
+                        const int dist = cv.dist(e, i2, qd);
+                        ent = ((uint32_t)dist << kLocKeyDist) | ((uint32_t)oct << kLocKeyOct) | (uint32_t)i2;
                     }
-                    const GroupCols gc = group_cols(clo, clen, gl);
-                    for (int base = 0; base < gc.total; base += kQL) {
-                        const int fi = base + gl;
-                        const int e = gc.index(fi);
-                        const int c1 = fi < gc.total ? e + 1 : e;
-                        bool ok = false;
-                        uint32_t ent = 0;
-                        if (e < c1) {
-                            const int i2 = (int)(L.sort[e] & ((1u << kIdxBits) - 1));
-                            float x, y, ur;
-                            int oct;
-                            cv.get(e, i2, x, y, ur, oct);
-                            ok = !(oct < w.minL || oct > w.maxL);              // chk is always set here
-                            const float distx = x - w.u, disty = y - w.v;
-                            if (!(fabsf(distx) < w.radius && fabsf(disty) < w.radius)) ok = false;
-                            if (!kLds && b.cur_obs[i2] > 0) ok = false;  // :86-88, entry holder (LDS: kHeldOct)
-                            if (ur > 0 && fabsf(w.ur_q - ur) > w.radius) ok = false;   // :90-95
-                            if (ok) {
-                                const int dist = cv.dist(e, i2, qd);
-                                ent = ((uint32_t)dist << kLocKeyDist) | ((uint32_t)oct << kLocKeyOct) | (uint32_t)i2;
-                            }
-                        }
-                        const uint32_t gb = (uint32_t)(__ballot(ok) >> gsh) & ((1u << kQL) - 1u);
-                        if (ok) {
-                            const int pos = cnt + __popc(gb & ((1u << gl) - 1u));
-                            if (pos < kCQ) lst[pos] = ent;
-                        }
-                        cnt += __popc(gb);
-                    }
-                }
+                    return ok;
+                });
                 if (cnt > kCQ) s_flag[0] = 1;
             }
-            if (q < nq && gl == 0) L.qn[q] = cnt < 0 ? -1 : (min(cnt, kCQ) | (qi.nobs > 0 ? 0x10000 : 0));
+            if (q < nq && gl == 0) L.qn[q] = qn_word(cnt, qi.nobs > 0);
         }
     }
     __syncthreads();
@@ -1071,20 +1118,10 @@ __global__ __launch_bounds__(NT) void k_match_local(MatchCam cam, LocalBufs b0, 
     // lists in registers across the iterations, as k_match's claims do; the rest are read from
     // the global lists in each iteration
     constexpr int LQ = COEB_LOCAL_QPT, LR = COEB_LOCAL_RL;
-    auto walk = [&](uint32_t v, int q, int& bestDist, int& bestLevel, int& bestDist2, int& bestLevel2, int& bestIdx) {
+    auto walk = [&](uint32_t v, int q, BestTwo& bt) {
         const int i2 = (int)(v & ((1u << kIdxBits) - 1));
         if (L.owner[i2] < q) return;                       // taken by an earlier point
-        const int dist = (int)(v >> kLocKeyDist), oct = (int)((v >> kLocKeyOct) & 0xF);
-        if (dist < bestDist) {
-            bestDist2 = bestDist; bestDist = dist;
-            bestLevel2 = bestLevel; bestLevel = oct; bestIdx = i2;
-        } else if (dist < bestDist2) {
-            bestLevel2 = oct; bestDist2 = dist;
-        }
-    };
-    auto decide = [&](int bestDist, int bestLevel, int bestDist2, int bestLevel2, int bestIdx) {
-        return bestDist <= TH_HIGH && !(bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2)
-                   ? bestIdx : -1;
+        bt.add((int)(v >> kLocKeyDist), (int)((v >> kLocKeyOct) & 0xF), i2);
     };
     if (!seq) {
         uint32_t rl[LQ][LR];
@@ -1121,13 +1158,13 @@ __global__ __launch_bounds__(NT) void k_match_local(MatchCam cam, LocalBufs b0, 
                 if (q < nq) {
                     int res = -1;
                     if (rm[u] >= 0) {
-                        int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
+                        BestTwo bt;
 #pragma unroll
                         for (int e = 0; e < LR; e++)
-                            if (e < rm[u]) walk(rl[u][e], q, bestDist, bestLevel, bestDist2, bestLevel2, bestIdx);
+                            if (e < rm[u]) walk(rl[u][e], q, bt);
                         const uint32_t* lst = b.lists + (int64_t)q * kCQ;
-                        for (int e = LR; e < rm[u]; e++) walk(lst[e], q, bestDist, bestLevel, bestDist2, bestLevel2, bestIdx);
-                        res = decide(bestDist, bestLevel, bestDist2, bestLevel2, bestIdx);
+                        for (int e = LR; e < rm[u]; e++) walk(lst[e], q, bt);
+                        res = bt.pick(nnratio);
                     }
                     if (it == 0 || res != L.res[q]) s_flag[1] = 1;
                     L.res[q] = res;
@@ -1139,9 +1176,9 @@ __global__ __launch_bounds__(NT) void k_match_local(MatchCam cam, LocalBufs b0, 
                 if (qn >= 0) {
                     const int m = qn & 0xFFFF;
                     const uint32_t* lst = b.lists + (int64_t)q * kCQ;
-                    int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
-                    for (int e = 0; e < m; e++) walk(lst[e], q, bestDist, bestLevel, bestDist2, bestLevel2, bestIdx);
-                    res = decide(bestDist, bestLevel, bestDist2, bestLevel2, bestIdx);
+                    BestTwo bt;
+                    for (int e = 0; e < m; e++) walk(lst[e], q, bt);
+                    res = bt.pick(nnratio);
                 }
                 if (it == 0 || res != L.res[q]) s_flag[1] = 1;
                 L.res[q] = res;
@@ -1167,27 +1204,21 @@ __global__ __launch_bounds__(NT) void k_match_local(MatchCam cam, LocalBufs b0, 
                 if (!w.ok) continue;
                 uint32_t qd[8];
                 for (int k = 0; k < 8; k++) qd[k] = reinterpret_cast<const uint32_t*>(b.desc + 32 * q)[k];
-                int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
+                BestTwo bt;
                 for_candidates<kLds>(w, L.cell, L.sort, cv, [&](int e, int i2) {
                     if (L.owner[i2] > 0) return true;
                     const int dist = cv.dist(e, i2, qd);
                     float x, y, ur;
                     int oct;
                     cv.get(e, i2, x, y, ur, oct);
-                    if (dist < bestDist) {
-                        bestDist2 = bestDist; bestDist = dist;
-                        bestLevel2 = bestLevel; bestLevel = oct; bestIdx = i2;
-                    } else if (dist < bestDist2) {
-                        bestLevel2 = oct; bestDist2 = dist;
-                    }
+                    bt.add(dist, oct, i2);
                     return true;
                 });
-                if (bestDist <= TH_HIGH) {
-                    if (bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2) continue;
-                    b.match[bestIdx] = q;
-                    L.owner[bestIdx] = b.nobs[q];
-                    nm++;
-                }
+                const int r = bt.pick(nnratio);
+                if (r < 0) continue;
+                b.match[r] = q;
+                L.owner[r] = b.nobs[q];
+                nm++;
             }
             *b.nmatch = nm;
         }
@@ -1237,11 +1268,7 @@ __device__ __forceinline__ QueryWin kf_window(const MatchCam& cam, const float* 
     if (!b.valid[q]) return w;
     const float* X = b.xw + 3 * q;
     float p3[3];
-    for (int k = 0; k < 3; k++) {                  // x3Dc = Rcw*x3Dw + tcw (as query_window)
-        float t = T[k * 4 + 0] * X[0] + T[k * 4 + 1] * X[1];
-        t = t + T[k * 4 + 2] * X[2];
-        p3[k] = (float)((double)t + (double)T[k * 4 + 3]);
-    }
+    cam_point(T, X, p3);
     const float invzc = (float)(1.0 / (double)p3[2]);
     w.u = __builtin_fmaf(cam.fx * p3[0], invzc, cam.cx);
     w.v = __builtin_fmaf(cam.fy * p3[1], invzc, cam.cy);
@@ -1273,35 +1300,21 @@ __global__ __launch_bounds__(kMThreads) void k_match_kf(MatchCam cam, KfBufs b, 
     __shared__ int s_flag[8];
     const int tid = threadIdx.x;
     const int n = b.cur_n, nq = b.kf_n;
-    size_t off[7];
-    match_lds_bytes(n, nq, kLds, off);
-    MatchLds L;
-    L.cell = reinterpret_cast<int*>(smem + off[0]);
-    L.sort = reinterpret_cast<uint32_t*>(smem + off[1]);
-    L.owner = reinterpret_cast<int*>(smem + off[2]);
-    L.res = reinterpret_cast<int*>(smem + off[3]);
-    L.qn = reinterpret_cast<int*>(smem + off[4]);
-    L.kp = reinterpret_cast<float4*>(smem + off[5]);
-    L.desc = reinterpret_cast<uint32_t*>(smem + off[6]);
+    const MatchLds L = match_lds(smem, n, nq, kLds);
     const Kp* cur = reinterpret_cast<const Kp*>(b.cur_kps);
     if (n >= (1 << kIdxBits)) {
         if (tid == 0) { atomicOr(b.err, 16); *b.nmatch = 0; }
         return;
     }
     // no uR is read here: the CSR staging takes the keypoint records only
-    CurView<kLds> cv;
-    cv.kp = L.kp; cv.desc = L.desc; cv.gkp = cur; cv.gur = nullptr; cv.gdesc = b.cur_desc;
+    const CurView<kLds> cv = cur_view<kLds>(L, cur, nullptr, b.cur_desc);
     stage_grid<kLds>(cam, cur, nullptr, b.cur_desc, n, L);
     const float* T = b.Tcw;
     float Ow[3];
-    for (int k = 0; k < 3; k++) {                 // Ow = -Rcw^T tcw (double accumulation)
-        double s = (double)T[0 * 4 + k] * T[3] + (double)T[1 * 4 + k] * T[7];
-        s = s + (double)T[2 * 4 + k] * T[11];
-        Ow[k] = (float)(s * -1.0);
-    }
+    cam_centre(T, Ow);
     if (tid == 0) { s_flag[0] = 0; s_flag[1] = 0; }
     __syncthreads();
-    // ---- phase 1: candidate lists (window, levels, entry holders, dist <= ORBdist) ----
+    // ---- phase 1: candidate lists (walk_window: window, levels, entry holders, dist <= ORBdist) ----
     {
         const int grp = tid / kQL, gl = tid % kQL, gsh = (tid & 63) & ~(kQL - 1);
         for (int q0 = 0; q0 < nq; q0 += kMThreads / kQL) {
@@ -1316,47 +1329,22 @@ __global__ __launch_bounds__(kMThreads) void k_match_kf(MatchCam cam, KfBufs b, 
                 const uint4 d0 = d[0], d1 = d[1];
                 qd[0] = d0.x; qd[1] = d0.y; qd[2] = d0.z; qd[3] = d0.w;
                 qd[4] = d1.x; qd[5] = d1.y; qd[6] = d1.z; qd[7] = d1.w;
-                cnt = 0;
-                uint32_t* lst = b.lists + (int64_t)q * kCQ;
-                for (int gx = w.x0; gx <= w.x1; gx += kQL) {        // column groups, as in k_match
-                    int clo = 0, clen = 0;
-                    if (gx + gl <= w.x1) {
-                        clo = L.cell[(gx + gl) * COEB_GRID_ROWS + w.y0];
-                        clen = L.cell[(gx + gl) * COEB_GRID_ROWS + w.y1 + 1] - clo;
+                cnt = walk_window(w, L, cv, b.lists + (int64_t)q * kCQ, gl, gsh,
+                                  [&](int e, int i2, float x, float y, float ur, int oct, uint32_t& ent) {
+                    bool ok = !(oct < w.minL || oct > w.maxL);            // chk always set (maxL >= 0)
+                    const float distx = x - w.u, disty = y - w.v;
+                    if (!(fabsf(distx) < w.radius && fabsf(disty) < w.radius)) ok = false;
+                    if (b.cur_has[i2]) ok = false;                     // :1545-1546, entry holder
+                    if (ok) {
+                        const int dist = cv.dist(e, i2, qd);
+                        ok = dist <= orb_dist;
+                        ent = ((uint32_t)dist << kIdxBits) | (uint32_t)i2;
                     }
-                    const GroupCols gc = group_cols(clo, clen, gl);
-                    for (int base = 0; base < gc.total; base += kQL) {
-                        const int fi = base + gl;
-                        const int e = gc.index(fi);
-                        const int c1 = fi < gc.total ? e + 1 : e;
-                        bool ok = false;
-                        uint32_t ent = 0;
-                        if (e < c1) {
-                            const int i2 = (int)(L.sort[e] & ((1u << kIdxBits) - 1));
-                            float x, y, ur;
-                            int oct;
-                            cv.get(e, i2, x, y, ur, oct);
-                            ok = !(oct < w.minL || oct > w.maxL);            // chk always set (maxL >= 0)
-                            const float distx = x - w.u, disty = y - w.v;
-                            if (!(fabsf(distx) < w.radius && fabsf(disty) < w.radius)) ok = false;
-                            if (b.cur_has[i2]) ok = false;                     // :1545-1546, entry holder
-                            if (ok) {
-                                const int dist = cv.dist(e, i2, qd);
-                                ok = dist <= orb_dist;
-                                ent = ((uint32_t)dist << kIdxBits) | (uint32_t)i2;
-                            }
-                        }
-                        const uint32_t gb = (uint32_t)(__ballot(ok) >> gsh) & ((1u << kQL) - 1u);
-                        if (ok) {
-                            const int pos = cnt + __popc(gb & ((1u << gl) - 1u));
-                            if (pos < kCQ) lst[pos] = ent;
-                        }
-                        cnt += __popc(gb);
-                    }
-                }
+                    return ok;
+                });
                 if (cnt > kCQ) s_flag[0] = 1;
             }
-            if (q < nq && gl == 0) L.qn[q] = cnt < 0 ? -1 : (min(cnt, kCQ) | 0x10000);
+            if (q < nq && gl == 0) L.qn[q] = qn_word(cnt, true);       // every assignment blocks
         }
     }
     __syncthreads();
@@ -1409,17 +1397,39 @@ int launch_prep(const PrepBufs& b, int F, hipStream_t s, ProfileHook* prof)
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// The LDS form of a matcher workgroup over cs current keypoints and qs second-side points: the
+// current frame staged where that fits the CU's 160 KB (with 256 bytes kept for the kernels'
+// static arrays), else read from global memory, else neither fits (the launchers return -2).
+// bytes = the dynamic LDS of the chosen form.
+struct LdsForm { bool fits, staged; size_t bytes; };
+static LdsForm lds_form(int cs, int qs)
+{
+    constexpr size_t kBudget = 160 * 1024 - 256;
+    const size_t full = match_lds_bytes(cs, qs, true, nullptr), min = match_lds_bytes(cs, qs, false, nullptr);
+    if (full <= kBudget) return {true, true, full};
+    return {min <= kBudget, false, min};
+}
+
+template <class K, class... A>
+static void launch_lds(K kern, dim3 grid, int nt, size_t lds, hipStream_t s, const A&... args)
+{
+    lds_limit_max((const void*)kern);
+    hipLaunchKernelGGL(kern, grid, dim3(nt), lds, s, args...);
+}
+
 int launch_match(const MatchCam& cam, const MatchBufs& b, int P, float th, int bmono, int check_ori,
                  int retry_below, hipStream_t s, ProfileHook* prof)
 {
     if (P <= 0) return 0;
     const int force_seq = coeb_switch("COEB_MATCH_SEQUENTIAL") ? 1 : 0;   // test knob: exact literal path
-    const size_t lds_full = match_lds_bytes(b.cur_stride, b.last_stride, true, nullptr) + 256;
-    const size_t lds_min = match_lds_bytes(b.cur_stride, b.last_stride, false, nullptr) + 256;
+    // (the current frame read from global memory instead, for half the LDS: config A 8.72-8.77 vs
+    // 8.39-8.46 ms per step, D 35.43-35.55 vs 35.17-35.24, profiles/r06/s14)
+    LdsForm f = lds_form(b.cur_stride, b.last_stride);
+    if (!f.fits) return -2;
     // 512-thread workgroups when a pair's LDS fits half a CU (config A: 80.6 KB), so two pairs
     // share a CU and one pair's barrier waits overlap the other's work (k_match 0.355 -> 0.335 ms
     // per 1025-frame launch, profiles/r03/s5/match_nt_ab.txt); otherwise 1024 threads per pair
-    const int nt = lds_full <= 80 * 1024 ? 512 : 1024;     // (1024 always: config A 8.62-8.70 vs 8.35-8.47 ms, r06/s10)
+    const int nt = f.staged && f.bytes + 256 <= 80 * 1024 ? 512 : 1024;   // (1024 always: config A 8.62-8.70 vs 8.35-8.47 ms, r06/s10)
     // Few pairs (a small shard): the candidate lists are built by k_match_lists with nsplit
     // workgroups per pair, so ~256 workgroups share the work instead of P; COEB_MATCH_SPLIT=0
     // turns this off, =N forces N
@@ -1429,38 +1439,26 @@ int launch_match(const MatchCam& cam, const MatchBufs& b, int P, float th, int b
         if (const char* e = coeb_switch("COEB_MATCH_SPLIT")) nsplit = std::max(0, std::min(kMaxSplit, atoi(e)));
         if (nsplit < 2) nsplit = 0;
     }
-    // (the current frame read from global memory instead, for half the LDS: config A 8.72-8.77 vs
-    // 8.39-8.46 ms per step, D 35.43-35.55 vs 35.17-35.24, profiles/r06/s14)
-    bool lds_cur = lds_full <= 160 * 1024;
-    if (!lds_cur && lds_min > 160 * 1024) return -2;
     if (nsplit) {
         // the lists kernel stages the current frame in LDS where it fits; k_match then needs no
         // staged frame (its phases 0-1 run only for the sequential fallback / the retry, then
         // reading the frame from global memory), so it takes a fraction of the LDS and leaves the
         // CU to the other pipeline's kernels
-        const size_t lds_l = match_lds_bytes(b.cur_stride, 0, lds_cur, nullptr);
-        auto gl = [&](auto kern) {
-            lds_limit_max((const void*)kern);
-            hipLaunchKernelGGL(kern, dim3(P, nsplit), dim3(1024), lds_l, s, cam, b, th, bmono);
-        };
+        const size_t lds_l = match_lds_bytes(b.cur_stride, 0, f.staged, nullptr);
         prof_begin(prof, "k_match_lists", s);
-        if (lds_cur) gl(k_match_lists<true, 1024>);
-        else gl(k_match_lists<false, 1024>);
+        if (f.staged) launch_lds(k_match_lists<true, 1024>, dim3(P, nsplit), 1024, lds_l, s, cam, b, th, bmono);
+        else launch_lds(k_match_lists<false, 1024>, dim3(P, nsplit), 1024, lds_l, s, cam, b, th, bmono);
         prof_end(prof, s);
-        lds_cur = false;
+        f = {true, false, match_lds_bytes(b.cur_stride, b.last_stride, false, nullptr)};
     }
-    auto go = [&](auto kern, size_t lds) {
-        lds_limit_max((const void*)kern);
-        const MatchArgs a{cam, b, th, bmono, check_ori, retry_below, force_seq, nsplit};
-        hipLaunchKernelGGL(kern, dim3(P), dim3(nt), lds - 256, s, a);
-    };
+    const MatchArgs a{cam, b, th, bmono, check_ori, retry_below, force_seq, nsplit};
     prof_begin(prof, "k_match", s);
-    if (lds_cur) {
-        if (nt == 512) go(k_match<true, 512>, lds_full);
-        else go(k_match<true, 1024>, lds_full);
+    if (f.staged) {
+        if (nt == 512) launch_lds(k_match<true, 512>, dim3(P), nt, f.bytes, s, a);
+        else launch_lds(k_match<true, 1024>, dim3(P), nt, f.bytes, s, a);
     } else {
-        if (nt == 512) go(k_match<false, 512>, lds_min);
-        else go(k_match<false, 1024>, lds_min);
+        if (nt == 512) launch_lds(k_match<false, 512>, dim3(P), nt, f.bytes, s, a);
+        else launch_lds(k_match<false, 1024>, dim3(P), nt, f.bytes, s, a);
     }
     prof_end(prof, s);
     return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -1472,31 +1470,19 @@ int launch_match_local(const MatchCam& cam, const LocalBufs& b, float th, float 
     if (P <= 0) return 0;
     if (b.cur_n_arr && b.cur_stride >= (1 << kIdxBits)) return -2;
     const int force_seq = coeb_switch("COEB_MATCH_SEQUENTIAL") ? 1 : 0;
-    const int cs = std::max(b.cur_n_arr ? b.cur_stride : b.cur_n, 1), qs = std::max(b.mp_n, 1);
-    const size_t lds_full = match_lds_bytes(cs, qs, true, nullptr) + 256;
-    const size_t lds_min = match_lds_bytes(cs, qs, false, nullptr) + 256;
-    prof_begin(prof, "k_match_local", s);
+    const LdsForm f = lds_form(std::max(b.cur_n_arr ? b.cur_stride : b.cur_n, 1), std::max(b.mp_n, 1));
+    if (!f.fits) return -2;
     // a batch (the configs[4] loop's TrackLocalMap) takes 512 threads per frame: the kernel alone
     // runs longer (0.78 vs 0.51 ms per 1537 frames) but leaves room to the pose / flow kernels it
     // overlaps, and the config-D step is shorter (35.11 vs 35.45-35.60 ms, profiles/r06/s8); one
     // frame from host buffers keeps 1024 (its latency is all there is)
-    auto go = [&](auto k1024, auto k512, size_t lds) {
-        if (P > 1) {
-            lds_limit_max((const void*)k512);
-            hipLaunchKernelGGL(k512, dim3(P), dim3(512), lds - 256, s, cam, b, th, nnratio, force_seq);
-        } else {
-            lds_limit_max((const void*)k1024);
-            hipLaunchKernelGGL(k1024, dim3(P), dim3(1024), lds - 256, s, cam, b, th, nnratio, force_seq);
-        }
+    auto go = [&](auto k1024, auto k512) {
+        if (P > 1) launch_lds(k512, dim3(P), 512, f.bytes, s, cam, b, th, nnratio, force_seq);
+        else launch_lds(k1024, dim3(P), 1024, f.bytes, s, cam, b, th, nnratio, force_seq);
     };
-    if (lds_full <= 160 * 1024) {
-        go(k_match_local<true, 1024>, k_match_local<true, 512>, lds_full);
-    } else if (lds_min <= 160 * 1024) {
-        go(k_match_local<false, 1024>, k_match_local<false, 512>, lds_min);
-    } else {
-        prof_end(prof, s);
-        return -2;
-    }
+    prof_begin(prof, "k_match_local", s);
+    if (f.staged) go(k_match_local<true, 1024>, k_match_local<true, 512>);
+    else go(k_match_local<false, 1024>, k_match_local<false, 512>);
     prof_end(prof, s);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -1505,22 +1491,11 @@ int launch_match_kf(const MatchCam& cam, const KfBufs& b, float th, int orb_dist
                     ProfileHook* prof)
 {
     const int force_seq = coeb_switch("COEB_MATCH_SEQUENTIAL") ? 1 : 0;
-    const int cs = std::max(b.cur_n, 1), qs = std::max(b.kf_n, 1);
-    const size_t lds_full = match_lds_bytes(cs, qs, true, nullptr) + 256;
-    const size_t lds_min = match_lds_bytes(cs, qs, false, nullptr) + 256;
+    const LdsForm f = lds_form(std::max(b.cur_n, 1), std::max(b.kf_n, 1));
+    if (!f.fits) return -2;
     prof_begin(prof, "k_match_kf", s);
-    if (lds_full <= 160 * 1024) {
-        lds_limit_max((const void*)k_match_kf<true>);
-        hipLaunchKernelGGL(k_match_kf<true>, dim3(1), dim3(kMThreads), lds_full - 256, s, cam, b, th, orb_dist, check_ori,
-                           force_seq);
-    } else if (lds_min <= 160 * 1024) {
-        lds_limit_max((const void*)k_match_kf<false>);
-        hipLaunchKernelGGL(k_match_kf<false>, dim3(1), dim3(kMThreads), lds_min - 256, s, cam, b, th, orb_dist, check_ori,
-                           force_seq);
-    } else {
-        prof_end(prof, s);
-        return -2;
-    }
+    if (f.staged) launch_lds(k_match_kf<true>, dim3(1), kMThreads, f.bytes, s, cam, b, th, orb_dist, check_ori, force_seq);
+    else launch_lds(k_match_kf<false>, dim3(1), kMThreads, f.bytes, s, cam, b, th, orb_dist, check_ori, force_seq);
     prof_end(prof, s);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

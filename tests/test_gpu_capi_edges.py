@@ -634,3 +634,38 @@ def test_match_keyframe_unstaged_form(ctx, oracle_mod, ex, crowded_frame):
                                     seed=1, n_distract=0)
     assert len(kf["valid"]) == N_SECOND
     assert keyframe_both(ctx, oracle_mod, ex, k, d, None, kf, synth.motion_pose()) >= N_SECOND // 4
+
+
+def assert_holders_unmatched(m_ref, held, nm):
+    """m_ref: the oracle's mvpMapPoints, which the device result equals index for index."""
+    assert not np.any((m_ref >= 0) & held), np.nonzero((m_ref >= 0) & held)[0][:8]
+    assert nm == int(np.sum(m_ref >= 0)) and nm >= N_SECOND // 8, nm
+
+
+def test_match_localmap_unstaged_holders(ctx, oracle_mod, ex, crowded_frame):
+    """k_match_local<false> with entry holders: the staged form marks them while staging, the
+    unstaged form tests cur_obs per candidate.  Half of the true matches are held."""
+    k, d, ur, last = crowded_frame
+    mp = synth.make_local_map(last["xw"], last["mp_desc"], last["keys_un"]["octave"], synth.motion_pose(), 640, 480,
+                              seed=1, dup_frac=0.0, n_distract=0)
+    obs = np.random.default_rng(41).choice(np.array([-1, 0, 2], np.int32), len(k))
+    obs[:N_SECOND:2] = 2
+    nm = localmap_both(ctx, oracle_mod, ex, k, d, ur, obs, mp, th=5.0)
+    cam_o = oracle_mod.camera(ex, 640, 480, synth.TUM_FX, synth.TUM_FY, synth.TUM_CX, synth.TUM_CY, synth.TUM_BF)
+    _, m_ref = oracle_mod.search_local_map(cam_o, k, d, ur, obs, mp, 5.0, 0.8)
+    assert_holders_unmatched(m_ref, obs > 0, nm)
+
+
+def test_match_keyframe_unstaged_holders(ctx, oracle_mod, ex, crowded_frame):
+    """k_match_kf<false> with entry holders (cur_has): half of the true matches and a tenth of
+    the other keypoints already hold a MapPoint."""
+    k, d, _, last = crowded_frame
+    kf = synth.make_keyframe_points(last["xw"], last["mp_desc"], last["keys_un"]["octave"], last["keys_un"]["angle"],
+                                    seed=1, n_distract=0)
+    has = (np.random.default_rng(43).random(len(k)) < 0.1).astype(np.uint8)
+    has[:N_SECOND:2] = 1
+    Tcw = synth.motion_pose()
+    nm = keyframe_both(ctx, oracle_mod, ex, k, d, has, kf, Tcw)
+    cam_o = oracle_mod.camera(ex, 640, 480, synth.TUM_FX, synth.TUM_FY, synth.TUM_CX, synth.TUM_CY, synth.TUM_BF)
+    _, m_ref = oracle_mod.search_keyframe(cam_o, k, d, has, kf, Tcw, 10.0, 100, True)
+    assert_holders_unmatched(m_ref, has > 0, nm)
