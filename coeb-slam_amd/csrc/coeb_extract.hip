@@ -372,10 +372,64 @@ __device__ __forceinline__ void pyr_rows_out(const uint32_t (&w)[PR_ROWS][4], co
     }
 }
 
+// A band whose row pattern is kPyrPatternMask[kPat] (PyrBand, coeb_plan.hpp).  Consecutive output
+// rows share a source row wherever the pattern steps by 1, so the band reads 9 + popcount(mask)
+// consecutive source rows (10 or 11), not 16: each is loaded once (all loads back to back, the row
+// offset a scalar that steps by the pitch) and its horizontal pass runs once; every output row's
+// vertical pass names its two h rows statically.  The arithmetic per pixel is pyr_rows_out's.
+// !kLast (no tail column, not the level's last column): straight-line, no branch and no exec-mask
+// change between the first load and the last store.  kLast (a level's last strip): tail columns
+// round exactly and the stores are guarded per lane, as pyr_rows_out<true, true>.
+template <int kPat, bool kLast>
+__device__ __forceinline__ void pyr_rows_pattern(__amdgpu_buffer_rsrc_t rs, __amdgpu_buffer_rsrc_t rd, uint32_t wb,
+                                                 uint32_t wb1, const uint32_t (&sel)[2], const uint32_t (&coef)[2],
+                                                 const int* __restrict__ band, int src_off, int dst_off, int sp,
+                                                 int dp, uint32_t cx, int dw, int xs)
+{
+    constexpr uint32_t kMask = kPyrPatternMask[kPat];
+    constexpr int kSrc = PR_ROWS + 1 + __builtin_popcount(kMask);
+    uint32_t h[kSrc][2];
+#pragma unroll
+    for (int j = 0; j < kSrc; j++) {
+        h[j][0] = __builtin_amdgcn_raw_buffer_load_b32(rs, wb, src_off + j * sp, 0);
+        h[j][1] = __builtin_amdgcn_raw_buffer_load_b32(rs, wb1, src_off + j * sp, 0);
+    }
+    int beta[PR_ROWS];
+#pragma unroll
+    for (int r = 0; r < PR_ROWS; r++) beta[r] = band[4 + r];
+#pragma unroll
+    for (int j = 0; j < kSrc; j++) {
+        const uint32_t w0 = h[j][0], w1 = h[j][1];
+#pragma unroll
+        for (int k = 0; k < 2; k++)
+            h[j][k] = __builtin_amdgcn_udot2(as_us2(__builtin_amdgcn_perm(w1, w0, sel[k])), as_us2(coef[k]), 0u, false);
+    }
+#pragma unroll
+    for (int r = 0; r < PR_ROWS; r++) {
+        const int j = r + __builtin_popcount(kMask & ((1u << r) - 1u));     // sy(oy + r) - sy(oy)
+        const uint32_t bb = (uint32_t)beta[r];
+        const uint32_t b0s = (bb << 12) & 0xFFF000u, b1s = (bb >> 4) & 0xFFF000u;
+        uint32_t v[2];
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+            v[k] = (__umulhi(h[j][k] & 0xFFFF0u, b0s) + __umulhi(h[j + 1][k] & 0xFFFF0u, b1s) + 2u) >> 2;
+            if (kLast && (int)cx + k >= xs)
+                v[k] = min((__umul24(h[j][k], bb & 0xFFFFu) + __umul24(h[j + 1][k], bb >> 16) + (1u << 21)) >> 22, 255u);
+        }
+        const uint32_t pr = v[0] | (v[1] << 8);
+        if (!kLast) {
+            __builtin_amdgcn_raw_buffer_store_b16((uint16_t)pr, rd, cx, dst_off + r * dp, 0);
+        } else {
+            if ((int)cx + 1 < dw) __builtin_amdgcn_raw_buffer_store_b16((uint16_t)pr, rd, cx, dst_off + r * dp, 0);
+            else if ((int)cx < dw) __builtin_amdgcn_raw_buffer_store_b8((uint8_t)pr, rd, cx, dst_off + r * dp, 0);
+        }
+    }
+}
+
 __global__ __launch_bounds__(kThreads) void k_pyr_rows(const uint8_t* __restrict__ src, int64_t src_fs, int sp,
                                                        int sh, uint8_t* __restrict__ dst, int64_t dst_fs, int dp,
                                                        int dw, int dh, const int* __restrict__ tab, int xmax, int xs,
-                                                       const int4* __restrict__ yrow)
+                                                       const int4* __restrict__ yrow, const int* __restrict__ bands)
 {
     const int f = blockIdx.z;
     const int oy = (blockIdx.y * kWaves + wave_id()) * PR_ROWS;
@@ -402,15 +456,43 @@ __global__ __launch_bounds__(kThreads) void k_pyr_rows(const uint8_t* __restrict
         __builtin_amdgcn_make_buffer_rsrc((void*)(src + (int64_t)f * src_fs), 0, 0x7fffffff, 0x00020000);
     const __amdgpu_buffer_rsrc_t rd =
         __builtin_amdgcn_make_buffer_rsrc((void*)(dst + (int64_t)f * dst_fs), 0, 0x7fffffff, 0x00020000);
+    const bool edge = ox + PR_COLS > dw - 1, tail = ox + PR_COLS > xs;
+    // Pattern bands: one scalar dispatch per wave on the band's descriptor to the body of its row
+    // pattern; generic bands (a clamped source row, a partial band, a sequence outside
+    // kPyrPatternMask) take the per-row body below.  What was measured: DESIGN.md s4.1.
+    const int* band = bands + (oy / PR_ROWS) * kPyrBandInts;
+    const int4 bd = *reinterpret_cast<const int4*>(band);      // pattern, src_off, dst_off
+    if (bd.x != kPyrBandGeneric) {
+#define COEB_PYR_PATTERN(P, LAST) pyr_rows_pattern<P, LAST>(rs, rd, wb, wb1, sel, coef, band, bd.y, bd.z, sp, dp, cx, dw, xs)
+        if (edge || tail) {
+            switch (bd.x) {
+            case 0: COEB_PYR_PATTERN(0, true); break;
+            case 1: COEB_PYR_PATTERN(1, true); break;
+            case 2: COEB_PYR_PATTERN(2, true); break;
+            case 3: COEB_PYR_PATTERN(3, true); break;
+            default: COEB_PYR_PATTERN(4, true); break;
+            }
+        } else {
+            switch (bd.x) {
+            case 0: COEB_PYR_PATTERN(0, false); break;
+            case 1: COEB_PYR_PATTERN(1, false); break;
+            case 2: COEB_PYR_PATTERN(2, false); break;
+            case 3: COEB_PYR_PATTERN(3, false); break;
+            default: COEB_PYR_PATTERN(4, false); break;
+            }
+        }
+#undef COEB_PYR_PATTERN
+        return;
+    }
     uint32_t w[PR_ROWS][4];
     // (round 6: dealing the grid to the XCDs in contiguous runs (block_xy's mapping over
     // (strip, band, frame)) cuts this kernel's fetch 1.88x -> 1.02x its reads -- round-robin puts
     // neighbouring strips, which share 2-3 source lines per row, on different L2s -- but runs
     // 0.583 vs 0.568 ms per 7-launch pyramid, the step unchanged; a frame-major grid (a frame's
     // blocks on one XCD) fetched 1.06x and ran 0.600 ms.  The pyramid is not bound by these bytes;
-    // profiles/r06/s17..s19.  Reusing the source row that consecutive output rows share, behind wave-uniform
-    // branches, ran 0.669 vs 0.569 ms per 7-launch pyramid: the loads no longer issue back to
-    // back; profiles/r06/s3)
+    // profiles/r06/s17..s19.  Reusing the source row that consecutive output rows share behind a
+    // wave-uniform branch per row ran 0.669 vs 0.569 ms: the loads no longer issue back to back;
+    // profiles/r06/s3.  The pattern bodies above reuse it with one branch per wave instead.)
 #pragma unroll
     for (int r = 0; r < PR_ROWS; r++) {
         const int4 yr = yrow[min(oy + r, dh - 1)];
@@ -419,9 +501,7 @@ __global__ __launch_bounds__(kThreads) void k_pyr_rows(const uint8_t* __restrict
         w[r][2] = __builtin_amdgcn_raw_buffer_load_b32(rs, wb, yr.y, 0);
         w[r][3] = __builtin_amdgcn_raw_buffer_load_b32(rs, wb1, yr.y, 0);
     }
-    (void)dp;
-    const bool edge = ox + PR_COLS > dw - 1;
-    if (ox + PR_COLS > xs) {
+    if (tail) {
         if (edge) pyr_rows_out<true, true>(w, sel, coef, yrow, rd, oy, dh, cx, dw, xs);
         else pyr_rows_out<true, false>(w, sel, coef, yrow, rd, oy, dh, cx, dw, xs);
     } else {
@@ -2571,7 +2651,7 @@ int launch_extract(const Plan& plan, const Plan* d_plan, const ExtractBufs& b, i
             hipLaunchKernelGGL(k_pyr_rows, dim3((g.w + PR_COLS - 1) / PR_COLS, (g.h + kWaves * PR_ROWS - 1) / (kWaves * PR_ROWS), F),
                                dim3(kThreads), 0, s, src, src_fs, gp.pitch, gp.h, b.pyr + g.pyr_off, plan.pyr_stride,
                                g.pitch, g.w, g.h, b.rtab + g.rtab_off, g.xmax, resize_simd_end(g.w),
-                               reinterpret_cast<const int4*>(b.rtab + g.yrow_off));
+                               reinterpret_cast<const int4*>(b.rtab + g.yrow_off), b.rtab + g.band_off);
         } else {
             int tsw, tsh;
             pyr_tile_lds(gp.w, gp.h, g.w, g.h, &tsw, &tsh);

@@ -120,6 +120,23 @@ int resize_tables(int sw, int sh, int dw, int dh, std::vector<int>& tab)
     return xmax;
 }
 
+static_assert(sizeof(PyrBand) == kPyrBandInts * sizeof(int) && kPyrBandInts % 4 == 0, "PyrBand: whole 16-byte table rows");
+
+int pyr_band_pattern(const int* yofs, int oy, int dh, int sh)
+{
+    if (oy + kPyrBandRows > dh) return kPyrBandGeneric;                      // the partial band
+    if (yofs[oy] < 0 || yofs[oy + kPyrBandRows - 1] + 1 > sh - 1) return kPyrBandGeneric;   // a clamped row
+    unsigned mask = 0;
+    for (int i = 0; i + 1 < kPyrBandRows; i++) {
+        const int step = yofs[oy + i + 1] - yofs[oy + i];
+        if (step != 1 && step != 2) return kPyrBandGeneric;
+        mask |= (unsigned)(step - 1) << i;
+    }
+    for (int p = 0; p < kPyrPatterns; p++)
+        if (kPyrPatternMask[p] == mask) return p;
+    return kPyrBandGeneric;
+}
+
 bool make_plan(const Tables& t, int W, int H, int oct_kl_override, Plan& P, std::vector<int>& rtab,
                std::vector<CellDesc>& cells, std::string& err)
 {
@@ -163,6 +180,21 @@ bool make_plan(const Tables& t, int W, int H, int oct_kl_override, Plan& P, std:
                 rtab.push_back(r1 * sp);
                 rtab.push_back(bb);
                 rtab.push_back(dy * g.pitch);
+            }
+            // k_pyr_rows' band descriptors (PyrBand, coeb_plan.hpp)
+            g.band_off = (int)rtab.size();
+            rtab.reserve(rtab.size() + (size_t)kPyrBandInts * ((g.h + kPyrBandRows - 1) / kPyrBandRows));
+            const int* yofs = rtab.data() + g.rtab_off + 2 * g.w;      // stays valid: reserved above
+            for (int oy = 0; oy < g.h; oy += kPyrBandRows) {
+                PyrBand bd;
+                memset(&bd, 0, sizeof bd);
+                bd.pattern = pyr_band_pattern(yofs, oy, g.h, sh);
+                bd.src_off = std::max(0, std::min(yofs[oy], sh - 1)) * sp;
+                bd.dst_off = oy * g.pitch;
+                for (int r = 0; r < kPyrBandRows && oy + r < g.h; r++) bd.beta[r] = yofs[g.h + oy + r];
+                int v[kPyrBandInts];
+                memcpy(v, &bd, sizeof v);
+                rtab.insert(rtab.end(), v, v + kPyrBandInts);
             }
         }
         // FAST cells (ComputeKeyPointsOctTree :795-829)

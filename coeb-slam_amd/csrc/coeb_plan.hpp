@@ -27,6 +27,7 @@ struct LevelGeom {
                            // the pair's 4-byte aligned window start (scale <= 2)
     int yrow_off;          // into resize table (ints): per output row {r0 * sp, r1 * sp, beta, dy * pitch}
                            // (the clamped source rows' byte offsets; sp = the source level's pitch)
+    int band_off;          // into resize table (ints): per 8-row output band one PyrBand descriptor
     int ncols, nrows, wcell, hcell;
     int cell0, ncells;     // range in the cell table (row-major over non-skipped cells)
     int kcap_off, kcap;    // octree key buffers: offset / capacity (u32 entries)
@@ -40,6 +41,28 @@ struct LevelGeom {
     float scale;           // mvScaleFactor[l]
     int size_i;            // (int)(PATCH_SIZE * scale)
     int maxX, maxY;        // octree box: maxBorderX - minBorderX, maxBorderY - minBorderY
+};
+
+// k_pyr_rows' band descriptors.  A band is 8 consecutive output rows oy .. oy + 7 (one wave's
+// rows); its row pattern is the sequence sy(oy + r) - sy(oy), r = 0..7, of the rows' first source
+// rows, written as a 7-bit mask: bit i set where sy(oy + i + 1) - sy(oy + i) is 2 (else it is 1).
+// A band with mask m reads the 9 + popcount(m) consecutive source rows sy(oy) .. sy(oy + 7) + 1.
+// At the cascade's scale of ~1.2 a double step comes every 5 output rows, which leaves the five
+// masks below, one per phase; the real ratios (640/533, ...) drift through them down the image
+// and, where the drift crosses a phase, give another mask in one band (1-2 % of the bands of
+// 640x480 and 1280x960, from whose plans this list is taken).  Such a band is generic, like a
+// band with a clamped source row and a level's last, partial band: the kernel's per-row body.
+constexpr int kPyrBandRows = 8;
+constexpr int kPyrPatterns = 5;
+constexpr unsigned kPyrPatternMask[kPyrPatterns] = {0x10, 0x08, 0x04, 0x42, 0x21};
+constexpr int kPyrBandGeneric = -1;
+constexpr int kPyrBandInts = 12;
+struct PyrBand {           // kPyrBandInts ints in the resize table, 16-byte aligned
+    int pattern;           // index into kPyrPatternMask, or kPyrBandGeneric
+    int src_off;           // byte offset of the band's first source row: clamp(sy(oy)) * sp
+    int dst_off;           // byte offset of the band's first output row: oy * pitch
+    int pad;
+    int beta[kPyrBandRows];   // the rows' beta entries (0 past the level's last row)
 };
 
 struct Plan {
@@ -85,6 +108,10 @@ void gauss_kernel7(int k[7]);
 // cv::resize INTER_LINEAR coefficient tables (imgproc resize.cpp, 8U fixed point) appended to
 // tab as xofs[dw], alpha[dw], yofs[dh], beta[dh]; returns xmax
 int resize_tables(int sw, int sh, int dw, int dh, std::vector<int>& tab);
+// The PyrBand pattern of the output rows oy .. oy + 7 of a level of dh rows resized from sh rows
+// (yofs: resize_tables' unclamped first source rows): an index into kPyrPatternMask, or
+// kPyrBandGeneric.
+int pyr_band_pattern(const int* yofs, int oy, int dh, int sh);
 // The plan of a W x H image with its resize tables / row descriptors (rtab) and FAST cells;
 // false with err set when the size is not supported.  oct_kl_override: 0, or the keys k_octree
 // keeps in LDS per level (clamped to [256, 8192]) in place of the computed count.
