@@ -10,8 +10,9 @@ nmatchesMap, local-map matches, both optimisations' outlier flags, state), then 
 coverage condition that is the reason for its scenario.  Those conditions are computed from the
 ORACLE's results (chain_util.assert_coverage_*), never from device output, so none can pass
 because a kernel is wrong; tests/test_oracle_kat.py asserts the same conditions without a GPU.
-All scenarios are 640x480, F = 8: the kernels' per-frame indexing is fully exercised there,
-bench-size batches are tests/test_gpu_bench_scale.py's business.
+All scenarios are 640x480, F = 8, with the image bounds of an undistorted image: frame sizes
+whose per-frame offsets are no multiple of 4 and other image bounds are
+tests/test_gpu_chain_shapes.py's business, bench-size batches tests/test_gpu_bench_scale.py's.
 """
 import numpy as np
 import pytest

@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-from chain_util import _chain_oracle, _check_chain
+from chain_util import TUM, _chain_oracle, _check_chain, cameras, matcher_pair
 from coeb_front import KEYPOINT_DTYPE, synth
 
 pytestmark = pytest.mark.gpu
@@ -278,11 +278,12 @@ def test_rgbd_preprocess_and_stereo(ctx, oracle_mod):
 
 
 # ------------------------------------------------------------------ matcher
-def match_both(ctx, oracle_mod, ex, cur_k, cur_d, cur_ur, last, Tc, Tl, th=15.0, bmono=False, check_ori=True):
+def match_both(ctx, oracle_mod, ex, cur_k, cur_d, cur_ur, last, Tc, Tl, th=15.0, bmono=False, check_ori=True,
+               cams=None):
+    """cams: (oracle Camera, coeb_front.Camera), default the 640x480 TUM camera."""
     import coeb_front
-    cam_o = oracle_mod.camera(ex, 640, 480, synth.TUM_FX, synth.TUM_FY, synth.TUM_CX, synth.TUM_CY, synth.TUM_BF)
+    cam_o, cam = cams or cameras(oracle_mod, ex, 640, 480, TUM)
     nm_ref, m_ref = oracle_mod.search_by_projection(cam_o, cur_k, cur_d, cur_ur, last, Tc, Tl, th, bmono, check_ori)
-    cam = coeb_front.make_camera(synth.TUM_FX, synth.TUM_FY, synth.TUM_CX, synth.TUM_CY, synth.TUM_BF, 640, 480)
     cur = coeb_front.Frame(cur_k, cur_d, cur_ur, Tcw=Tc)
     lf = coeb_front.Frame(last["keys_un"], last["mp_desc"], Tcw=Tl, outlier=last["outlier"],
                           map_points=dict(world_pos=last["xw"], descriptor=last["mp_desc"],
@@ -302,13 +303,7 @@ def test_golden_match(ctx, oracle_mod, ex):
 
 @pytest.fixture(scope="module")
 def pair(oracle_mod, ex):
-    fr = synth.make_frames(640, 480, 2, seed=77)
-    r0, r1 = ex.extract(fr[0]), ex.extract(fr[1])
-    depth = synth.make_depth(640, 480)
-    last = oracle_mod.mapframe_from_extraction(r0["kps"], r0["desc"], depth, synth.TUM_FX, synth.TUM_FY,
-                                               synth.TUM_CX, synth.TUM_CY, synth.TUM_BF)
-    ur1, _ = oracle_mod.stereo_from_rgbd(r1["kps"], depth, synth.TUM_BF)
-    return r1, ur1, last
+    return matcher_pair(oracle_mod, ex)
 
 
 def test_match_variants(ctx, oracle_mod, ex, pair):
@@ -729,13 +724,12 @@ def test_host_stream_overlapped_equals_device_batch(mode, shared):
 
 
 # ------------------------------------------------------------------ local-map projection search
-def localmap_both(ctx, oracle_mod, ex, cur_k, cur_d, cur_ur, cur_obs, mp, th=3.0, nnratio=0.8):
+def localmap_both(ctx, oracle_mod, ex, cur_k, cur_d, cur_ur, cur_obs, mp, th=3.0, nnratio=0.8, cams=None):
     """coeb_match_localmap vs oracle.search_local_map (ORBmatcher.cc:44-129), bit-exact."""
     import coeb_front
-    cam_o = oracle_mod.camera(ex, 640, 480, synth.TUM_FX, synth.TUM_FY, synth.TUM_CX, synth.TUM_CY, synth.TUM_BF)
+    cam_o, cam = cams or cameras(oracle_mod, ex, 640, 480, TUM)
     obs = np.full(len(cur_k), -1, np.int32) if cur_obs is None else cur_obs
     nm_ref, m_ref = oracle_mod.search_local_map(cam_o, cur_k, cur_d, cur_ur, obs, mp, th, nnratio)
-    cam = coeb_front.make_camera(synth.TUM_FX, synth.TUM_FY, synth.TUM_CX, synth.TUM_CY, synth.TUM_BF, 640, 480)
     F = coeb_front.Frame(cur_k, cur_d, cur_ur)
     if cur_obs is not None:
         F.mvpMapPointObs = cur_obs.copy()
@@ -841,17 +835,16 @@ def test_localmap_crowded_windows(ctx, oracle_mod, ex):
 
 # ------------------------------------------------------------------ relocalisation projection search
 def keyframe_both(ctx, oracle_mod, ex, cur_k, cur_d, cur_has, kf, Tcw, th=10.0, orb_dist=100, check_ori=True,
-                  already=()):
+                  already=(), cams=None):
     """coeb_match_keyframe vs oracle.search_keyframe (ORBmatcher.cc:1473-1600), bit-exact."""
     import coeb_front
-    cam_o = oracle_mod.camera(ex, 640, 480, synth.TUM_FX, synth.TUM_FY, synth.TUM_CX, synth.TUM_CY, synth.TUM_BF)
+    cam_o, cam = cams or cameras(oracle_mod, ex, 640, 480, TUM)
     kv = dict(kf)
     kv["valid"] = kf["valid"].copy()
     for i in already:
         kv["valid"][i] = 0
     has = np.zeros(len(cur_k), np.uint8) if cur_has is None else cur_has
     nm_ref, m_ref = oracle_mod.search_keyframe(cam_o, cur_k, cur_d, has, kv, Tcw, th, orb_dist, check_ori)
-    cam = coeb_front.make_camera(synth.TUM_FX, synth.TUM_FY, synth.TUM_CX, synth.TUM_CY, synth.TUM_BF, 640, 480)
     F = coeb_front.Frame(cur_k, cur_d, Tcw=Tcw)
     if cur_has is not None:
         F.mvpMapPoints = np.where(cur_has > 0, 10 ** 6, -1).astype(np.int32)    # a MapPoint from elsewhere

@@ -193,11 +193,11 @@ def _py_search_local_map(cam, kps, desc, ur, cur_obs, mp, th, nnratio):
     cols, rows = 64, 48
     grid = [[[] for _ in range(rows)] for _ in range(cols)]
     for i, k in enumerate(kps):
-        px = math.floor(abs(float((f32(k["x"]) - cam.min_x) * f32(cam.grid_inv_w))) + 0.5)
-        py = math.floor(abs(float((f32(k["y"]) - cam.min_y) * f32(cam.grid_inv_h))) + 0.5)
-        if (f32(k["x"]) - cam.min_x) < 0:
+        px = math.floor(abs(float((f32(k["x"]) - f32(cam.min_x)) * f32(cam.grid_inv_w))) + 0.5)
+        py = math.floor(abs(float((f32(k["y"]) - f32(cam.min_y)) * f32(cam.grid_inv_h))) + 0.5)
+        if (f32(k["x"]) - f32(cam.min_x)) < 0:
             px = -px
-        if (f32(k["y"]) - cam.min_y) < 0:
+        if (f32(k["y"]) - f32(cam.min_y)) < 0:
             py = -py
         if 0 <= px < cols and 0 <= py < rows:
             grid[px][py].append(i)
@@ -257,11 +257,37 @@ def _py_search_local_map(cam, kps, desc, ur, cur_obs, mp, th, nnratio):
     return nm, np.array(match, np.int32)
 
 
+def _kat_camera(oracle_mod, bounds=None):
+    import chain_util as cu
+    return cu.cameras(oracle_mod, oracle_mod.Extractor(), 640, 480, (535.4, 539.2, 320.1, 247.6, 40.0), bounds)[0]
+
+
+def _kat_bounds():
+    import chain_util as cu
+    return [cu.BOUNDS_INSIDE, cu.BOUNDS_OUTSIDE]
+
+
 @pytest.mark.parametrize("seed", [0, 1, 2])
 def test_search_local_map_oracle_vs_python(oracle_mod, seed):
+    _local_map_case(oracle_mod, seed, _kat_camera(oracle_mod))
+
+
+@pytest.mark.parametrize("bounds", _kat_bounds(), ids=["inside", "outside"])
+def test_search_local_map_oracle_vs_python_image_bounds(oracle_mod, bounds):
+    """The same comparison under the image bounds of a distorted camera, inside and outside the
+    image: the oracle's use of min_x / min_y and of the grid inverses is pinned by the model,
+    not by itself.  Inside bounds leave keypoints off the grid and change the result."""
+    import chain_util as cu
+    cam = _kat_camera(oracle_mod, bounds)
+    assert abs(cam.grid_inv_w - 64.0 / (bounds[1] - bounds[0])) < 1e-6 and abs(cam.grid_inv_w - 64.0 / 640) > 1e-3
+    res = _local_map_case(oracle_mod, 0, cam)
+    if bounds == cu.BOUNDS_INSIDE:
+        ref = _local_map_case(oracle_mod, 0, _kat_camera(oracle_mod))
+        assert any(not np.array_equal(a, b) for a, b in zip(res, ref))
+
+
+def _local_map_case(oracle_mod, seed, cam):
     rng = np.random.default_rng(seed)
-    ex = oracle_mod.Extractor()
-    cam = oracle_mod.camera(ex, 640, 480, 535.4, 539.2, 320.1, 247.6, 40.0)
     n, m = 300, 260
     kps = np.zeros(n, oracle_mod.KP_DTYPE)
     kps["x"] = rng.uniform(0, 640, n)
@@ -283,11 +309,14 @@ def test_search_local_map_oracle_vs_python(oracle_mod, seed):
               level=np.clip(kps["octave"][src] + rng.integers(-1, 2, m), 0, 7).astype(np.int32),
               view_cos=rng.uniform(0.99, 1.0, m).astype(np.float32), descriptor=d,
               observations=rng.choice(np.array([0, 1, 2], np.int32), m).astype(np.int32))
+    out = []
     for th, ratio in ((3.0, 0.8), (1.0, 1.0), (6.0, 0.6)):
         nm, mt = oracle_mod.search_local_map(cam, kps, desc, ur, cur_obs, mp, th, ratio)
         nm_py, mt_py = _py_search_local_map(cam, kps, desc, ur, cur_obs, mp, th, ratio)
         assert nm == nm_py and np.array_equal(mt, mt_py)
         assert nm > 0
+        out.append(mt)
+    return out
 
 
 # ---- relocalisation SearchByProjection: C oracle vs a literal Python loop (ORBmatcher.cc:1473-1600) ----
@@ -392,9 +421,22 @@ def _py_search_keyframe(cam, kps, desc, cur_has, kf, T, th, orb_dist, check_ori)
 
 @pytest.mark.parametrize("seed", [0, 1])
 def test_search_keyframe_oracle_vs_python(oracle_mod, seed):
+    _keyframe_case(oracle_mod, seed, _kat_camera(oracle_mod))
+
+
+@pytest.mark.parametrize("bounds", _kat_bounds(), ids=["inside", "outside"])
+def test_search_keyframe_oracle_vs_python_image_bounds(oracle_mod, bounds):
+    """As test_search_local_map_oracle_vs_python_image_bounds, for the relocalisation search:
+    PosInGrid, the window's cells and the u < min_x / u > max_x rejections of the projection."""
+    import chain_util as cu
+    res = _keyframe_case(oracle_mod, 0, _kat_camera(oracle_mod, bounds))
+    if bounds == cu.BOUNDS_INSIDE:
+        ref = _keyframe_case(oracle_mod, 0, _kat_camera(oracle_mod))
+        assert any(not np.array_equal(a, b) for a, b in zip(res, ref))
+
+
+def _keyframe_case(oracle_mod, seed, cam):
     rng = np.random.default_rng(seed)
-    ex = oracle_mod.Extractor()
-    cam = oracle_mod.camera(ex, 640, 480, 535.4, 539.2, 320.1, 247.6, 40.0)
     n, m = 300, 260
     kps = np.zeros(n, oracle_mod.KP_DTYPE)
     kps["x"] = rng.uniform(0, 640, n)
@@ -418,11 +460,14 @@ def test_search_keyframe_oracle_vs_python(oracle_mod, seed):
     T = np.eye(4, dtype=np.float32)
     T[:3, 3] = [0.01, -0.02, 0.015]
     has = (rng.random(n) < 0.2).astype(np.uint8)
+    out = []
     for th, od, ori in ((10.0, 100, True), (3.0, 64, True), (15.0, 80, False)):
         nm, mt = oracle_mod.search_keyframe(cam, kps, desc, has, kf, T, th, od, ori)
         nm_py, mt_py = _py_search_keyframe(cam, kps, desc, has, kf, T, th, od, ori)
         assert nm == nm_py and np.array_equal(mt, mt_py), (nm, nm_py)
         assert nm > 0
+        out.append(mt)
+    return out
 
 
 # ---- Optimizer::PoseOptimization oracle: properties (g2o absent: parity vs g2o unpinned) ----
@@ -783,6 +828,29 @@ def test_is_in_frustum_kat(oracle_mod):
     assert _frustum(O, cam, T, P, Pn, d * 3, d * 1.3)[0] == 0                        # inside 0.8 * mind
 
 
+def test_is_in_frustum_image_bounds(oracle_mod):
+    """isInFrustum's image test (Frame.cc:467-470) is against the camera's bounds, not the image
+    size: points projecting 10 px inside / outside each bound of the two bounded cameras."""
+    import chain_util as cu
+    O = oracle_mod
+    fx, fy, cx, cy, _ = cu.TUM
+    T = np.eye(4, dtype=np.float32)
+    for bounds in (cu.BOUNDS_INSIDE, cu.BOUNDS_OUTSIDE):
+        cam = cu.cameras(O, O.Extractor(), 640, 480, cu.TUM, bounds)[0]
+        mid = (0.5 * (bounds[0] + bounds[1]), 0.5 * (bounds[2] + bounds[3]))
+        for axis, lo, hi in ((0, bounds[0], bounds[1]), (1, bounds[2], bounds[3])):
+            for edge, sign in ((lo, -1), (hi, 1)):
+                for off, want in ((-10 * sign, 1), (10 * sign, 0)):
+                    uv = list(mid)
+                    uv[axis] = edge + off
+                    P = np.float32([(uv[0] - cx) * 2.0 / fx, (uv[1] - cy) * 2.0 / fy, 2.0])
+                    d = float(np.linalg.norm(P))
+                    got = _frustum(O, cam, T, P, P / d, d * 1.3, d * 0.5)
+                    assert got[0] == want, (bounds, axis, edge, off)
+                    if want:
+                        assert abs(got[1] - uv[0]) < 1e-2 and abs(got[2] - uv[1]) < 1e-2
+
+
 def test_oracle_track_chain_properties(oracle_mod):
     """The configs[4] loop on the oracle (track_frame: motion model + TrackLocalMap) over a
     plain synthetic sequence: every frame tracked, the local map contributes matches, the
@@ -862,3 +930,39 @@ def test_batch_depth_scenarios_reach_their_branches(oracle_mod):
     cu.assert_coverage_perturbed(cu.run_oracle(O, ex, cu.scenario_perturbed(), cu.KCAP, isg)[1], cu.KCAP)
     cu.assert_coverage_lost_neighbours(cu.run_oracle(O, ex, cu.scenario_lost_neighbours(), cu.KCAP, isg)[1], cu.KCAP)
     cu.assert_coverage_grab(cu.run_oracle(O, ex, cu.scenario_grab_rgbd(), cu.KCAP, isg)[1])
+
+
+def test_chain_shape_scenarios_reach_their_branches(oracle_mod):
+    """The scenarios of tests/test_gpu_chain_shapes.py on the oracle alone: the ragged sizes keep
+    every frame tracked on full matches, the Frame constructor's sequence gives T_M points inside
+    a box, each bounded camera changes the matches and the inside ones push keypoints off the
+    grid, and the single-frame matchers' results move with the bounds.  The local map's slot
+    stride only numbers the slots, so any value that holds a frame's keypoints serves here."""
+    import chain_util as cu
+    O = oracle_mod
+    ex = O.Extractor()
+    isg = np.array(ex.p.inv_sigma2[:8], np.float32)
+    F, stride = cu.SHAPES_F, 2048
+    assert all((w * h) % 2 == 1 for w, h in cu.RAGGED_SIZES)
+    assert sorted((f * cu.RAGGED_SIZES[0][0] * cu.RAGGED_SIZES[0][1]) % 4 for f in range(4)) == [0, 1, 2, 3]
+    default = {}
+    for w, h in ((640, 480),) + cu.RAGGED_SIZES:
+        _, default[w, h] = cu.run_oracle(O, ex, cu.scenario_holes(w, h, F), stride, isg, intr=cu.intrinsics(w, h))
+        if (w, h) in cu.RAGGED_SIZES:
+            cu.assert_coverage_ragged(default[w, h])
+    for w, h, bounds, inside in cu.BOUNDED:
+        intr = cu.intrinsics(w, h)
+        ext, res = cu.run_oracle(O, ex, cu.scenario_holes(w, h, F), stride, isg, intr=intr, bounds=bounds)
+        cu.assert_coverage_bounds(cu.cameras(O, ex, w, h, intr, bounds)[0], ext, res, default[w, h], inside)
+    # default bounds: every keypoint has a grid cell, at every size (why the bounded cameras are needed)
+    ext, _ = cu.run_oracle(O, ex, cu.scenario_holes(427, 321, F), stride, isg, intr=cu.intrinsics(427, 321))
+    assert all(cu.coverage_off_grid(cu.cameras(O, ex, 427, 321)[0], e["kps"]) == 0 for e in ext)
+    w, h = cu.RAGGED_SIZES[0]
+    s = cu.scenario_frame_ctor(w, h, F)
+    ext, res = cu.run_oracle(O, ex, s, stride, isg, intr=cu.intrinsics(w, h))
+    cu.assert_coverage_frame_ctor(ext, s["boxes"])
+    assert sum(len(e["kps"]) for e in ext) < sum(len(ex.extract(f)["kps"]) for f in s["frames"])   # the mask removes keypoints
+    r1, ur1, last = cu.matcher_pair(O, ex)
+    mp, kf = cu.matcher_scene(last)
+    bounded = cu.oracle_matchers(O, cu.cameras(O, ex, 640, 480, cu.TUM, cu.BOUNDS_INSIDE)[0], r1, ur1, last, mp, kf)
+    cu.assert_coverage_matchers(bounded, cu.oracle_matchers(O, cu.cameras(O, ex, 640, 480, cu.TUM)[0], r1, ur1, last, mp, kf))
