@@ -346,6 +346,17 @@ def pose_last_stats():
     return it.value, tr.value
 
 
+POSE_BRANCHES = ("quat_branch", "reject_run", "qmax10_rounds", "ldlt_failures", "small_exp", "nonfinite_chi2")
+
+
+def pose_last_branches():
+    """Branch counters of the last pose_optimization call on this thread, as a dict keyed by
+    POSE_BRANCHES (orb_oracle.h: oc_pose_last_branches)."""
+    out = (C.c_int * 6)()
+    lib().oc_pose_last_branches(out)
+    return dict(zip(POSE_BRANCHES, list(out)))
+
+
 def undistort_keypoints(kps, fx, fy, cx, cy, dist):
     """Frame::UndistortKeyPoints (Frame.cc:579-609); dist = (k1, k2, p1, p2, k3)."""
     kps = np.ascontiguousarray(kps)

@@ -1491,9 +1491,11 @@ int oc_local_map_build(const oc_camera* cam, const oc_kfview* kf2, const float T
  * the same operations in the same order. */
 typedef struct { double w, x, y, z, t[3]; } oc_se3;
 
-/* Quaterniond(const Matrix3d&) (Eigen quaternionbase_assign_impl) */
-static void pq_from_R(const double R[9], oc_se3* s)
+/* Quaterniond(const Matrix3d&) (Eigen quaternionbase_assign_impl).  Returns the branch taken:
+ * -1 for trace > 0, else the index of the largest diagonal element. */
+static int pq_from_R(const double R[9], oc_se3* s)
 {
+    int branch = -1;
     double t = (R[0] + R[4]) + R[8];
     double q[4];                     /* x, y, z, w */
     if (t > 0.0) {
@@ -1507,6 +1509,7 @@ static void pq_from_R(const double R[9], oc_se3* s)
         int i = 0;
         if (R[4] > R[0]) i = 1;
         if (R[8] > R[i * 4]) i = 2;
+        branch = i;
         const int j = (i + 1) % 3, k = (j + 1) % 3;
         t = sqrt(((R[i * 4] - R[j * 4]) - R[k * 4]) + 1.0);
         q[i] = 0.5 * t;
@@ -1516,6 +1519,7 @@ static void pq_from_R(const double R[9], oc_se3* s)
         q[k] = (R[k * 3 + i] + R[i * 3 + k]) * t;
     }
     s->x = q[0]; s->y = q[1]; s->z = q[2]; s->w = q[3];
+    return branch;
 }
 
 /* SE3Quat::normalizeRotation: w >= 0, unit norm */
@@ -1579,6 +1583,18 @@ static void pq_sincos(double x, double* sn, double* cs)
     else { *sn = -c0; *cs = s0; }
 }
 
+/* Branch counters of the last oc_pose_optimization call on this thread (a KAT hook): the
+ * quaternion branch of the entry pose (pq_from_R's return), the longest run of rejected trials
+ * in one iteration, optimize() calls ended by qmax == 10, failed LDL' factorisations, small-angle
+ * exponentials, classified edges whose chi2 was not finite. */
+static _Thread_local int pq_br_quat, pq_br_reject_run, pq_br_qmax10, pq_br_ldlt_fail, pq_br_small_exp, pq_br_nonfinite;
+
+void oc_pose_last_branches(int out[6])
+{
+    out[0] = pq_br_quat; out[1] = pq_br_reject_run; out[2] = pq_br_qmax10;
+    out[3] = pq_br_ldlt_fail; out[4] = pq_br_small_exp; out[5] = pq_br_nonfinite;
+}
+
 /* SE3Quat::exp(update), update = (omega, upsilon) */
 static oc_se3 pq_exp(const double u[6])
 {
@@ -1591,6 +1607,7 @@ static oc_se3 pq_exp(const double u[6])
             Om2[i * 3 + j] = (Om[i * 3] * Om[j] + Om[i * 3 + 1] * Om[3 + j]) + Om[i * 3 + 2] * Om[6 + j];
     double R[9], V[9];
     if (theta < 0.00001) {
+        pq_br_small_exp++;
         for (int i = 0; i < 9; i++) R[i] = ((i % 4 == 0 ? 1.0 : 0.0) + Om[i]) + Om2[i];
         for (int i = 0; i < 9; i++) V[i] = R[i];
     } else {
@@ -1618,7 +1635,7 @@ static oc_se3 pq_from_Tcw(const float T[16])
     for (int i = 0; i < 3; i++)
         for (int j = 0; j < 3; j++) R[i * 3 + j] = (double)T[i * 4 + j];
     oc_se3 s;
-    pq_from_R(R, &s);
+    pq_br_quat = pq_from_R(R, &s);
     for (int i = 0; i < 3; i++) s.t[i] = (double)T[i * 4 + 3];
     pq_normalize(&s);
     return s;
@@ -1837,14 +1854,14 @@ static void pq_optimize(const oc_pose_frame* fr, oc_se3* s, const pq_edge* E, in
             ni = 2.0;
         }
         double rho = 0.0;
-        int qmax = 0;
+        int qmax = 0, run = 0;
         do {
             const oc_se3 saved = *s;                     /* push */
             double Hl[36], x[6] = {0, 0, 0, 0, 0, 0};
             memcpy(Hl, H, sizeof(Hl));
             for (int j = 0; j < 6; j++) Hl[j * 6 + j] = Hl[j * 6 + j] + lambda;
             const int ok2 = pq_solve6(Hl, b, x);
-            if (!ok2) for (int j = 0; j < 6; j++) x[j] = 0.0;
+            if (!ok2) { for (int j = 0; j < 6; j++) x[j] = 0.0; pq_br_ldlt_fail++; }
             const oc_se3 up = pq_exp(x);                 /* VertexSE3Expmap::oplusImpl */
             *s = pq_mul(&up, s);
             double tempChi = pq_active_chi2(fr, s, E, ne, active, robust, delta, chi2_last);
@@ -1860,14 +1877,17 @@ static void pq_optimize(const oc_pose_frame* fr, oc_se3* s, const pq_edge* E, in
                 lambda = lambda * sf;
                 ni = 2.0;
                 currentChi = tempChi;
+                run = 0;
             } else {
                 lambda = lambda * ni;
                 ni = ni * 2.0;
                 *s = saved;                              /* pop */
+                if (++run > pq_br_reject_run) pq_br_reject_run = run;
             }
             qmax++;
             pq_stat_trials++;
         } while (rho < 0 && qmax < 10);
+        if (qmax == 10) pq_br_qmax10++;
         if (qmax == 10 || rho == 0) break;               /* Terminate */
     }
 }
@@ -1876,6 +1896,8 @@ int oc_pose_optimization(const oc_pose_frame* fr, float Tcw[16], uint8_t* outlie
 {
     const int n = fr->n;
     pq_stat_iters = pq_stat_trials = 0;
+    pq_br_quat = -1;
+    pq_br_reject_run = pq_br_qmax10 = pq_br_ldlt_fail = pq_br_small_exp = pq_br_nonfinite = 0;
     pq_edge* E = (pq_edge*)malloc(sizeof(pq_edge) * (n > 0 ? n : 1));
     int* idx = (int*)malloc(sizeof(int) * (n > 0 ? n : 1));
     int ne = 0;
@@ -1909,6 +1931,7 @@ int oc_pose_optimization(const oc_pose_frame* fr, float Tcw[16], uint8_t* outlie
         for (int i = 0; i < ne; i++) {
             double c = chi2_last[i];
             if (!active[i]) { double e[3]; c = pq_edge_eval(fr, &s, &E[i], e, NULL); chi2_last[i] = c; }
+            if (!isfinite(c)) pq_br_nonfinite++;
             const double th = E[i].stereo ? (double)chi2Stereo : (double)chi2Mono;
             if (c > th) { outlier[idx[i]] = 1; active[i] = 0; nBad++; }
             else { outlier[idx[i]] = 0; active[i] = 1; }

@@ -240,6 +240,11 @@ typedef struct {
 int oc_pose_optimization(const oc_pose_frame* fr, float Tcw[16], uint8_t* outlier);
 /* LM iterations and trials the last oc_pose_optimization call on this thread ran (test hook). */
 void oc_pose_last_stats(int* iterations, int* trials);
+/* Branch counters of that call (test hook): [0] quaternion branch of the entry pose (-1 trace > 0,
+ * else the largest diagonal's index), [1] longest run of rejected trials in one iteration,
+ * [2] optimize() calls ended by qmax == 10, [3] failed LDL' factorisations, [4] small-angle
+ * SE3Quat::exp uses, [5] classified edges whose chi2 was not finite. */
+void oc_pose_last_branches(int out[6]);
 
 /* Frame::UndistortKeyPoints (Frame.cc:579-609): cv::undistortPoints(mat, mat, mK, mDistCoef,
  * Mat(), mK) of OpenCV 3.4 (cvUndistortPointsInternal, 5 fixed iterations) in double,

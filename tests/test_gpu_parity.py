@@ -915,24 +915,7 @@ def test_keyframe_paths_and_edges(ctx, oracle_mod, ex, pair, monkeypatch):
 
 
 # ------------------------------------------------------------------ Optimizer::PoseOptimization
-def pose_both(ctx, oracle_mod, P, cam=None):
-    """coeb_pose_optimization vs oracle.pose_optimization: pose bits, outlier flags and the
-    inlier count identical (same canonical operations and reduction order)."""
-    import coeb_front
-    isg = np.array(ctx.tables().inv_sigma2[:8], np.float32)
-    intr = P.get("cam", (synth.TUM_FX, synth.TUM_FY, synth.TUM_CX, synth.TUM_CY, synth.TUM_BF))
-    nin_ref, T_ref, out_ref = oracle_mod.pose_optimization(P["kps"], P["has_mp"], P["xw"], P["ur"], isg, *intr,
-                                                           P["Tcw_init"])
-    cam = cam or coeb_front.make_camera(*intr, 640, 480)
-    F = coeb_front.Frame(P["kps"], np.zeros((len(P["kps"]), 32), np.uint8), P["ur"], Tcw=P["Tcw_init"])
-    F.mvpMapPoints = np.where(P["has_mp"] > 0, 0, -1).astype(np.int32)
-    F.mvMapPointPos = P["xw"]
-    nin = coeb_front.Optimizer.PoseOptimization(F, cam, ctx)
-    assert nin == nin_ref, (nin, nin_ref)
-    assert np.array_equal(F.mTcw.view(np.uint32), T_ref.view(np.uint32)), (F.mTcw, T_ref)
-    has = P["has_mp"] > 0
-    assert np.array_equal(F.mvbOutlier[has], out_ref[has])
-    return nin
+from pose_ref import pose_both  # noqa: E402  (the comparison lives with the pose problems)
 
 
 @pytest.mark.parametrize("seed,kw", [(0, {}), (1, {"outlier_frac": 0.4}), (2, {"mono_frac": 1.0}),

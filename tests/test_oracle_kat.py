@@ -966,3 +966,55 @@ def test_chain_shape_scenarios_reach_their_branches(oracle_mod):
     mp, kf = cu.matcher_scene(last)
     bounded = cu.oracle_matchers(O, cu.cameras(O, ex, 640, 480, cu.TUM, cu.BOUNDS_INSIDE)[0], r1, ur1, last, mp, kf)
     cu.assert_coverage_matchers(bounded, cu.oracle_matchers(O, cu.cameras(O, ex, 640, 480, cu.TUM)[0], r1, ur1, last, mp, kf))
+
+
+def test_pose_scenarios_reach_their_branches(oracle_mod):
+    """The directed PoseOptimization problems of tests/pose_ref.py on the oracle alone, by the
+    counters of oc_pose_last_branches: each reaches the branch it is named for, so the GPU tests
+    of test_gpu_pose_paths.py run k_pose's twin of that branch.  The counters leave the results
+    unchanged (the existing bit-parity goldens and tests hold).
+
+    Two notes.  (1) No problem found here has its very FIRST iteration rejected five times: the
+    first Gauss-Newton step from lambda = 1e-5 max|H_jj| is accepted on every start tried (the
+    longest first-iteration run in a search over several hundred starts was 4).  k_pose sizes its speculative
+    rounds from qmax alone (1, 4, then min(4, 10 - qmax)), not from the iteration, so a run of
+    5 to 9 rejections followed by an acceptance in any iteration walks the same rounds:
+    base-seed4 has a longest run of 7 and no qmax == 10 round (rounds of 1, 4 and 4 trials, the
+    last cut at its third trial), as have base-seed3 (k_pose<9>) and n2600 (k_pose<0>); the
+    qmax == 10 problems run the final 1-trial round.  (2) LDL'
+    failures with lambda > 0 ARE reachable: a diverged estimate (init_err 1 rad / 1 m) or a point
+    at z == 0 puts inf or NaN into H."""
+    import pose_ref as R
+    O = oracle_mod
+
+    def run(name):
+        P = R.PROBLEMS[name]()
+        nin, T, outl = R.run_oracle(O, P)
+        return P, nin, T, outl, O.pose_last_branches(), O.pose_last_stats()
+
+    for ax, name in enumerate(["quat0-turn180x", "quat1-turn180y", "quat2-turn180z"]):
+        P, nin, T, outl, br, _ = run(name)
+        assert np.trace(P["Tcw_init"][:3, :3]) < -0.9 and br["quat_branch"] == ax
+        assert nin == 208                                         # and it still converges
+    assert run("base-seed0")[4]["quat_branch"] == -1
+    _, _, _, _, br, st = run("qmax10-init1.0-seed3")
+    assert br["qmax10_rounds"] >= 1 and br["reject_run"] == 10 and br["ldlt_failures"] > 0 and st == (13, 40)
+    for name in ("base-seed4-rejectrun7", "base-seed3", "n2600"):
+        br = run(name)[4]
+        assert 5 <= br["reject_run"] <= 9 and br["qmax10_rounds"] == 0, (name, br)
+    for name, least in (("behind-every7-zinf", 1), ("behind-every7-znan", 1)):
+        P, nin, T, outl, br, _ = run(name)
+        Xc = P["xw"].astype(np.float64) @ P["Tcw_init"][:3, :3].astype(np.float64).T + P["Tcw_init"][:3, 3]
+        has = P["has_mp"] > 0
+        assert Xc[-1, 2] == 0 and (Xc[has, 2] < 0).sum() >= 30    # one at z == 0, many behind
+        assert br["nonfinite_chi2"] >= least and br["ldlt_failures"] > 0
+        assert np.isfinite(T).all()
+    assert outl[-1] == 0 and np.array_equal(T, P["Tcw_init"])     # NaN chi2: `c > th` is false, nothing moves
+    P, nin, T, outl, br, _ = run("behind-every7-zinf")
+    assert outl[-1] == 1 and outl[has & (Xc[:, 2] < 0)].all() and nin > 150
+    _, _, _, _, br, _ = run("base-seed0")
+    assert br["small_exp"] > 0 and br["ldlt_failures"] == 0 and br["nonfinite_chi2"] == 0
+    assert run("n1")[5] == (0, 0) and run("n9")[5][0] <= 10 and run("n10")[5][0] > 10    # the ne < 3, ne < 10 exits
+    sizes = {name: len(R.PROBLEMS[name]()["kps"]) for name in R.PROBLEMS}
+    assert {R.ept_of(n) for n in sizes.values()} == {5, 9, 0}
+    assert (R.ept_of(1280), R.ept_of(1281), R.ept_of(2304), R.ept_of(2305)) == (5, 9, 9, 0)
