@@ -1856,10 +1856,15 @@ int launch_gf(const FlowDev* d, const uint8_t* img, int w, int h, int stride, in
               double min_distance, double k, hipStream_t s, int64_t iz = 0)
 {
     const int P = d->npairs;
-    const int cell = (int)lrint(min_distance);
+    int cell = (int)lrint(min_distance);
     if (cell < 1) return -2;
+    // A coarser grid selects the same corners.  Corners are integer pixels, so two that are closer
+    // than minDistance differ by at most lrint(minDistance) in x and in y and lie in adjacent cells
+    // for every grid step from there up, and the farther pairs a coarser grid brings together pass
+    // the distance test.  So the cells widen until the list heads fit the LDS (minDistance 1 on a
+    // frame of more than ~60k pixels, which the reference's own step would not fit).
+    while (gf_select_lds(w, h, cell, kGfBatch) > 160 * 1024) cell++;
     const size_t lds = gf_select_lds(w, h, cell, kGfBatch);
-    if (lds > 160 * 1024) return -2;
     (void)hipMemset2DAsync(d->rmax, (size_t)d->pz, 0, 4, P, s);      // one word per pair
     (void)hipMemset2DAsync(d->nkeys, (size_t)d->pz, 0, 4, P, s);
     FLOW_LAUNCH(d, "k_gf_response", s, k_gf_response, dim3((w + 4 * kGfCols - 1) / (4 * kGfCols), (h + kGfRows - 1) / kGfRows, P),

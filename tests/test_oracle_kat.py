@@ -1018,3 +1018,51 @@ def test_pose_scenarios_reach_their_branches(oracle_mod):
     sizes = {name: len(R.PROBLEMS[name]()["kps"]) for name in R.PROBLEMS}
     assert {R.ept_of(n) for n in sizes.values()} == {5, 9, 0}
     assert (R.ept_of(1280), R.ept_of(1281), R.ept_of(2304), R.ept_of(2305)) == (5, 9, 9, 0)
+
+
+def test_flow_shape_scenarios_reach_their_branches(oracle_mod):
+    """The shapes and directed points of tests/test_gpu_flow_shapes.py (tests/flow_shapes.py) on the
+    oracle alone.  LK: the sizes' level byte sizes cover every residue mod 4; every directed window
+    is the one intended (the builders check the float32 origin) and is inside or outside its level
+    as named; for win 15, 21 and 22 the level-0 last inside window and its neighbour past the edge
+    are tracked at every size and level count, for win 3 and 7 at least half of the natural
+    corners are; the point at ipx = -win - 1 of level 0 and the points outside the image are
+    rejected.  goodFeaturesToTrack: the hand-made image's eight strongest corners sit on rows and
+    columns 1 and n - 2.  cornerSubPix: the margin points fall on both sides of the 14 px split,
+    some points leave the image and some are reset.  MovingTail: the hand-made SADs are 2120 and
+    2121 and decide as such, and the edge rule keeps 5 and n - 6 and drops 4 and n - 5."""
+    import flow_shapes as fs
+    O = oracle_mod
+    assert sorted({m for v in fs.LEVEL_BYTES_MOD4.values() for m in v}) == [0, 1, 2, 3]
+    for w, h in fs.SIZES:
+        prev, cur = fs.pair(w, h)
+        assert [(lw * lh) % 4 for lw, lh in fs.lk_level_sizes(w, h, 22, 5)] == fs.LEVEL_BYTES_MOD4[w, h]
+        assert len(fs.lk_grid(w, h)) == len(fs.WINS) * len(fs.MAX_LEVELS)
+        for win, ml in fs.lk_grid(w, h):
+            pts, nnat, names, levels, want = fs.lk_points(O, prev, win, ml)
+            assert len(pts) <= 1024
+            _, st = O.lk_pyr(prev, cur, pts, win=win, max_level=ml)
+            fs.assert_lk_coverage(w, h, win, ml, nnat, names, levels, want, st)
+        e = fs.subpix_edge_points(w, h)
+        inner = fs.subpix_is_interior(e, w, h)
+        assert inner.sum() == 8 and len(e) == 24                  # 4 edges + 4 corners at exactly 14.0
+    assert fs.lk_level_sizes(45, 45, 22, 5)[1] == (23, 23)
+    assert len(fs.lk_level_sizes(640, 480, 3, 8)) == 8 and len(fs.lk_level_sizes(1280, 960, 3, 8)) == 9
+    assert len(fs.lk_level_sizes(427, 321, 3, 7)) == 7
+    img = fs.gf_border_image()
+    c = O.good_features(img, min_distance=1.0)
+    assert sorted(map(tuple, c[:8].astype(int).tolist())) == sorted(fs.gf_border_points(img.shape[1], img.shape[0]))
+    assert [im.shape[1] % 4 for im in fs.gf_ragged_images()] == [1, 2, 3]
+    assert [int(np.rint(d)) for d in fs.GF_MIN_DISTANCE] == [1, 3, 8, 8, 20]
+    out, reset = fs.subpix_wander_points(O, fs.subpix_wander_image())
+    assert len(out) >= 2 and len(reset) >= 8
+    for w, h in ((91, 93), (427, 321)):
+        prev, cur, sp, sn, sad = fs.sad_pair(w, h)
+        assert [fs.sad_of(prev, cur, p, q) for p, q in zip(sp, sn)] == [2120, 2121, 2120, 2121]
+        assert O.moving_tail(prev, cur, sp, sn, np.ones(4, np.uint8))[1].tolist() == [1, 0, 1, 0]
+        ep, en, keep = fs.tail_edge_points(w, h)
+        tr = lambda a: a.astype(np.int64)
+        assert sorted(set(tr(ep[:, 0])) | set(tr(en[:, 0]))) [:2] == [4, 5] and {w - 6, w - 5} <= set(tr(ep[:, 0]))
+        assert {4, 5, h - 6, h - 5} <= set(tr(en[:, 1]))
+        st = O.moving_tail(prev, cur, ep, en, np.ones(len(ep), np.uint8))[1]
+        assert np.array_equal(st == 1, keep)                       # their SADs are under the limit
