@@ -1,0 +1,175 @@
+/*
+ * Tracking_coeb.h -- MI355X bodies for Tracking::SearchLocalPoints and Tracking::TrackLocalMap
+ * (src/Tracking.cc:1222-1272, 996-1047): Frame::isInFrustum over the local map, the local-map
+ * projection search, the pose optimisation and the inlier count in one library call with one
+ * synchronisation (coeb_search_local_points / coeb_track_local_map).
+ *
+ * Included from the reference's src/Tracking.cc.  SearchLocalPoints' body becomes
+ *
+ *     int th = 1; if (mSensor == System::RGBD) th = 3;
+ *     if (mCurrentFrame.mnId < mnLastRelocFrameId + 2) th = 5;
+ *     coeb::SearchLocalPoints(mCurrentFrame, mvpLocalMapPoints, th, 0.8f);
+ *
+ * and TrackLocalMap's, after UpdateLocalMap() and up to the decision at :1029, becomes
+ *
+ *     mnMatchesInliers = coeb::TrackLocalMap(mCurrentFrame, mvpLocalMapPoints, th, 0.8f, mbOnlyTracking,
+ *                                            mSensor == System::STEREO);
+ *
+ * What they do, in the reference's terms and in its order:
+ *   - the first loop of :1225-1241: a bad MapPoint of the frame is reset to NULL, the others get
+ *     IncreaseVisible(), mnLastFrameSeen = F.mnId and mbTrackInView = false;
+ *   - snapshot, per local-map point: valid = mnLastFrameSeen != F.mnId && !isBad() (:1249-1252),
+ *     GetWorldPos(), GetNormal(), mfMaxDistance / mfMinDistance (the two getters INTEGRATION.md s3
+ *     adds), GetDescriptor(), Observations(); per keypoint: Observations() and GetWorldPos() of the
+ *     MapPoint it holds (-1 for NULL); positions are read under MapPoint::mGlobalMutex as
+ *     Optimizer::PoseOptimization reads them (Optimizer.cc:276);
+ *   - the call;
+ *   - per valid point what isInFrustum leaves (Frame.cc:447, 493-498): mbTrackInView, and where it
+ *     is set mTrackProjX / Y / XR, mnTrackScaleLevel, mTrackViewCos and IncreaseVisible() (:1256);
+ *   - F.mvpMapPoints[i] = vpLocalMapPoints[match[i]] (ORBmatcher.cc:123);
+ *   - TrackLocalMap only: mvbOutlier for the keypoints that hold a point and F.SetPose (with at
+ *     least 3 of them, Optimizer.cc:361-362, 446-448), then IncreaseFound() for the inliers and, for
+ *     a stereo sensor, NULL for the outliers (:1013-1026); the return value is mnMatchesInliers.
+ */
+#ifndef COEB_ADAPTER_TRACKING_H
+#define COEB_ADAPTER_TRACKING_H
+
+#include <cstring>
+#include <mutex>
+#include <stdexcept>
+#include <vector>
+
+#include <opencv2/core/core.hpp>
+
+#include "coeb_front.h"
+#include "ORBmatcher_coeb.h"
+
+namespace coeb
+{
+
+namespace detail
+{
+
+// pose: TrackLocalMap (search + optimisation + inlier count), else SearchLocalPoints alone.
+// Returns mnMatchesInliers, or nToMatch for the search alone.
+template <class FrameT, class MapPointT>
+inline int track_local_map(FrameT& F, const std::vector<MapPointT*>& vpLocalMapPoints, float th, float nnratio, bool pose,
+                           bool bOnlyTracking, bool bStereo, coeb_ctx* ctx)
+{
+    if (!ctx) ctx = matcher_ctx(F.mnScaleLevels, F.mfScaleFactor);
+    const int N = F.N, nq = (int)vpLocalMapPoints.size();
+    // Do not search map points already matched (:1225-1241)
+    for (int i = 0; i < N; ++i) {
+        MapPointT* pMP = F.mvpMapPoints[i];
+        if (!pMP) continue;
+        if (pMP->isBad()) {
+            F.mvpMapPoints[i] = static_cast<MapPointT*>(nullptr);
+        } else {
+            pMP->IncreaseVisible();
+            pMP->mnLastFrameSeen = F.mnId;
+            pMP->mbTrackInView = false;
+        }
+    }
+    std::vector<uint8_t> valid(nq), desc((size_t)nq * 32);
+    std::vector<float> xw((size_t)nq * 3), normal((size_t)nq * 3), maxd(nq), mind(nq), cxw((size_t)N * 3);
+    std::vector<int32_t> nobs(nq), cobs((size_t)N);
+    {
+        std::unique_lock<std::mutex> lock(MapPointT::mGlobalMutex);
+        for (int q = 0; q < nq; ++q) {
+            MapPointT* pMP = vpLocalMapPoints[q];
+            valid[q] = pMP->mnLastFrameSeen != F.mnId && !pMP->isBad();
+            if (!valid[q]) continue;
+            cv::Mat P = pMP->GetWorldPos(), Pn = pMP->GetNormal();
+            for (int k = 0; k < 3; ++k) {
+                xw[3 * q + k] = P.at<float>(k);
+                normal[3 * q + k] = Pn.at<float>(k);
+            }
+            maxd[q] = pMP->GetMaxDistance();
+            mind[q] = pMP->GetMinDistance();
+            cv::Mat d = pMP->GetDescriptor();
+            std::memcpy(&desc[32 * (size_t)q], d.ptr<uint8_t>(0), 32);
+            nobs[q] = pMP->Observations();
+        }
+        for (int i = 0; i < N; ++i) {
+            MapPointT* pMP = F.mvpMapPoints[i];
+            cobs[i] = pMP ? pMP->Observations() : -1;
+            if (!pMP) continue;
+            cv::Mat P = pMP->GetWorldPos();
+            for (int k = 0; k < 3; ++k) cxw[3 * i + k] = P.at<float>(k);
+        }
+    }
+    coeb_local_points pts{nq, valid.data(), xw.data(), normal.data(), maxd.data(), mind.data(), desc.data(), nobs.data()};
+    cv::Mat curDesc = F.mDescriptors.isContinuous() ? F.mDescriptors : F.mDescriptors.clone();
+    coeb_curframe cur{N, reinterpret_cast<const coeb_keypoint*>(F.mvKeysUn.data()),
+                      curDesc.empty() ? nullptr : curDesc.ptr<uint8_t>(0), F.mvuRight.data()};
+    const coeb_camera cam = frame_camera(F);
+    float T[16];
+    for (int r = 0; r < 4; ++r)
+        for (int k = 0; k < 4; ++k) T[4 * r + k] = F.mTcw.template at<float>(r, k);
+    std::vector<uint8_t> view(nq), outl((size_t)N);
+    std::vector<float> px(nq), py(nq), pxr(nq), vcos(nq);
+    std::vector<int32_t> lvl(nq), match((size_t)N);
+    coeb_track_fields tf{view.data(), px.data(), py.data(), pxr.data(), lvl.data(), vcos.data()};
+    int nToMatch = 0, nlocal = 0, ninl = 0, nMatchesInliers = 0;
+    const int rc = pose ? coeb_track_local_map(ctx, &cam, &cur, cobs.data(), cxw.data(), T, &pts, 0.5f, th, nnratio,
+                                               bOnlyTracking ? 1 : 0, &tf, match.data(), outl.data(), &nToMatch, &nlocal,
+                                               &ninl, &nMatchesInliers)
+                        : coeb_search_local_points(ctx, &cam, &cur, cobs.data(), T, &pts, 0.5f, th, nnratio, &tf,
+                                                   match.data(), &nToMatch, &nlocal);
+    if (rc != COEB_OK) throw std::runtime_error(coeb_last_error(ctx));
+    // Project points in frame and check its visibility (:1246-1259)
+    for (int q = 0; q < nq; ++q) {
+        if (!valid[q]) continue;
+        MapPointT* pMP = vpLocalMapPoints[q];
+        pMP->mbTrackInView = view[q] != 0;
+        if (!view[q]) continue;
+        pMP->mTrackProjX = px[q];
+        pMP->mTrackProjXR = pxr[q];
+        pMP->mTrackProjY = py[q];
+        pMP->mnTrackScaleLevel = lvl[q];
+        pMP->mTrackViewCos = vcos[q];
+        pMP->IncreaseVisible();
+    }
+    for (int i = 0; i < N; ++i)
+        if (match[i] >= 0) F.mvpMapPoints[i] = vpLocalMapPoints[match[i]];
+    if (!pose) return nToMatch;
+    // Optimizer::PoseOptimization's outputs (Optimizer.cc:361-362, 437-448)
+    int nInitial = 0;
+    for (int i = 0; i < N; ++i)
+        if (F.mvpMapPoints[i]) { F.mvbOutlier[i] = outl[i] != 0; nInitial++; }
+    if (nInitial >= 3) {
+        cv::Mat Tcw(4, 4, CV_32F);
+        for (int r = 0; r < 4; ++r)
+            for (int k = 0; k < 4; ++k) Tcw.at<float>(r, k) = T[4 * r + k];
+        F.SetPose(Tcw);
+    }
+    // Update MapPoints Statistics (:1010-1027); the count is the call's
+    for (int i = 0; i < N; ++i) {
+        if (!F.mvpMapPoints[i]) continue;
+        if (!F.mvbOutlier[i]) F.mvpMapPoints[i]->IncreaseFound();
+        else if (bStereo) F.mvpMapPoints[i] = static_cast<MapPointT*>(nullptr);
+    }
+    return nMatchesInliers;
+}
+
+}  // namespace detail
+
+// Tracking::SearchLocalPoints (th as the reference picks it at :1263-1269); returns nToMatch
+template <class FrameT, class MapPointT>
+inline int SearchLocalPoints(FrameT& F, const std::vector<MapPointT*>& vpLocalMapPoints, float th, float nnratio,
+                             coeb_ctx* ctx = nullptr)
+{
+    return detail::track_local_map(F, vpLocalMapPoints, th, nnratio, false, false, false, ctx);
+}
+
+// Tracking::TrackLocalMap between UpdateLocalMap() and the decision at :1029; returns mnMatchesInliers
+template <class FrameT, class MapPointT>
+inline int TrackLocalMap(FrameT& F, const std::vector<MapPointT*>& vpLocalMapPoints, float th, float nnratio,
+                         bool bOnlyTracking, bool bStereo = false, coeb_ctx* ctx = nullptr)
+{
+    return detail::track_local_map(F, vpLocalMapPoints, th, nnratio, true, bOnlyTracking, bStereo, ctx);
+}
+
+}  // namespace coeb
+
+#endif

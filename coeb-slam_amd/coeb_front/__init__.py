@@ -24,6 +24,9 @@
       bow_vector(word, weight, node): BowVector::addWeight + normalize(L1).
   Vocabulary.from_text(text) / from_arrays(...)  ORBVocabulary::loadFromTextFile (src/System.cc:72)
   ORBmatcher.DescriptorDistance(a, b)  src/ORBmatcher.cc:1648-1664
+  search_local_points(ctx, camera, F, cur_observations, LocalPoints, ...) / track_local_map(...)
+      Tracking::SearchLocalPoints from :1246 and Tracking::TrackLocalMap after UpdateLocalMap
+      (src/Tracking.cc:996-1047, 1222-1272) on one host frame, one call each; return dicts.
   Optimizer.PoseOptimization(F, camera)  include/Optimizer.h:47, src/Optimizer.cc:239-451; reads
       F.mvpMapPoints (>= 0: has a MapPoint) and F.mvMapPointPos, sets F.mTcw and F.mvbOutlier.
 
@@ -72,6 +75,7 @@ ABI_SYMBOLS = [
     "coeb_match_bow",
     "coeb_bow_vector", "coeb_kfdb_create", "coeb_kfdb_destroy", "coeb_kfdb_add", "coeb_kfdb_erase", "coeb_kfdb_clear",
     "coeb_kfdb_size", "coeb_kfdb_query", "coeb_match_bow_kfdb",
+    "coeb_search_local_points", "coeb_track_local_map",
 ]
 # COEB_ABI_VERSION of the include/coeb_front.h these argtypes are written against; lib() refuses
 # a library that reports another (tests/test_capi_symbols.py keeps the two equal)
@@ -108,6 +112,17 @@ class LocalMapC(C.Structure):
     _fields_ = [("n", C.c_int32), ("in_view", C.c_void_p), ("proj_x", C.c_void_p), ("proj_y", C.c_void_p),
                 ("proj_xr", C.c_void_p), ("level", C.c_void_p), ("view_cos", C.c_void_p), ("descriptor", C.c_void_p),
                 ("observations", C.c_void_p)]
+
+
+class LocalPointsC(C.Structure):
+    _fields_ = [("n", C.c_int32), ("valid", C.c_void_p), ("world_pos", C.c_void_p), ("normal", C.c_void_p),
+                ("max_distance", C.c_void_p), ("min_distance", C.c_void_p), ("descriptor", C.c_void_p),
+                ("observations", C.c_void_p)]
+
+
+class TrackFieldsC(C.Structure):
+    _fields_ = [("in_view", C.c_void_p), ("proj_x", C.c_void_p), ("proj_y", C.c_void_p), ("proj_xr", C.c_void_p),
+                ("level", C.c_void_p), ("view_cos", C.c_void_p)]
 
 
 class KeyFramePointsC(C.Structure):
@@ -192,6 +207,14 @@ def lib():
                                            C.c_int, C.c_void_p, C.POINTER(C.c_int)]
         L.coeb_match_localmap.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(CurFrameC), C.c_void_p,
                                           C.POINTER(LocalMapC), C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_int)]
+        L.coeb_search_local_points.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(CurFrameC), C.c_void_p,
+                                               C.c_void_p, C.POINTER(LocalPointsC), C.c_float, C.c_float, C.c_float,
+                                               C.POINTER(TrackFieldsC), C.c_void_p, C.POINTER(C.c_int),
+                                               C.POINTER(C.c_int)]
+        L.coeb_track_local_map.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(CurFrameC), C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.POINTER(LocalPointsC), C.c_float, C.c_float, C.c_float,
+                                           C.c_int, C.POINTER(TrackFieldsC), C.c_void_p, C.c_void_p] + \
+            [C.POINTER(C.c_int)] * 4
         L.coeb_match_keyframe.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(CurFrameC), C.c_void_p,
                                           C.POINTER(KeyFramePointsC), C.c_void_p, C.c_float, C.c_int, C.c_int,
                                           C.c_void_p, C.POINTER(C.c_int)]
@@ -902,6 +925,93 @@ class LocalMap:
         return LocalMapC(self.N, *[C.c_void_p(a.ctypes.data) for a in (
             self.mbTrackInView, self.mTrackProjX, self.mTrackProjY, self.mTrackProjXR, self.mnTrackScaleLevel,
             self.mTrackViewCos, self.mDescriptor, self.nObs)])
+
+
+class LocalPoints:
+    """vpLocalMapPoints as Tracking::SearchLocalPoints reads them before isInFrustum
+    (src/Tracking.cc:1246-1259): per point, valid (!isBad() and not seen in this frame),
+    GetWorldPos(), GetNormal(), mfMaxDistance, mfMinDistance, GetDescriptor() and Observations()."""
+
+    def __init__(self, valid, world_pos, normal, max_distance, min_distance, descriptor, observations):
+        self.valid = np.ascontiguousarray(valid, np.uint8)
+        self.N = len(self.valid)
+        self.world_pos = np.ascontiguousarray(world_pos, np.float32).reshape(self.N, 3)
+        self.normal = np.ascontiguousarray(normal, np.float32).reshape(self.N, 3)
+        self.max_distance = np.ascontiguousarray(max_distance, np.float32)
+        self.min_distance = np.ascontiguousarray(min_distance, np.float32)
+        self.descriptor = np.ascontiguousarray(descriptor, np.uint8).reshape(self.N, 32) if self.N else \
+            np.zeros((0, 32), np.uint8)
+        self.observations = np.ascontiguousarray(observations, np.int32)
+        for a in (self.max_distance, self.min_distance, self.observations):
+            if len(a) != self.N:
+                raise ValueError("LocalPoints arrays differ in length")
+
+    def c_struct(self):
+        return LocalPointsC(self.N, *[C.c_void_p(a.ctypes.data) for a in (
+            self.valid, self.world_pos, self.normal, self.max_distance, self.min_distance, self.descriptor,
+            self.observations)])
+
+
+TRACK_FIELDS = (("in_view", np.uint8), ("proj_x", np.float32), ("proj_y", np.float32), ("proj_xr", np.float32),
+                ("level", np.int32), ("view_cos", np.float32))
+
+
+def _track_fields(n):
+    arrs = {k: np.zeros(max(n, 1), dt) for k, dt in TRACK_FIELDS}
+    return arrs, TrackFieldsC(*[C.c_void_p(arrs[k].ctypes.data) for k, _ in TRACK_FIELDS])
+
+
+def search_local_points(ctx, camera, F, cur_observations, points, cos_limit=0.5, th=3.0, nnratio=0.8,
+                        track_fields=True):
+    """Tracking::SearchLocalPoints from the projection loop on (src/Tracking.cc:1246-1271) in one
+    call (coeb_search_local_points): isInFrustum(pMP, cos_limit) with F.mTcw over `points` (a
+    LocalPoints), then SearchByProjection(F, vpLocalMapPoints, th).  cur_observations: i32[F.N]
+    Observations() of the MapPoint each keypoint holds (-1: none), or None.  Returns a dict:
+    the six TRACK_FIELDS arrays (when track_fields), match (i32[F.N], local-map index or -1),
+    n_to_match, nmatches."""
+    cf = CurFrameC(F.N, C.c_void_p(F.mvKeysUn.ctypes.data), C.c_void_p(F.mDescriptors.ctypes.data),
+                   C.c_void_p(F.mvuRight.ctypes.data))
+    cobs = None if cur_observations is None else np.ascontiguousarray(cur_observations, np.int32)
+    T = np.ascontiguousarray(F.mTcw, np.float32)
+    lp = points.c_struct()
+    arrs, tf = _track_fields(points.N) if track_fields else ({}, None)
+    match = np.full(max(F.N, 1), -1, np.int32)
+    ntm, nm = C.c_int(), C.c_int()
+    ctx.check(lib().coeb_search_local_points(ctx.h, C.byref(camera), C.byref(cf), _p(cobs), _p(T), C.byref(lp),
+                                             cos_limit, th, nnratio, C.byref(tf) if tf is not None else None,
+                                             _p(match), C.byref(ntm), C.byref(nm)))
+    res = {k: v[:points.N] for k, v in arrs.items()}
+    res.update(match=match[:F.N], n_to_match=ntm.value, nmatches=nm.value)
+    return res
+
+
+def track_local_map(ctx, camera, F, cur_observations, cur_world_pos, points, cos_limit=0.5, th=3.0, nnratio=0.8,
+                    only_tracking=False, track_fields=True):
+    """Tracking::TrackLocalMap after UpdateLocalMap (src/Tracking.cc:996-1047) in one call
+    (coeb_track_local_map): search_local_points, Optimizer::PoseOptimization from F.mTcw over the
+    keypoints that hold a point afterwards (the search's, else the entry MapPoint:
+    cur_observations[i] >= 0 at cur_world_pos[i]) and mnMatchesInliers.  F is not modified.
+    Returns a dict: the TRACK_FIELDS arrays (when track_fields), match, n_to_match, nlocal,
+    Tcw (4x4 f32), outlier (u8[F.N], 0 where the keypoint holds no point), ninliers_pose,
+    nmatches_inliers."""
+    cf = CurFrameC(F.N, C.c_void_p(F.mvKeysUn.ctypes.data), C.c_void_p(F.mDescriptors.ctypes.data),
+                   C.c_void_p(F.mvuRight.ctypes.data))
+    cobs = None if cur_observations is None else np.ascontiguousarray(cur_observations, np.int32)
+    cxw = None if cur_world_pos is None else np.ascontiguousarray(cur_world_pos, np.float32)
+    T = np.ascontiguousarray(F.mTcw, np.float32).copy()
+    lp = points.c_struct()
+    arrs, tf = _track_fields(points.N) if track_fields else ({}, None)
+    match = np.full(max(F.N, 1), -1, np.int32)
+    outl = np.zeros(max(F.N, 1), np.uint8)
+    ntm, nl, nin, nmi = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    ctx.check(lib().coeb_track_local_map(ctx.h, C.byref(camera), C.byref(cf), _p(cobs), _p(cxw), _p(T), C.byref(lp),
+                                         cos_limit, th, nnratio, int(bool(only_tracking)),
+                                         C.byref(tf) if tf is not None else None, _p(match), _p(outl), C.byref(ntm),
+                                         C.byref(nl), C.byref(nin), C.byref(nmi)))
+    res = {k: v[:points.N] for k, v in arrs.items()}
+    res.update(match=match[:F.N], n_to_match=ntm.value, nlocal=nl.value, Tcw=T.reshape(4, 4), outlier=outl[:F.N],
+               ninliers_pose=nin.value, nmatches_inliers=nmi.value)
+    return res
 
 
 class KeyFramePoints:

@@ -1171,6 +1171,166 @@ int coeb_pose_optimization(coeb_ctx* c, const coeb_camera* cam, const coeb_pose_
 
 namespace {
 
+// Common body of coeb_search_local_points and coeb_track_local_map (pose: the latter).  One staged
+// region on the device: the inputs (uploaded), then the results (counts and pose, uploaded with
+// the inputs as their initial values; matches, outlier flags and track fields, written by the
+// kernels) copied back in one piece, then scratch.
+int track_local_map_impl(coeb_ctx* c, const char* who, bool pose, const coeb_camera* cam, const coeb_curframe* cur,
+                         const int32_t* cur_obs, const float* cur_xw, float* Tcw, const coeb_local_points* mp,
+                         float cos_limit, float th, float nnratio, int only_tracking, const coeb_track_fields* tf,
+                         int32_t* match_out, uint8_t* outlier_out, int* n_to_match, int* nlocal, int* ninliers_pose,
+                         int* nmatches_inliers)
+{
+    const std::string w(who);
+    if (!c || !cam || !cur || !Tcw || !mp || !n_to_match || !nlocal || (pose && (!ninliers_pose || !nmatches_inliers)))
+        return set_err(c, COEB_EINVAL, w + ": invalid arguments");
+    if (cur->n < 0 || mp->n < 0) return set_err(c, COEB_EINVAL, w + ": negative frame / local map size");
+    if (cur->n > kCurMax) return set_err(c, COEB_EINVAL, w + ": more than 4095 current keypoints");
+    const int n = cur->n, nq = mp->n;
+    if (n && (!cur->keys_un || !cur->descriptors || !cur->u_right))
+        return set_err(c, COEB_EINVAL, w + ": missing current-frame arrays");
+    if (nq && (!mp->valid || !mp->world_pos || !mp->normal || !mp->max_distance || !mp->min_distance || !mp->descriptor ||
+               !mp->observations))
+        return set_err(c, COEB_EINVAL, w + ": missing local-map arrays");
+    if (pose && n && cur_obs && !cur_xw) return set_err(c, COEB_EINVAL, w + ": cur_observations without cur_world_pos");
+    // which keypoints take a point is decided on the device: k_pose indexes mvInvLevelSigma2[octave] of any of them
+    for (int i = 0; i < n; i++)
+        if (cur->keys_un[i].octave < 0 || cur->keys_un[i].octave >= c->tab.nlevels)
+            return set_err(c, COEB_EINVAL, w + ": keypoint octave outside the pyramid");
+    // PredictScale's (int)ceil(log(mfMaxDistance / dist) / mfLogScaleFactor) is undefined otherwise
+    for (int q = 0; q < nq; q++) {
+        if (!mp->valid[q]) continue;
+        for (int k = 0; k < 3; k++)
+            if (!std::isfinite(mp->world_pos[3 * q + k]) || !std::isfinite(mp->normal[3 * q + k]))
+                return set_err(c, COEB_EINVAL, w + ": non-finite position or normal of a valid point");
+        const float mn = mp->min_distance[q], mx = mp->max_distance[q];
+        if (!(mn > 0.0f && mn <= mx && std::isfinite(mx)))
+            return set_err(c, COEB_EINVAL, w + ": distance range of a valid point is not 0 < min <= max < inf");
+    }
+    if (!match_local_fits(n, nq)) return set_err(c, COEB_ERANGE, w + ": frame and local map exceed the LDS budget");
+    (void)hipSetDevice(c->device);
+    const int cs = std::max(n, 1), qs = std::max(nq, 1);
+    int rc;
+    uint8_t* dbase;
+    SingleFrameBufs& sf = c->sf;
+    if ((rc = ensure(c, sf.l_list, (size_t)qs * kCQ)) || (rc = ensure(c, sf.l_path, 2)) || (rc = ensure(c, c->ex.err, 4)) ||
+        (rc = ensure(c, sf.p_act, cs)) || (rc = ensure(c, sf.p_edge, cs)) || (rc = ensure(c, sf.p_chi, cs)))
+        return rc;
+    hipStream_t s = main_stream(c);
+    Pack pk;
+    const size_t o_k = pk.add(cur->keys_un, (size_t)n * sizeof(coeb_keypoint)), o_d = pk.add(cur->descriptors, (size_t)n * 32);
+    const size_t o_ur = pk.add(cur->u_right, (size_t)n * 4);
+    const size_t o_co = cur_obs ? pk.add(cur_obs, (size_t)n * 4) : pk.fill(0xff, (size_t)n * 4);   // -1: all NULL
+    const size_t nx = pose ? (size_t)n * 12 : 0;    // entry MapPoint positions: the optimiser's only
+    const size_t o_cx = cur_obs && cur_xw ? pk.add(cur_xw, nx) : pk.fill(0, nx);
+    const size_t o_v = pk.add(mp->valid, (size_t)nq), o_x = pk.add(mp->world_pos, (size_t)nq * 12);
+    const size_t o_nr = pk.add(mp->normal, (size_t)nq * 12), o_mx = pk.add(mp->max_distance, (size_t)nq * 4);
+    const size_t o_mn = pk.add(mp->min_distance, (size_t)nq * 4), o_qd = pk.add(mp->descriptor, (size_t)nq * 32);
+    const size_t o_no = pk.add(mp->observations, (size_t)nq * 4), o_is = pk.add(c->tab.inv_sigma2, sizeof(float) * COEB_MAXL);
+    const size_t o_T0 = pk.add(Tcw, 64);            // the pose the frustum reads
+    // results with an initial value: {n, nToMatch, ninliers_pose, mnMatchesInliers}, the pose k_pose updates
+    const int32_t cnt[4] = {n, 0, 0, 0};
+    const size_t o_cnt = pk.add(cnt, 16), o_T = pk.add(Tcw, 64);
+    // results the kernels write (not uploaded), then scratch
+    size_t at = pk.total;
+    auto take = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 15) & ~(size_t)15; return o; };
+    const size_t o_m = take(((size_t)cs + 1) * 4), o_out = take((size_t)cs);
+    const size_t head_end = at;
+    const size_t o_iv = take((size_t)qs), o_px = take((size_t)qs * 4), o_py = take((size_t)qs * 4), o_pxr = take((size_t)qs * 4);
+    const size_t o_lv = take((size_t)qs * 4), o_vc = take((size_t)qs * 4);
+    const size_t back_end = tf ? at : head_end;
+    const size_t o_h2 = take((size_t)cs), o_x2 = take((size_t)cs * 12), o_o2 = take((size_t)cs * 4);
+    const size_t o_err = at;
+    if ((rc = pinned(c, o_err + 16)) || (rc = ensure(c, c->ex.stage, at)) || (rc = stage_in(c, pk, &dbase, s))) return rc;
+    const MatchCam mcam = make_cam(c, cam);
+    LmBufs t;
+    memset(&t, 0, sizeof(t));
+    int32_t* dcnt = (int32_t*)(dbase + o_cnt);
+    t.mp_n = nq; t.valid = dbase + o_v; t.xw = (const float*)(dbase + o_x); t.normal = (const float*)(dbase + o_nr);
+    t.maxd = (const float*)(dbase + o_mx); t.mind = (const float*)(dbase + o_mn); t.nobs = (const int*)(dbase + o_no);
+    t.Tcw = (const float*)(dbase + o_T0); t.cos_limit = cos_limit;
+    t.in_view = dbase + o_iv; t.px = (float*)(dbase + o_px); t.py = (float*)(dbase + o_py); t.pxr = (float*)(dbase + o_pxr);
+    t.level = (int*)(dbase + o_lv); t.vcos = (float*)(dbase + o_vc); t.n_to_match = dcnt + 1;
+    t.cur_n = n; t.cur_obs = (const int*)(dbase + o_co); t.cur_xw = (const float*)(dbase + o_cx);
+    t.lmatch = (const int*)(dbase + o_m);
+    t.has2 = dbase + o_h2; t.xw2 = (float*)(dbase + o_x2); t.obs2 = (int*)(dbase + o_o2);
+    t.outl = dbase + o_out; t.only_tracking = only_tracking ? 1 : 0; t.ninl = dcnt + 3;
+    if (launch_frustum(mcam, t, s, &c->hook)) return hip_err(c, hipGetLastError(), "launch_frustum");
+    LocalBufs b;
+    b.cur_kps = dbase + o_k; b.cur_desc = dbase + o_d; b.cur_ur = (const float*)(dbase + o_ur);
+    b.cur_obs = t.cur_obs; b.cur_n = n;
+    b.in_view = t.in_view; b.proj_x = t.px; b.proj_y = t.py; b.proj_xr = t.pxr; b.level = t.level; b.view_cos = t.vcos;
+    b.desc = dbase + o_qd; b.nobs = t.nobs; b.mp_n = nq;
+    b.match = (int*)(dbase + o_m); b.nmatch = b.match + cs; b.lists = sf.l_list.p; b.err = c->ex.err.p; b.path = sf.l_path.p;
+    // nothing in view: the search finds nothing (the reference skips it, Tracking.cc:1261)
+    rc = launch_match_local(mcam, b, th, nnratio, s, &c->hook);
+    if (rc == -2) return set_err(c, COEB_ERANGE, w + ": frame and local map exceed the LDS budget");
+    if (rc) return hip_err(c, hipGetLastError(), "launch_match_local");
+    if (pose) {
+        if (launch_lm_pose_prep(t, s, &c->hook)) return hip_err(c, hipGetLastError(), "launch_lm_pose_prep");
+        PoseBufs p;
+        p.n = dcnt; p.has_mp = t.has2; p.xw = t.xw2; p.kps = dbase + o_k; p.ur = (const float*)(dbase + o_ur);
+        p.inv_sigma2 = (const float*)(dbase + o_is); p.Tcw = (float*)(dbase + o_T); p.outlier = dbase + o_out;
+        p.result = dcnt + 2; p.edges = sf.p_edge.p; p.active = sf.p_act.p; p.chi2 = sf.p_chi.p;
+        p.stride = cs; p.timing = nullptr;
+        if (launch_pose(p, 1, cam->fx, cam->fy, cam->cx, cam->cy, cam->bf, s, &c->hook))
+            return hip_err(c, hipGetLastError(), "launch_pose");
+        if (launch_lm_tail(t, s, &c->hook)) return hip_err(c, hipGetLastError(), "launch_lm_tail");
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->pin + o_cnt, dbase + o_cnt, back_end - o_cnt, hipMemcpyDeviceToHost, s));
+    if ((rc = err_word_async(c, c->pin + o_err))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if ((rc = err_word_seen(c, c->pin + o_err))) return rc;
+    int32_t hc[4];
+    memcpy(hc, c->pin + o_cnt, 16);
+    const int32_t* hm = reinterpret_cast<const int32_t*>(c->pin + o_m);
+    if (n && match_out) memcpy(match_out, hm, (size_t)n * 4);
+    *n_to_match = hc[1];
+    *nlocal = hm[cs];
+    if (tf && nq) {
+        if (tf->in_view) memcpy(tf->in_view, c->pin + o_iv, (size_t)nq);
+        if (tf->proj_x) memcpy(tf->proj_x, c->pin + o_px, (size_t)nq * 4);
+        if (tf->proj_y) memcpy(tf->proj_y, c->pin + o_py, (size_t)nq * 4);
+        if (tf->proj_xr) memcpy(tf->proj_xr, c->pin + o_pxr, (size_t)nq * 4);
+        if (tf->level) memcpy(tf->level, c->pin + o_lv, (size_t)nq * 4);
+        if (tf->view_cos) memcpy(tf->view_cos, c->pin + o_vc, (size_t)nq * 4);
+    }
+    if (pose) {
+        memcpy(Tcw, c->pin + o_T, 64);
+        if (outlier_out)
+            for (int i = 0; i < n; i++)
+                if (hm[i] >= 0 || (cur_obs && cur_obs[i] >= 0)) outlier_out[i] = c->pin[o_out + i];
+        *ninliers_pose = hc[2];
+        *nmatches_inliers = hc[3];
+    }
+    return COEB_OK;
+}
+
+}  // namespace
+
+int coeb_search_local_points(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe* cur, const int32_t* cur_obs,
+                             const float Tcw[16], const coeb_local_points* points, float cos_limit, float th,
+                             float nnratio, const coeb_track_fields* track_fields_out, int32_t* match_out,
+                             int* n_to_match, int* nmatches)
+{
+    return track_local_map_impl(c, "coeb_search_local_points", false, cam, cur, cur_obs, nullptr, const_cast<float*>(Tcw),
+                                points, cos_limit, th, nnratio, 0, track_fields_out, match_out, nullptr, n_to_match,
+                                nmatches, nullptr, nullptr);
+}
+
+int coeb_track_local_map(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe* cur, const int32_t* cur_obs,
+                         const float* cur_world_pos, float Tcw[16], const coeb_local_points* points, float cos_limit,
+                         float th, float nnratio, int only_tracking, const coeb_track_fields* track_fields_out,
+                         int32_t* match_out, uint8_t* outlier_out, int* n_to_match, int* nlocal, int* ninliers_pose,
+                         int* nmatches_inliers)
+{
+    return track_local_map_impl(c, "coeb_track_local_map", true, cam, cur, cur_obs, cur_world_pos, Tcw, points, cos_limit,
+                                th, nnratio, only_tracking, track_fields_out, match_out, outlier_out, n_to_match, nlocal,
+                                ninliers_pose, nmatches_inliers);
+}
+
+namespace {
+
 // Common body of the batch matchers.  dT_cur: device poses, pair p (current frame p+1) at
 // dT_cur + 16 p; LastFrame poses are identities (frame p is the world frame of its pair).
 int match_batch_impl(coeb_ctx* c, const float* d_depth, int F, int W, int H, const coeb_camera* cam,
@@ -1828,7 +1988,8 @@ int coeb_debug_read(coeb_ctx* c, const char* what, int f, void* host, size_t byt
         return COEB_OK;
     }
     if (c && what && (std::string(what) == "search_path" || std::string(what) == "localmap_path")) {
-        // {path, iterations} of the last coeb_match_localmap / coeb_match_keyframe
+        // {path, iterations} of the last coeb_match_localmap / coeb_match_keyframe / coeb_search_local_points /
+        // coeb_track_local_map
         if (!c->sf.l_path.p) return COEB_EINVAL;
         if (size_out) *size_out = 8;
         if (host && bytes) {

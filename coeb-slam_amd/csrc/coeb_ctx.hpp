@@ -80,7 +80,8 @@ struct TrackLocalMapBufs {  // coeb_track_local_map_batch_device
                         tl_lnobs, tl_lmatch, tl_nlocal, tl_path, tl_n2, tl_res2, tl_lists);
     }
 };
-struct SingleFrameBufs {    // coeb_match_lastframe (m_*), _localmap / _keyframe (l_*), coeb_pose_optimization (p_*)
+struct SingleFrameBufs {    // coeb_match_lastframe (m_*), _localmap / _keyframe (l_*), coeb_pose_optimization (p_*);
+                            // coeb_search_local_points / coeb_track_local_map use l_list, l_path and p_*
     DevArr<int32_t> m_scr{"m_scr"}, m_qn{"m_qn"}, l_out{"l_out"}, l_path{"l_path"};
     DevArr<uint32_t> l_list{"l_list"};
     DevArr<uint8_t> p_act{"p_act"};

@@ -310,6 +310,26 @@ int launch_tlm_snapshot(const TlmBufs& t, int F, hipStream_t s, ProfileHook* pro
 int launch_tlm_frustum(const MatchCam& cam, const TlmBufs& t, int F, hipStream_t s, ProfileHook* prof);
 int launch_tlm_pose_prep(const TlmBufs& t, int F, hipStream_t s, ProfileHook* prof);
 
+// Tracking::TrackLocalMap on one host frame (coeb_track.hip), every array in device memory:
+// k_frustum -> k_match_local -> k_lm_pose_prep -> k_pose -> k_lm_tail, no host step between.
+struct LmBufs {
+    // vpLocalMapPoints before isInFrustum, and CurrentFrame.mTcw as the call received it
+    int mp_n; const uint8_t* valid; const float* xw; const float* normal; const float* maxd; const float* mind;
+    const int* nobs; const float* Tcw; float cos_limit;
+    // k_frustum: what isInFrustum leaves on the points (zeros where not in view) and nToMatch (zero on entry)
+    uint8_t* in_view; float* px; float* py; float* pxr; int* level; float* vcos; int* n_to_match;
+    // k_lm_pose_prep: mvpMapPoints at entry (cur_obs >= 0: held, position cur_xw) merged with the search's lmatch
+    int cur_n; const int* cur_obs; const float* cur_xw; const int* lmatch;
+    uint8_t* has2; float* xw2; int* obs2;
+    // k_lm_tail: mnMatchesInliers from k_pose's outlier flags (zero on entry)
+    const uint8_t* outl; int only_tracking; int* ninl;
+};
+int launch_frustum(const MatchCam& cam, const LmBufs& t, hipStream_t s, ProfileHook* prof);
+int launch_lm_pose_prep(const LmBufs& t, hipStream_t s, ProfileHook* prof);
+int launch_lm_tail(const LmBufs& t, hipStream_t s, ProfileHook* prof);
+// launch_match_local's LDS-budget verdict for cur_n keypoints and mp_n points, before anything is enqueued
+bool match_local_fits(int cur_n, int mp_n);
+
 // relocalisation projection search (ORBmatcher::SearchByProjection(Frame&, KeyFrame*, set, th, ORBdist))
 struct KfBufs {
     const void* cur_kps; const uint8_t* cur_desc; const uint8_t* cur_has; int cur_n;

@@ -1487,6 +1487,8 @@ int launch_match_local(const MatchCam& cam, const LocalBufs& b, float th, float 
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+bool match_local_fits(int cur_n, int mp_n) { return lds_form(std::max(cur_n, 1), std::max(mp_n, 1)).fits; }
+
 int launch_match_kf(const MatchCam& cam, const KfBufs& b, float th, int orb_dist, int check_ori, hipStream_t s,
                     ProfileHook* prof)
 {

@@ -13,12 +13,17 @@
 // definition and its canonical float forms are DESIGN.md s4.3; oracle/orb_oracle.c
 // (oc_local_map_build) restates them for the parity tests.
 //
-// Launch order: k_tlm_snapshot on the context stream (it copies every batch array the rest
+// The same step on one host frame over an arbitrary local map (coeb_search_local_points /
+// coeb_track_local_map): k_frustum -> k_match_local -> k_lm_pose_prep -> k_pose -> k_lm_tail on
+// the context stream, the map as the caller snapshots it (normals and distance ranges given).
+//
+// Batch launch order: k_tlm_snapshot on the context stream (it copies every batch array the rest
 // reads, so the next batch's extraction may overwrite them), then on the pose stream after
 // the first k_pose: k_tlm_discard -> k_tlm_frustum -> k_match_local -> k_tlm_pose_prep -> k_pose.
 #include <hip/hip_runtime.h>
 
 #include "coeb_internal.hpp"
+#include "coeb_track_dev.hpp"
 
 namespace {
 
@@ -78,26 +83,6 @@ __global__ __launch_bounds__(kT) void k_tlm_discard(TlmBufs t)
     if ((threadIdx.x & 63) == 0 && b) atomicAdd(&t.nmap[f], (int)__popcll(b));
 }
 
-// x = R*X + t (cv::Mat R*X + t: small-matrix float products, the addend added in double)
-__device__ __forceinline__ void gemm_add(const float* T, const float* X, float* out)
-{
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        float v = T[k * 4 + 0] * X[0] + T[k * 4 + 1] * X[1];
-        v = v + T[k * 4 + 2] * X[2];
-        out[k] = (float)((double)v + (double)T[k * 4 + 3]);
-    }
-}
-
-__device__ __forceinline__ double norm3(const float* d)
-{
-    double ss = 0.0;
-    ss += (double)d[0] * (double)d[0];
-    ss += (double)d[1] * (double)d[1];
-    ss += (double)d[2] * (double)d[2];
-    return sqrt(ss);
-}
-
 // ---- k_tlm_frustum: the local map of frame f through Frame::isInFrustum(pMP, 0.5) ----
 __global__ __launch_bounds__(kT) void k_tlm_frustum(MatchCam cam, TlmBufs t)
 {
@@ -136,48 +121,15 @@ __global__ __launch_bounds__(kT) void k_tlm_frustum(MatchCam cam, TlmBufs t)
             const int oct = t.s_oct[g * K + j];
             const float maxd = (float)nd * cam.scale[oct];
             const float mind = maxd / cam.scale[cam.nlevels - 1];
-            // isInFrustum (Frame.cc:445-501)
-            const float* T = t.T1 + (int64_t)f * 16;
-            float Pc[3];
-            gemm_add(T, P, Pc);
-            bool v = !(Pc[2] < 0.0f);
-            float u = 0.f, vv = 0.f, invz = 0.f;
-            if (v) {
-                invz = 1.0f / Pc[2];
-                u = __builtin_fmaf(cam.fx * Pc[0], invz, cam.cx);
-                vv = __builtin_fmaf(cam.fy * Pc[1], invz, cam.cy);
-                if (u < cam.min_x || u > cam.max_x) v = false;
-                if (vv < cam.min_y || vv > cam.max_y) v = false;
-            }
-            float dist = 0.f, viewCos = 0.f;
-            if (v) {
-                float Oc[3];
-                for (int k = 0; k < 3; k++) {                      // mOw = -mRcw.t()*mtcw (GEMM_1_T)
-                    double s = (double)T[0 * 4 + k] * T[3] + (double)T[1 * 4 + k] * T[7];
-                    s = s + (double)T[2 * 4 + k] * T[11];
-                    Oc[k] = (float)(s * -1.0);
-                }
-                const float PO[3] = {P[0] - Oc[0], P[1] - Oc[1], P[2] - Oc[2]};
-                dist = (float)norm3(PO);
-                if (dist < 0.8f * mind || dist > 1.2f * maxd) v = false;
-                if (v) {
-                    double dot = 0.0;
-                    dot += (double)PO[0] * (double)Pn[0];
-                    dot += (double)PO[1] * (double)Pn[1];
-                    dot += (double)PO[2] * (double)Pn[2];
-                    viewCos = (float)(dot / (double)dist);
-                    if (viewCos < 0.5f) v = false;
-                }
-            }
-            if (v) {
-                const float ratio = maxd / dist;                   // PredictScale
-                int s = (int)ceilf((float)log((double)ratio) / cam.log_sf);
-                lvl = s < 0 ? 0 : (s >= cam.nlevels ? cam.nlevels - 1 : s);
+            // isInFrustum (Frame.cc:445-501) with PredictScale
+            const FrustumView fv = is_in_frustum(cam, t.T1 + (int64_t)f * 16, P, Pn, maxd, mind, 0.5f);
+            if (fv.in_view) {
+                lvl = fv.level;
                 in = 1;
-                t.px[o] = u;
-                t.py[o] = vv;
-                t.pxr[o] = __builtin_fmaf(-cam.bf, invz, u);       // u - mbf*invz (fused)
-                t.vcos[o] = viewCos;
+                t.px[o] = fv.u;
+                t.py[o] = fv.v;
+                t.pxr[o] = fv.ur;
+                t.vcos[o] = fv.view_cos;
                 t.lm_xw[3 * o + 0] = P[0];
                 t.lm_xw[3 * o + 1] = P[1];
                 t.lm_xw[3 * o + 2] = P[2];
@@ -228,7 +180,91 @@ __global__ __launch_bounds__(kT) void k_tlm_pose_prep(TlmBufs t)
     }
 }
 
+// ---- k_frustum: an arbitrary local map through Frame::isInFrustum(pMP, cos_limit) ----
+// One thread per point of vpLocalMapPoints (Tracking.cc:1246-1259); the points in view are
+// counted as k_tlm_discard counts: a ballot and one atomic per wave.
+__global__ __launch_bounds__(kT) void k_frustum(MatchCam cam, LmBufs t)
+{
+    const int q = blockIdx.x * kT + threadIdx.x;
+    FrustumView fv{false, 0.f, 0.f, 0.f, 0.f, 0};
+    if (q < t.mp_n) {
+        if (t.valid[q]) {
+            const float P[3] = {t.xw[3 * q + 0], t.xw[3 * q + 1], t.xw[3 * q + 2]};
+            const float Pn[3] = {t.normal[3 * q + 0], t.normal[3 * q + 1], t.normal[3 * q + 2]};
+            fv = is_in_frustum(cam, t.Tcw, P, Pn, t.maxd[q], t.mind[q], t.cos_limit);
+        }
+        t.in_view[q] = fv.in_view ? 1 : 0;
+        t.px[q] = fv.u;
+        t.py[q] = fv.v;
+        t.pxr[q] = fv.ur;
+        t.level[q] = fv.level;
+        t.vcos[q] = fv.view_cos;
+    }
+    const uint64_t b = __ballot(fv.in_view);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(t.n_to_match, (int)__popcll(b));
+}
+
+// ---- k_lm_pose_prep: CurrentFrame.mvpMapPoints for TrackLocalMap's PoseOptimization (:1006) ----
+// A keypoint holds the local-map point the search gave it, else the MapPoint it entered with.
+__global__ __launch_bounds__(kT) void k_lm_pose_prep(LmBufs t)
+{
+    const int i = blockIdx.x * kT + threadIdx.x;
+    if (i >= t.cur_n) return;
+    const int lm = t.lmatch[i];
+    const float* X = nullptr;
+    int obs = -1;
+    if (lm >= 0) {
+        X = t.xw + 3 * (int64_t)lm;
+        obs = t.nobs[lm];
+    } else if (t.cur_obs[i] >= 0) {
+        X = t.cur_xw + 3 * (int64_t)i;
+        obs = t.cur_obs[i];
+    }
+    t.has2[i] = X ? 1 : 0;
+    t.obs2[i] = obs;
+    t.xw2[3 * i + 0] = X ? X[0] : 0.f;
+    t.xw2[3 * i + 1] = X ? X[1] : 0.f;
+    t.xw2[3 * i + 2] = X ? X[2] : 0.f;
+}
+
+// ---- k_lm_tail: mnMatchesInliers (Tracking.cc:1010-1027) ----
+__global__ __launch_bounds__(kT) void k_lm_tail(LmBufs t)
+{
+    const int i = blockIdx.x * kT + threadIdx.x;
+    bool inl = false;
+    if (i < t.cur_n) inl = t.has2[i] && !t.outl[i] && (t.only_tracking || t.obs2[i] > 0);
+    const uint64_t b = __ballot(inl);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(t.ninl, (int)__popcll(b));
+}
+
 }  // namespace
+
+int launch_frustum(const MatchCam& cam, const LmBufs& t, hipStream_t s, ProfileHook* prof)
+{
+    if (t.mp_n <= 0) return 0;                      // n_to_match stays 0
+    prof_begin(prof, "k_frustum", s);
+    hipLaunchKernelGGL(k_frustum, dim3((t.mp_n + kT - 1) / kT), dim3(kT), 0, s, cam, t);
+    prof_end(prof, s);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_lm_pose_prep(const LmBufs& t, hipStream_t s, ProfileHook* prof)
+{
+    if (t.cur_n <= 0) return 0;
+    prof_begin(prof, "k_lm_pose_prep", s);
+    hipLaunchKernelGGL(k_lm_pose_prep, dim3((t.cur_n + kT - 1) / kT), dim3(kT), 0, s, t);
+    prof_end(prof, s);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_lm_tail(const LmBufs& t, hipStream_t s, ProfileHook* prof)
+{
+    if (t.cur_n <= 0) return 0;                     // ninl stays 0
+    prof_begin(prof, "k_lm_tail", s);
+    hipLaunchKernelGGL(k_lm_tail, dim3((t.cur_n + kT - 1) / kT), dim3(kT), 0, s, t);
+    prof_end(prof, s);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 
 int launch_tlm_snapshot(const TlmBufs& t, int F, hipStream_t s, ProfileHook* prof)
 {

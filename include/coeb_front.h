@@ -31,6 +31,15 @@
  *                                      const float th)  include/ORBmatcher.h:46,
  *                                      src/ORBmatcher.cc:44-129 (RadiusByViewingCos :131-137),
  *                                      the call in Tracking::SearchLocalPoints  src/Tracking.cc:1222-1271
+ *   coeb_search_local_points        <- Tracking::SearchLocalPoints from the projection loop on
+ *                                      src/Tracking.cc:1246-1271: Frame::isInFrustum(pMP, 0.5)
+ *                                      src/Frame.cc:445-501 (MapPoint::PredictScale
+ *                                      src/MapPoint.cc:402-417) over vpLocalMapPoints, then the
+ *                                      SearchByProjection above, on one host frame in one call
+ *   coeb_track_local_map            <- Tracking::TrackLocalMap  src/Tracking.cc:996-1047 after
+ *                                      UpdateLocalMap: SearchLocalPoints (:1222-1272, as above),
+ *                                      Optimizer::PoseOptimization (:1006) and mnMatchesInliers
+ *                                      (:1010-1027), one call and one synchronisation
  *   coeb_match_keyframe             <- ORBmatcher::SearchByProjection(Frame&, KeyFrame*,
  *                                      const set<MapPoint*>&, const float th, const int ORBdist)
  *                                      include/ORBmatcher.h:55, src/ORBmatcher.cc:1473-1600
@@ -302,6 +311,64 @@ typedef struct {
 int coeb_match_localmap(coeb_ctx* ctx, const coeb_camera* cam, const coeb_curframe* cur,
                         const int32_t* cur_observations, const coeb_localmap* mp, float th,
                         float nnratio, int32_t* match_out, int* nmatches);
+
+/* vpLocalMapPoints as Tracking::SearchLocalPoints reads them before isInFrustum. */
+typedef struct {
+    int32_t n;                        /* mvpLocalMapPoints.size() */
+    const uint8_t* valid;             /* !isBad() && mnLastFrameSeen != mCurrentFrame.mnId (Tracking.cc:1249-1252) */
+    const float* world_pos;           /* n x 3, GetWorldPos() */
+    const float* normal;              /* n x 3, GetNormal() */
+    const float* max_distance;        /* mfMaxDistance (GetMaxDistanceInvariance() = 1.2f * it) */
+    const float* min_distance;        /* mfMinDistance (GetMinDistanceInvariance() = 0.8f * it) */
+    const uint8_t* descriptor;        /* n x 32, GetDescriptor() */
+    const int32_t* observations;      /* Observations() */
+} coeb_local_points;
+
+/* The fields Frame::isInFrustum leaves on every local-map point (Frame.cc:447, 493-498), each of
+ * length points->n: mbTrackInView, mTrackProjX / Y / XR, mnTrackScaleLevel, mTrackViewCos (zeros
+ * where in_view is 0).  Any pointer may be NULL. */
+typedef struct {
+    uint8_t* in_view;
+    float* proj_x;
+    float* proj_y;
+    float* proj_xr;
+    int32_t* level;
+    float* view_cos;
+} coeb_track_fields;
+
+/* ---- Tracking::SearchLocalPoints from :1246 on ----
+ * isInFrustum(pMP, cos_limit) for every valid point with the pose Tcw (CurrentFrame.mTcw, row-major
+ * 4x4), then SearchByProjection(CurrentFrame, vpLocalMapPoints, th) with nnratio on the points in
+ * view; cur_observations, match_out and *nmatches as coeb_match_localmap's.  *n_to_match = the
+ * number of points in view (nToMatch; with none the search is skipped in the reference and finds
+ * nothing here).  track_fields_out may be NULL.  The frame and the local map together are bounded
+ * by the matcher's on-chip memory: COEB_ERANGE beyond it, as coeb_match_localmap.  COEB_EINVAL,
+ * with nothing written, for a missing array, a valid point with a non-finite position or normal,
+ * or a valid point whose distances are not 0 < min_distance <= max_distance < inf (PredictScale
+ * is undefined there). */
+int coeb_search_local_points(coeb_ctx* ctx, const coeb_camera* cam, const coeb_curframe* cur,
+                             const int32_t* cur_observations, const float Tcw[16],
+                             const coeb_local_points* points, float cos_limit, float th, float nnratio,
+                             const coeb_track_fields* track_fields_out, int32_t* match_out,
+                             int* n_to_match, int* nmatches);
+
+/* ---- Tracking::TrackLocalMap after UpdateLocalMap ----
+ * coeb_search_local_points, then Optimizer::PoseOptimization from Tcw over the keypoints that hold
+ * a point afterwards: the local-map point the search gave them, else the MapPoint they entered
+ * with (cur_observations[i] >= 0, position cur_world_pos[3 i ..], read only there;
+ * cur_observations[i] = -1 where mvpMapPoints[i] is NULL or was bad and reset at :1230-1233).
+ * Tcw holds the optimised pose on return (untouched with < 3 edges, *ninliers_pose = 0 then);
+ * outlier_out[i] (length cur->n, may be NULL) = mvbOutlier[i], written where keypoint i holds a
+ * point; *nlocal = SearchByProjection's return value; *ninliers_pose = PoseOptimization's;
+ * *nmatches_inliers = mnMatchesInliers (:1010-1027): keypoints holding a point that is no outlier
+ * and, unless only_tracking (mbOnlyTracking), has Observations() > 0.  Every keypoint's octave
+ * must lie inside the pyramid. */
+int coeb_track_local_map(coeb_ctx* ctx, const coeb_camera* cam, const coeb_curframe* cur,
+                         const int32_t* cur_observations, const float* cur_world_pos, float Tcw[16],
+                         const coeb_local_points* points, float cos_limit, float th, float nnratio,
+                         int only_tracking, const coeb_track_fields* track_fields_out, int32_t* match_out,
+                         uint8_t* outlier_out, int* n_to_match, int* nlocal, int* ninliers_pose,
+                         int* nmatches_inliers);
 
 /* Map points of a KeyFrame as ORBmatcher.cc:1487-1530 reads them (pKF->GetMapPointMatches()). */
 typedef struct {
@@ -649,7 +716,7 @@ int coeb_device_count(void);
  * rectangles), "plan", "u_right" / "kp_depth" (float mvuRight / mvDepth of the frame's keypoint
  * slots as the last coeb_match_batch_device* computed them from the frame's own depth map;
  * COEB_EINVAL before any batch match), "search_path" (int32 {path, iterations} of the last
- * coeb_match_localmap / coeb_match_keyframe: 0 parallel claims, 1 forced sequential,
+ * coeb_match_localmap / coeb_match_keyframe / coeb_search_local_points / coeb_track_local_map: 0 parallel claims, 1 forced sequential,
  * 2 candidate-list overflow, 3 no convergence; frame ignored; alias "localmap_path").  Copies min(bytes, size); *size_out = full size. */
 int coeb_debug_read(coeb_ctx* ctx, const char* what, int frame, void* host, size_t bytes, size_t* size_out);
 
