@@ -1,8 +1,9 @@
 /*
- * Tracking_coeb.h -- MI355X bodies for Tracking::SearchLocalPoints and Tracking::TrackLocalMap
- * (src/Tracking.cc:1222-1272, 996-1047): Frame::isInFrustum over the local map, the local-map
- * projection search, the pose optimisation and the inlier count in one library call with one
- * synchronisation (coeb_search_local_points / coeb_track_local_map).
+ * Tracking_coeb.h -- MI355X bodies for Tracking::SearchLocalPoints, Tracking::TrackLocalMap
+ * (src/Tracking.cc:1222-1272, 996-1047) and Tracking::TrackReferenceKeyFrame (:823-865, further
+ * down).  The first two: Frame::isInFrustum over the local map, the local-map projection search,
+ * the pose optimisation and the inlier count in one library call with one synchronisation
+ * (coeb_search_local_points / coeb_track_local_map).
  *
  * Included from the reference's src/Tracking.cc.  SearchLocalPoints' body becomes
  *
@@ -30,6 +31,27 @@
  *   - TrackLocalMap only: mvbOutlier for the keypoints that hold a point and F.SetPose (with at
  *     least 3 of them, Optimizer.cc:361-362, 446-448), then IncreaseFound() for the inliers and, for
  *     a stereo sensor, NULL for the outliers (:1013-1026); the return value is mnMatchesInliers.
+ *
+ * Tracking::TrackReferenceKeyFrame (src/Tracking.cc:823-865) becomes
+ *
+ *     return coeb::TrackReferenceKeyFrame(mCurrentFrame, mpReferenceKF, mLastFrame.mTcw, *coeb_voc);
+ *
+ * one library call with one synchronisation (coeb_track_reference_keyframe), where coeb_voc is the
+ * coeb::Vocabulary of BoW_coeb.h.  In the reference's order:
+ *   - snapshot of the KeyFrame: valid = vpMapPointsKF[i] && !isBad(), the mFeatVec node of every
+ *     feature (feature_nodes, ORBmatcher_coeb.h), mDescriptors, mvKeysUn[i].angle, and GetWorldPos()
+ *     / Observations() of the valid MapPoints under MapPoint::mGlobalMutex;
+ *   - ComputeBoW: with F.mBowVec empty the call runs the transform and F.mBowVec / F.mFeatVec are
+ *     filled from its words (coeb_bow_vector: addWeight in feature order, normalize(L1)) and node
+ *     ids; otherwise F.mFeatVec's node ids go in and no vocabulary is touched;
+ *   - nmatches < 15 (:835): false, with F.mvpMapPoints and the pose as they were;
+ *   - F.mvpMapPoints = vpMapPointMatches less the optimiser's outliers, mvbOutlier false on every
+ *     matched keypoint (:854 and Optimizer.cc:302), F.SetPose(the optimised pose; mLastFrame.mTcw
+ *     with fewer than 3 edges);
+ *   - mbTrackInView = false and mnLastFrameSeen = F.mnId on the discarded MapPoints (:855-856);
+ *   - the return value is nmatchesMap >= 10.
+ * The vocabulary's context has ORB-SLAM2's pyramid (8 levels, 1.2): its mvInvLevelSigma2 weigh the
+ * edges, so a frame with another pyramid is refused.
  */
 #ifndef COEB_ADAPTER_TRACKING_H
 #define COEB_ADAPTER_TRACKING_H
@@ -37,11 +59,13 @@
 #include <cstring>
 #include <mutex>
 #include <stdexcept>
+#include <type_traits>
 #include <vector>
 
 #include <opencv2/core/core.hpp>
 
 #include "coeb_front.h"
+#include "BoW_coeb.h"
 #include "ORBmatcher_coeb.h"
 
 namespace coeb
@@ -168,6 +192,84 @@ inline int TrackLocalMap(FrameT& F, const std::vector<MapPointT*>& vpLocalMapPoi
                          bool bOnlyTracking, bool bStereo = false, coeb_ctx* ctx = nullptr)
 {
     return detail::track_local_map(F, vpLocalMapPoints, th, nnratio, true, bOnlyTracking, bStereo, ctx);
+}
+
+// Tracking::TrackReferenceKeyFrame; *pnMatchesMap (when given) receives nmatchesMap
+template <class FrameT, class KeyFrameT, class MatT>
+inline bool TrackReferenceKeyFrame(FrameT& F, KeyFrameT* pRefKF, const MatT& lastTcw, Vocabulary& voc, float nnratio = 0.7f,
+                                   bool bCheckOrientation = true, int levelsup = 4, int* pnMatchesMap = nullptr)
+{
+    auto vpMapPointsKF = pRefKF->GetMapPointMatches();
+    typedef typename std::remove_pointer<typename decltype(vpMapPointsKF)::value_type>::type MapPointT;
+    const bool bTransform = F.mBowVec.empty();      // ComputeBoW's guard (Frame.cc:572)
+    if (bTransform && (F.mnScaleLevels != 8 || F.mfScaleFactor != 1.2f))
+        throw std::runtime_error("coeb::TrackReferenceKeyFrame: the frame's pyramid is not the vocabulary context's");
+    coeb_ctx* ctx = bTransform ? voc.ctx() : matcher_ctx(F.mnScaleLevels, F.mfScaleFactor);
+    const int N = F.N, nq = (int)vpMapPointsKF.size();
+    std::vector<uint8_t> valid(nq);
+    std::vector<float> kang(nq), xw((size_t)nq * 3);
+    std::vector<int32_t> nobs(nq);
+    {
+        std::unique_lock<std::mutex> lock(MapPointT::mGlobalMutex);
+        for (int i = 0; i < nq; ++i) {
+            MapPointT* pMP = vpMapPointsKF[i];
+            valid[i] = pMP && !pMP->isBad();
+            kang[i] = pRefKF->mvKeysUn[i].angle;
+            if (!valid[i]) continue;
+            cv::Mat P = pMP->GetWorldPos();
+            for (int k = 0; k < 3; ++k) xw[3 * i + k] = P.at<float>(k);
+            nobs[i] = pMP->Observations();
+        }
+    }
+    const std::vector<int32_t> knode = feature_nodes(pRefKF->mFeatVec, nq);
+    std::vector<int32_t> fnode;
+    if (!bTransform) {
+        fnode = feature_nodes(F.mFeatVec, N);
+        if (fnode.empty()) fnode.push_back(-1);     // an empty frame still passes "mBowVec is filled": not NULL
+    }
+    cv::Mat kfDesc = pRefKF->mDescriptors.isContinuous() ? pRefKF->mDescriptors : pRefKF->mDescriptors.clone();
+    cv::Mat curDesc = F.mDescriptors.isContinuous() ? F.mDescriptors : F.mDescriptors.clone();
+    coeb_ref_keyframe kf{{nq, valid.data(), kfDesc.empty() ? nullptr : kfDesc.ptr<uint8_t>(0), knode.data(), kang.data()},
+                         xw.data(), nobs.data()};
+    coeb_curframe cur{N, reinterpret_cast<const coeb_keypoint*>(F.mvKeysUn.data()),
+                      curDesc.empty() ? nullptr : curDesc.ptr<uint8_t>(0), F.mvuRight.data()};
+    const coeb_camera cam = frame_camera(F);
+    float T[16];
+    for (int r = 0; r < 4; ++r)
+        for (int k = 0; k < 4; ++k) T[4 * r + k] = lastTcw.template at<float>(r, k);
+    std::vector<int32_t> word((size_t)N), node((size_t)N), match((size_t)N), disc((size_t)N);
+    std::vector<double> weight((size_t)N);
+    int nmatchesBoW = 0, ninl = 0, nmatches = 0, nmatchesMap = 0;
+    const int rc = coeb_track_reference_keyframe(ctx, &cam, &cur, bTransform ? nullptr : fnode.data(), levelsup, &kf, T,
+                                                 nnratio, bCheckOrientation ? 1 : 0, 15, word.data(), node.data(),
+                                                 weight.data(), match.data(), disc.data(), &nmatchesBoW, &ninl, &nmatches,
+                                                 &nmatchesMap);
+    if (rc != COEB_OK) throw std::runtime_error(coeb_last_error(ctx));
+    if (bTransform) {                               // mCurrentFrame.ComputeBoW() (:826)
+        std::vector<int32_t> bw((size_t)N);
+        std::vector<double> bv((size_t)N);
+        int nw = 0;
+        if (coeb_bow_vector(word.data(), weight.data(), node.data(), N, 1, bw.data(), bv.data(), N, &nw) != COEB_OK)
+            throw std::runtime_error("coeb_bow_vector failed");
+        for (int j = 0; j < nw; ++j) F.mBowVec.addWeight(bw[j], bv[j]);
+        for (int i = 0; i < N; ++i)
+            if (node[i] >= 0) F.mFeatVec.addFeature(node[i], (unsigned int)i);
+    }
+    if (pnMatchesMap) *pnMatchesMap = nmatchesMap;
+    if (nmatchesBoW < 15) return false;             // :835
+    cv::Mat Tcw(4, 4, CV_32F);
+    for (int r = 0; r < 4; ++r)
+        for (int k = 0; k < 4; ++k) Tcw.at<float>(r, k) = T[4 * r + k];
+    F.SetPose(Tcw);
+    for (int i = 0; i < N; ++i) {
+        F.mvpMapPoints[i] = match[i] >= 0 ? vpMapPointsKF[match[i]] : static_cast<MapPointT*>(nullptr);
+        if (match[i] >= 0 || disc[i] >= 0) F.mvbOutlier[i] = false;
+        if (disc[i] < 0) continue;
+        MapPointT* pMP = vpMapPointsKF[disc[i]];    // :851-856
+        pMP->mbTrackInView = false;
+        pMP->mnLastFrameSeen = F.mnId;
+    }
+    return nmatchesMap >= 10;
 }
 
 }  // namespace coeb

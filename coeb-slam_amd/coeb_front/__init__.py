@@ -27,6 +27,9 @@
   search_local_points(ctx, camera, F, cur_observations, LocalPoints, ...) / track_local_map(...)
       Tracking::SearchLocalPoints from :1246 and Tracking::TrackLocalMap after UpdateLocalMap
       (src/Tracking.cc:996-1047, 1222-1272) on one host frame, one call each; return dicts.
+  Context.track_reference_keyframe(camera, F, kf, kf_world_pos, kf_observations, ...)
+      Tracking::TrackReferenceKeyFrame (src/Tracking.cc:823-865) on one host frame in one call:
+      ComputeBoW, SearchByBoW, the nmatches gate, PoseOptimization and the outlier discard; a dict.
   Optimizer.PoseOptimization(F, camera)  include/Optimizer.h:47, src/Optimizer.cc:239-451; reads
       F.mvpMapPoints (>= 0: has a MapPoint) and F.mvMapPointPos, sets F.mTcw and F.mvbOutlier.
 
@@ -75,7 +78,7 @@ ABI_SYMBOLS = [
     "coeb_match_bow",
     "coeb_bow_vector", "coeb_kfdb_create", "coeb_kfdb_destroy", "coeb_kfdb_add", "coeb_kfdb_erase", "coeb_kfdb_clear",
     "coeb_kfdb_size", "coeb_kfdb_query", "coeb_match_bow_kfdb",
-    "coeb_search_local_points", "coeb_track_local_map",
+    "coeb_search_local_points", "coeb_track_local_map", "coeb_track_reference_keyframe",
 ]
 # COEB_ABI_VERSION of the include/coeb_front.h these argtypes are written against; lib() refuses
 # a library that reports another (tests/test_capi_symbols.py keeps the two equal)
@@ -138,6 +141,10 @@ class PoseFrameC(C.Structure):
 class BowKeyFrameC(C.Structure):
     _fields_ = [("n", C.c_int32), ("valid", C.c_void_p), ("descriptor", C.c_void_p), ("node_id", C.c_void_p),
                 ("angle", C.c_void_p)]
+
+
+class RefKeyFrameC(C.Structure):
+    _fields_ = [("bow", BowKeyFrameC), ("world_pos", C.c_void_p), ("observations", C.c_void_p)]
 
 
 class BowFrameC(C.Structure):
@@ -215,6 +222,9 @@ def lib():
                                            C.c_void_p, C.POINTER(LocalPointsC), C.c_float, C.c_float, C.c_float,
                                            C.c_int, C.POINTER(TrackFieldsC), C.c_void_p, C.c_void_p] + \
             [C.POINTER(C.c_int)] * 4
+        L.coeb_track_reference_keyframe.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(CurFrameC), C.c_void_p,
+                                                    C.c_int, C.POINTER(RefKeyFrameC), C.c_void_p, C.c_float, C.c_int,
+                                                    C.c_int] + [C.c_void_p] * 5 + [C.POINTER(C.c_int)] * 4
         L.coeb_match_keyframe.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(CurFrameC), C.c_void_p,
                                           C.POINTER(KeyFramePointsC), C.c_void_p, C.c_float, C.c_int, C.c_int,
                                           C.c_void_p, C.POINTER(C.c_int)]
@@ -500,6 +510,44 @@ class Context:
         nd = nfv.value
         return dict(word=word[:n], node=node[:n], weight=weight[:n], fv_node=fv_node[:nd], fv_off=fv_off[:nd + 1],
                     fv_idx=fv_idx[:int(fv_off[nd])])
+
+    def track_reference_keyframe(self, camera, F, kf, kf_world_pos, kf_observations, cur_node_id=None, levelsup=4,
+                                 nnratio=0.7, check_orientation=True, min_matches=15):
+        """Tracking::TrackReferenceKeyFrame (src/Tracking.cc:823-865) in one call
+        (coeb_track_reference_keyframe): ComputeBoW of F.mDescriptors (skipped when cur_node_id, the
+        F.mFeatVec node per feature, is given), SearchByBoW against kf (a BowKeyFrame whose matched
+        MapPoints sit at kf_world_pos with kf_observations), the nmatches < min_matches gate,
+        PoseOptimization from F.mTcw (mLastFrame.mTcw) and the outlier discard.  F is not modified.
+        Returns a dict: word, node, weight (None when cur_node_id was given), match (i32[F.N],
+        KeyFrame index or -1, after the discard), discarded (i32[F.N], the KeyFrame index a discarded
+        keypoint had, else -1), Tcw (4x4 f32), nmatches_bow, ninliers_pose, nmatches, nmatches_map."""
+        n, m = F.N, max(F.N, 1)
+        cf = CurFrameC(n, C.c_void_p(F.mvKeysUn.ctypes.data), C.c_void_p(F.mDescriptors.ctypes.data),
+                       C.c_void_p(F.mvuRight.ctypes.data))
+        xw = np.ascontiguousarray(kf_world_pos, np.float32).reshape(kf.N, 3)
+        nobs = np.ascontiguousarray(kf_observations, np.int32)
+        if len(nobs) != kf.N:
+            raise ValueError("track_reference_keyframe: keyframe arrays differ in length")
+        kc = RefKeyFrameC(BowKeyFrameC(kf.N, *[C.c_void_p(a.ctypes.data) for a in (kf.valid, kf.descriptor, kf.node_id,
+                                                                                 kf.angle)]),
+                          C.c_void_p(xw.ctypes.data), C.c_void_p(nobs.ctypes.data))
+        cnode = None if cur_node_id is None else np.ascontiguousarray(cur_node_id, np.int32)
+        if cnode is not None and len(cnode) != n:
+            raise ValueError("track_reference_keyframe: cur_node_id must have F.N entries")
+        if cnode is not None and n == 0:
+            cnode = np.zeros(1, np.int32)               # an empty frame still says "mBowVec is filled": not NULL
+        word, node, weight = ((np.empty(m, np.int32), np.empty(m, np.int32), np.empty(m, np.float64))
+                              if cnode is None else (None, None, None))
+        T = np.ascontiguousarray(F.mTcw, np.float32).copy()
+        match, disc = np.full(m, -1, np.int32), np.full(m, -1, np.int32)
+        nb, nin, nm, nmap = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        self.check(lib().coeb_track_reference_keyframe(
+            self.h, C.byref(camera), C.byref(cf), _p(cnode), levelsup, C.byref(kc), _p(T), nnratio, int(bool(check_orientation)), int(min_matches), _p(word), _p(node),
+            _p(weight), _p(match), _p(disc), C.byref(nb), C.byref(nin), C.byref(nm), C.byref(nmap)))
+        cut = lambda a: None if a is None else a[:n]
+        return dict(word=cut(word), node=cut(node), weight=cut(weight), match=match[:n], discarded=disc[:n],
+                    Tcw=T.reshape(4, 4), nmatches_bow=nb.value, ninliers_pose=nin.value, nmatches=nm.value,
+                    nmatches_map=nmap.value)
 
     def bow_batch_device(self, levelsup=4):
         """The transform over the last extracted batch; results: batch_bow_results()."""

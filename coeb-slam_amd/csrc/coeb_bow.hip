@@ -188,6 +188,8 @@ __global__ __launch_bounds__(kCsrThreads) void k_bow_rot(int* inout, const int* 
     bow_rot_filter(inout, bin, hist, n, check_ori, inout + cap, s_ind, &s_cnt);
 }
 
+}  // namespace
+
 int launch_transform(coeb_ctx* c, const uint8_t* d_desc, const int* d_counts, int n_fixed, int stride, int F,
                      int levelsup, int* d_word, int* d_node, hipStream_t s)
 {
@@ -205,13 +207,49 @@ int launch_transform(coeb_ctx* c, const uint8_t* d_desc, const int* d_counts, in
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-}  // namespace
-
 void launch_bow_csr(coeb_ctx* c, const CsrArgs& a, int sides, hipStream_t s)
 {
     prof_begin(&c->hook, "k_bow_csr", s);
     hipLaunchKernelGGL(k_bow_csr, dim3(sides), dim3(kCsrThreads), 0, s, a);
     prof_end(&c->hook, s);
+}
+
+// launch_search_by_bow's scratch: the two CSRs (m_csr) and bin[max(cur_n, 1)] + hist[32] (m_aux)
+int bow_search_bufs(coeb_ctx* c, int kf_n, int cur_n)
+{
+    int rc;
+    if ((rc = ensure(c, c->bow.m_csr, (size_t)csr_ints(kf_n) + csr_ints(cur_n)))) return rc;
+    return ensure(c, c->bow.m_aux, (size_t)std::max(cur_n, 1) + 32);
+}
+
+// SearchByBoW on device arrays: k_bow_csr (both sides; it clears the outputs) -> k_match_bow -> k_bow_rot
+int launch_search_by_bow(coeb_ctx* c, const BowSearch& a, float nnratio, int check_ori, hipStream_t s)
+{
+    const int nq = a.kf_n, n = a.cur_n, cs = std::max(n, 1);
+    int* csr_k = c->bow.m_csr.p;
+    int* csr_c = csr_k + csr_ints(nq);
+    int* d_bin = c->bow.m_aux.p;
+    int* d_hist = d_bin + cs;
+    CsrArgs ca{};
+    ca.side[0] = CsrSide{a.kf_node, a.kf_valid, nq, csr_k};
+    ca.side[1] = CsrSide{a.cur_node, nullptr, n, csr_c};
+    ca.clear_m1 = a.match; ca.clear_n = cs + 1;
+    ca.clear_0 = d_bin; ca.clear_0n = cs + 32;
+    launch_bow_csr(c, ca, 2, s);
+    BowMatch bm;
+    bm.kf = BowSide{a.kf_desc, a.kf_angle, csr_k, nq};
+    bm.cur = BowSide{a.cur_desc, a.cur_angle, csr_c, n};
+    bm.nnratio = nnratio; bm.check_ori = check_ori ? 1 : 0;
+    bm.match = a.match; bm.bin = d_bin; bm.hist = d_hist;
+    if (nq && n) {
+        prof_begin(&c->hook, "k_match_bow", s);
+        hipLaunchKernelGGL(k_match_bow, dim3((nq + kBowWaves - 1) / kBowWaves), dim3(kBowThreads), 0, s, bm);
+        prof_end(&c->hook, s);
+    }
+    prof_begin(&c->hook, "k_bow_rot", s);
+    hipLaunchKernelGGL(k_bow_rot, dim3(1), dim3(kCsrThreads), 0, s, a.match, d_bin, d_hist, n, cs, bm.check_ori);
+    prof_end(&c->hook, s);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 extern "C" {
@@ -330,9 +368,7 @@ int coeb_match_bow(coeb_ctx* c, const coeb_bow_keyframe* kf, const coeb_bow_fram
     const int cs = std::max(n, 1);
     BowBufs& bw = c->bow;
     int rc;
-    if ((rc = ensure(c, bw.m_csr, (size_t)csr_ints(nq) + csr_ints(n))) || (rc = ensure(c, bw.m_out, (size_t)cs + 1)) ||
-        (rc = ensure(c, bw.m_aux, (size_t)cs + 32)))
-        return rc;
+    if ((rc = bow_search_bufs(c, nq, n)) || (rc = ensure(c, bw.m_out, (size_t)cs + 1))) return rc;
     hipStream_t s = main_stream(c);
     Pack pk;
     const size_t o_v = pk.add(kf->valid, (size_t)nq), o_kd = pk.add(kf->descriptor, (size_t)nq * 32);
@@ -341,30 +377,12 @@ int coeb_match_bow(coeb_ctx* c, const coeb_bow_keyframe* kf, const coeb_bow_fram
     const size_t o_ca = pk.add(cur->angle, (size_t)n * 4);
     uint8_t* dbase;
     if ((rc = pinned(c, std::max(pk.total, ((size_t)cs + 1) * 4))) || (rc = stage_in(c, pk, &dbase, s))) return rc;
-    int* csr_k = bw.m_csr.p;
-    int* csr_c = csr_k + csr_ints(nq);
-    int* d_bin = bw.m_aux.p;
-    int* d_hist = d_bin + cs;
-    CsrArgs ca{};
-    ca.side[0] = CsrSide{(const int*)(dbase + o_kn), dbase + o_v, nq, csr_k};
-    ca.side[1] = CsrSide{(const int*)(dbase + o_cn), nullptr, n, csr_c};
-    ca.clear_m1 = bw.m_out.p; ca.clear_n = cs + 1;
-    ca.clear_0 = d_bin; ca.clear_0n = cs + 32;
-    launch_bow_csr(c, ca, 2, s);
-    BowMatch bm;
-    bm.kf = BowSide{dbase + o_kd, (const float*)(dbase + o_ka), csr_k, nq};
-    bm.cur = BowSide{dbase + o_cd, (const float*)(dbase + o_ca), csr_c, n};
-    bm.nnratio = nnratio; bm.check_ori = check_orientation ? 1 : 0;
-    bm.match = bw.m_out.p; bm.bin = d_bin; bm.hist = d_hist;
-    if (nq && n) {
-        prof_begin(&c->hook, "k_match_bow", s);
-        hipLaunchKernelGGL(k_match_bow, dim3((nq + kBowWaves - 1) / kBowWaves), dim3(kBowThreads), 0, s, bm);
-        prof_end(&c->hook, s);
-    }
-    prof_begin(&c->hook, "k_bow_rot", s);
-    hipLaunchKernelGGL(k_bow_rot, dim3(1), dim3(kCsrThreads), 0, s, bw.m_out.p, d_bin, d_hist, n, cs, bm.check_ori);
-    prof_end(&c->hook, s);
-    HIP_TRY(c, hipGetLastError());
+    BowSearch bs;
+    bs.kf_valid = dbase + o_v; bs.kf_desc = dbase + o_kd; bs.kf_node = (const int*)(dbase + o_kn);
+    bs.kf_angle = (const float*)(dbase + o_ka); bs.kf_n = nq;
+    bs.cur_desc = dbase + o_cd; bs.cur_node = (const int*)(dbase + o_cn); bs.cur_angle = (const float*)(dbase + o_ca);
+    bs.cur_n = n; bs.match = bw.m_out.p;
+    if (launch_search_by_bow(c, bs, nnratio, check_orientation, s)) return hip_err(c, hipGetLastError(), "launch_search_by_bow");
     int32_t* hout = reinterpret_cast<int32_t*>(c->pin);
     HIP_TRY(c, hipMemcpyAsync(hout, bw.m_out.p, ((size_t)cs + 1) * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));

@@ -1329,6 +1329,113 @@ int coeb_track_local_map(coeb_ctx* c, const coeb_camera* cam, const coeb_curfram
                                 ninliers_pose, nmatches_inliers);
 }
 
+// One staged region on the device, as track_local_map_impl's: the inputs, then the results (counts
+// and pose uploaded as their initial values; matches, discards and the transform's ids written by the
+// kernels) copied back in one piece, then scratch.
+int coeb_track_reference_keyframe(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe* cur,
+                                  const int32_t* cur_node_id, int levelsup, const coeb_ref_keyframe* kf, float Tcw[16],
+                                  float nnratio, int check_orientation, int min_matches, int32_t* word_out,
+                                  int32_t* node_out, double* weight_out, int32_t* match_out, int32_t* discarded_out,
+                                  int* nmatches_bow, int* ninliers_pose, int* nmatches, int* nmatches_map)
+{
+    const std::string w("coeb_track_reference_keyframe");
+    if (!c || !cam || !cur || !kf || !Tcw || !nmatches_bow || !ninliers_pose || !nmatches || !nmatches_map)
+        return set_err(c, COEB_EINVAL, w + ": invalid arguments");
+    const int n = cur->n, nq = kf->bow.n;
+    if (n < 0 || nq < 0) return set_err(c, COEB_EINVAL, w + ": negative frame / keyframe size");
+    if (n > kCurMax || nq > kCurMax) return set_err(c, COEB_EINVAL, w + ": more than 4095 features");
+    const bool transform = !cur_node_id;
+    if (transform && levelsup < 0) return set_err(c, COEB_EINVAL, w + ": negative levelsup");
+    if (transform && !c->voc.k) return set_err(c, COEB_EINVAL, w + ": no vocabulary (coeb_bow_set_vocabulary)");
+    if (n && (!cur->keys_un || !cur->descriptors || !cur->u_right || !match_out))
+        return set_err(c, COEB_EINVAL, w + ": missing current-frame arrays");
+    if (nq && (!kf->bow.valid || !kf->bow.descriptor || !kf->bow.node_id || !kf->bow.angle || !kf->world_pos ||
+               !kf->observations))
+        return set_err(c, COEB_EINVAL, w + ": missing keyframe arrays");
+    // which keypoints take a point is decided on the device: k_pose indexes mvInvLevelSigma2[octave] of any of them
+    std::vector<float> angle((size_t)n);            // F.mvKeys[i].angle = mvKeysUn[i].angle, contiguous for the matcher
+    for (int i = 0; i < n; i++) {
+        if (cur->keys_un[i].octave < 0 || cur->keys_un[i].octave >= c->tab.nlevels)
+            return set_err(c, COEB_EINVAL, w + ": keypoint octave outside the pyramid");
+        angle[i] = cur->keys_un[i].angle;
+    }
+    (void)hipSetDevice(c->device);
+    const int cs = std::max(n, 1);
+    int rc;
+    uint8_t* dbase;
+    SingleFrameBufs& sf = c->sf;
+    if ((rc = bow_search_bufs(c, nq, n)) || (rc = ensure(c, sf.p_act, cs)) || (rc = ensure(c, sf.p_edge, cs)) ||
+        (rc = ensure(c, sf.p_chi, cs)))
+        return rc;
+    hipStream_t s = main_stream(c);
+    Pack pk;
+    const size_t o_k = pk.add(cur->keys_un, (size_t)n * sizeof(coeb_keypoint)), o_d = pk.add(cur->descriptors, (size_t)n * 32);
+    const size_t o_ur = pk.add(cur->u_right, (size_t)n * 4), o_ca = pk.add(angle.data(), (size_t)n * 4);
+    const size_t o_cn = transform ? 0 : pk.add(cur_node_id, (size_t)n * 4);
+    const size_t o_v = pk.add(kf->bow.valid, (size_t)nq), o_kd = pk.add(kf->bow.descriptor, (size_t)nq * 32);
+    const size_t o_kn = pk.add(kf->bow.node_id, (size_t)nq * 4), o_ka = pk.add(kf->bow.angle, (size_t)nq * 4);
+    const size_t o_x = pk.add(kf->world_pos, (size_t)nq * 12), o_no = pk.add(kf->observations, (size_t)nq * 4);
+    const size_t o_is = pk.add(c->tab.inv_sigma2, sizeof(float) * COEB_MAXL);
+    // results with an initial value: {the optimiser's n, ninliers_pose, nmatches, nmatches_map}, the pose k_pose updates
+    const int32_t cnt[4] = {0, 0, 0, 0};
+    const size_t o_cnt = pk.add(cnt, 16), o_T = pk.add(Tcw, 64);
+    // results the kernels write (not uploaded), then scratch
+    size_t at = pk.total;
+    auto take = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 15) & ~(size_t)15; return o; };
+    const size_t o_m = take(((size_t)cs + 1) * 4), o_dis = take((size_t)cs * 4);
+    const size_t o_wd = take(transform ? (size_t)cs * 4 : 0), o_nd = take(transform ? (size_t)cs * 4 : 0);
+    const size_t back_end = at;
+    const size_t o_has = take((size_t)cs), o_xw = take((size_t)cs * 12), o_out = take((size_t)cs);
+    if ((rc = pinned(c, at)) || (rc = ensure(c, c->ex.stage, at)) || (rc = stage_in(c, pk, &dbase, s))) return rc;
+    int32_t* dcnt = (int32_t*)(dbase + o_cnt);
+    if (transform && n &&
+        launch_transform(c, dbase + o_d, nullptr, n, n, 1, levelsup, (int*)(dbase + o_wd), (int*)(dbase + o_nd), s))
+        return hip_err(c, hipGetLastError(), "k_bow_transform");
+    BowSearch bs;
+    bs.kf_valid = dbase + o_v; bs.kf_desc = dbase + o_kd; bs.kf_node = (const int*)(dbase + o_kn);
+    bs.kf_angle = (const float*)(dbase + o_ka); bs.kf_n = nq;
+    bs.cur_desc = dbase + o_d; bs.cur_node = (const int*)(dbase + (transform ? o_nd : o_cn));
+    bs.cur_angle = (const float*)(dbase + o_ca); bs.cur_n = n; bs.match = (int*)(dbase + o_m);
+    if (launch_search_by_bow(c, bs, nnratio, check_orientation, s)) return hip_err(c, hipGetLastError(), "launch_search_by_bow");
+    TrkBufs t;
+    t.cur_n = n; t.match = bs.match; t.nm_bow = bs.match + cs; t.min_matches = min_matches;
+    t.kf_xw = (const float*)(dbase + o_x); t.kf_nobs = (const int*)(dbase + o_no);
+    t.has = dbase + o_has; t.xw = (float*)(dbase + o_xw); t.pose_n = dcnt; t.outl = dbase + o_out;
+    t.discarded = (int*)(dbase + o_dis); t.nmatches = dcnt + 2; t.nmap = dcnt + 3;
+    if (launch_trk_pose_prep(t, s, &c->hook)) return hip_err(c, hipGetLastError(), "launch_trk_pose_prep");
+    PoseBufs p;
+    p.n = dcnt; p.has_mp = t.has; p.xw = t.xw; p.kps = dbase + o_k; p.ur = (const float*)(dbase + o_ur);
+    p.inv_sigma2 = (const float*)(dbase + o_is); p.Tcw = (float*)(dbase + o_T); p.outlier = t.outl;
+    p.result = dcnt + 1; p.edges = sf.p_edge.p; p.active = sf.p_act.p; p.chi2 = sf.p_chi.p;
+    p.stride = cs; p.timing = nullptr;
+    if (launch_pose(p, 1, cam->fx, cam->fy, cam->cx, cam->cy, cam->bf, s, &c->hook))
+        return hip_err(c, hipGetLastError(), "launch_pose");
+    if (launch_trk_tail(t, s, &c->hook)) return hip_err(c, hipGetLastError(), "launch_trk_tail");
+    HIP_TRY(c, hipMemcpyAsync(c->pin + o_cnt, dbase + o_cnt, back_end - o_cnt, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    int32_t hc[4];
+    memcpy(hc, c->pin + o_cnt, 16);
+    const int32_t* hm = reinterpret_cast<const int32_t*>(c->pin + o_m);
+    if (transform) {
+        const int32_t* h_word = reinterpret_cast<const int32_t*>(c->pin + o_wd);
+        if (word_out) memcpy(word_out, h_word, (size_t)n * 4);
+        if (node_out) memcpy(node_out, c->pin + o_nd, (size_t)n * 4);
+        if (weight_out)
+            for (int i = 0; i < n; i++) {
+                const int wd = h_word[i];
+                weight_out[i] = (wd >= 0 && wd < (int)c->voc.word_weight.size()) ? c->voc.word_weight[wd] : 0.0;
+            }
+    }
+    if (n) memcpy(match_out, hm, (size_t)n * 4);
+    if (n && discarded_out) memcpy(discarded_out, c->pin + o_dis, (size_t)n * 4);
+    memcpy(Tcw, c->pin + o_T, 64);
+    *nmatches_bow = hm[cs];
+    *ninliers_pose = hc[1];
+    *nmatches = hc[2];
+    *nmatches_map = hc[3];
+    return COEB_OK;
+}
+
 namespace {
 
 // Common body of the batch matchers.  dT_cur: device poses, pair p (current frame p+1) at

@@ -82,6 +82,7 @@ struct TrackLocalMapBufs {  // coeb_track_local_map_batch_device
 };
 struct SingleFrameBufs {    // coeb_match_lastframe (m_*), _localmap / _keyframe (l_*), coeb_pose_optimization (p_*);
                             // coeb_search_local_points / coeb_track_local_map use l_list, l_path and p_*
+                            // coeb_track_reference_keyframe uses p_* (and BowBufs' m_csr / m_aux)
     DevArr<int32_t> m_scr{"m_scr"}, m_qn{"m_qn"}, l_out{"l_out"}, l_path{"l_path"};
     DevArr<uint32_t> l_list{"l_list"};
     DevArr<uint8_t> p_act{"p_act"};
@@ -275,6 +276,19 @@ struct Pack {
 int pinned(coeb_ctx* c, size_t bytes);          // the page-locked buffer holds at least bytes afterwards
 // pack -> pinned -> one H2D copy into the "stage" device buffer; *dbase = its device address
 int stage_in(coeb_ctx* c, const Pack& pk, uint8_t** dbase, hipStream_t s);
+
+// coeb_bow.hip, called by coeb_capi.hip (coeb_track_reference_keyframe): Frame::ComputeBoW's transform and
+// SearchByBoW on device arrays.  launch_transform: descriptor i of frame f at d_desc + (f * stride + i) * 32,
+// d_counts ? d_counts[f] : n_fixed of them; d_word / d_node [F][stride].
+int launch_transform(coeb_ctx* c, const uint8_t* d_desc, const int* d_counts, int n_fixed, int stride, int F,
+                     int levelsup, int* d_word, int* d_node, hipStream_t s);
+struct BowSearch {
+    const uint8_t* kf_valid; const uint8_t* kf_desc; const int* kf_node; const float* kf_angle; int kf_n;
+    const uint8_t* cur_desc; const int* cur_node; const float* cur_angle; int cur_n;
+    int* match;     // [max(cur_n, 1) + 1]: the KeyFrame index per frame feature (-1: none), then nmatches
+};
+int bow_search_bufs(coeb_ctx* c, int kf_n, int cur_n);      // the search's scratch, before anything is enqueued
+int launch_search_by_bow(coeb_ctx* c, const BowSearch& a, float nnratio, int check_ori, hipStream_t s);
 
 // coeb_flow.hip / coeb_frame.hip, called by coeb_capi.hip
 int pmo_batch(coeb_ctx* c, const uint8_t* d_gray, int F, int w, int h, float* tm_out, int* ntm_out, int tm_cap);

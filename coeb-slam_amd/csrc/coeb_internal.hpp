@@ -330,6 +330,22 @@ int launch_lm_tail(const LmBufs& t, hipStream_t s, ProfileHook* prof);
 // launch_match_local's LDS-budget verdict for cur_n keypoints and mp_n points, before anything is enqueued
 bool match_local_fits(int cur_n, int mp_n);
 
+// Tracking::TrackReferenceKeyFrame on one host frame (coeb_track.hip), every array in device memory:
+// k_bow_transform -> k_bow_csr -> k_match_bow -> k_bow_rot -> k_trk_pose_prep -> k_pose -> k_trk_tail,
+// no host step between.
+struct TrkBufs {
+    // SearchByBoW's result as k_bow_rot left it (the KeyFrame index per keypoint, its count), the gate (:835)
+    int cur_n; int* match; const int* nm_bow; int min_matches;
+    // mpReferenceKF's MapPoints by KeyFrame index: GetWorldPos() and Observations()
+    const float* kf_xw; const int* kf_nobs;
+    // k_trk_pose_prep: mvpMapPoints for PoseOptimization (:841), its keypoint count (0: gated), mvbOutlier cleared
+    uint8_t* has; float* xw; int* pose_n; uint8_t* outl;
+    // k_trk_tail: the discard loop (:843-862); match loses the discarded, nmatches / nmap zero on entry
+    int* discarded; int* nmatches; int* nmap;
+};
+int launch_trk_pose_prep(const TrkBufs& t, hipStream_t s, ProfileHook* prof);
+int launch_trk_tail(const TrkBufs& t, hipStream_t s, ProfileHook* prof);
+
 // relocalisation projection search (ORBmatcher::SearchByProjection(Frame&, KeyFrame*, set, th, ORBdist))
 struct KfBufs {
     const void* cur_kps; const uint8_t* cur_desc; const uint8_t* cur_has; int cur_n;

@@ -17,6 +17,9 @@
 // coeb_track_local_map): k_frustum -> k_match_local -> k_lm_pose_prep -> k_pose -> k_lm_tail on
 // the context stream, the map as the caller snapshots it (normals and distance ranges given).
 //
+// Tracking::TrackReferenceKeyFrame on one host frame (coeb_track_reference_keyframe,
+// src/Tracking.cc:823-865): behind SearchByBoW (coeb_bow.hip) k_trk_pose_prep -> k_pose -> k_trk_tail.
+//
 // Batch launch order: k_tlm_snapshot on the context stream (it copies every batch array the rest
 // reads, so the next batch's extraction may overwrite them), then on the pose stream after
 // the first k_pose: k_tlm_discard -> k_tlm_frustum -> k_match_local -> k_tlm_pose_prep -> k_pose.
@@ -237,6 +240,54 @@ __global__ __launch_bounds__(kT) void k_lm_tail(LmBufs t)
     if ((threadIdx.x & 63) == 0 && b) atomicAdd(t.ninl, (int)__popcll(b));
 }
 
+// ---- k_trk_pose_prep: TrackReferenceKeyFrame between SearchByBoW and PoseOptimization (:835-841) ----
+// mCurrentFrame.mvpMapPoints = vpMapPointMatches: keypoint i holds the MapPoint of KeyFrame feature
+// match[i].  `if (nmatches < 15) return false` (:835) is decided here: such a frame reaches the
+// optimiser with no keypoints, so k_pose leaves the pose and reports 0 (as k_track_prep does).
+__global__ __launch_bounds__(kT) void k_trk_pose_prep(TrkBufs t)
+{
+    const int i = blockIdx.x * kT + threadIdx.x;
+    if (i == 0) *t.pose_n = *t.nm_bow >= t.min_matches ? t.cur_n : 0;
+    if (i >= t.cur_n) return;
+    const int m = t.match[i];
+    const float* X = m >= 0 ? t.kf_xw + 3 * (int64_t)m : nullptr;
+    t.has[i] = X ? 1 : 0;
+    t.outl[i] = 0;                                  // k_pose writes the flags of the edges it takes
+    t.xw[3 * i + 0] = X ? X[0] : 0.f;
+    t.xw[3 * i + 1] = X ? X[1] : 0.f;
+    t.xw[3 * i + 2] = X ? X[2] : 0.f;
+}
+
+// ---- k_trk_tail: "Discard outliers" (:843-862) ----
+// A matched keypoint k_pose flagged loses its point (discarded[i] = the KeyFrame index it had);
+// nmatches counts the keypoints that keep one, nmatches_map those whose point has
+// Observations() > 0 (both zero on entry).  A gated frame keeps every match and counts no map point.
+__global__ __launch_bounds__(kT) void k_trk_tail(TrkBufs t)
+{
+    __shared__ int s_cnt[2];
+    const int i = blockIdx.x * kT + threadIdx.x;
+    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const bool go = *t.nm_bow >= t.min_matches;
+    bool kept = false, map = false;
+    if (i < t.cur_n) {
+        const int m = t.match[i];
+        const bool out = go && m >= 0 && t.outl[i];
+        t.discarded[i] = out ? m : -1;
+        if (out) t.match[i] = -1;
+        kept = m >= 0 && !out;
+        map = go && kept && t.kf_nobs[m] > 0;
+    }
+    const uint64_t bk = __ballot(kept), bm = __ballot(map);
+    if ((threadIdx.x & 63) == 0) {
+        if (bk) atomicAdd(&s_cnt[0], (int)__popcll(bk));
+        if (bm) atomicAdd(&s_cnt[1], (int)__popcll(bm));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && s_cnt[0]) atomicAdd(t.nmatches, s_cnt[0]);
+    if (threadIdx.x == 1 && s_cnt[1]) atomicAdd(t.nmap, s_cnt[1]);
+}
+
 }  // namespace
 
 int launch_frustum(const MatchCam& cam, const LmBufs& t, hipStream_t s, ProfileHook* prof)
@@ -262,6 +313,24 @@ int launch_lm_tail(const LmBufs& t, hipStream_t s, ProfileHook* prof)
     if (t.cur_n <= 0) return 0;                     // ninl stays 0
     prof_begin(prof, "k_lm_tail", s);
     hipLaunchKernelGGL(k_lm_tail, dim3((t.cur_n + kT - 1) / kT), dim3(kT), 0, s, t);
+    prof_end(prof, s);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_trk_pose_prep(const TrkBufs& t, hipStream_t s, ProfileHook* prof)
+{
+    if (t.cur_n <= 0) return 0;                     // pose_n stays 0
+    prof_begin(prof, "k_trk_pose_prep", s);
+    hipLaunchKernelGGL(k_trk_pose_prep, dim3((t.cur_n + kT - 1) / kT), dim3(kT), 0, s, t);
+    prof_end(prof, s);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_trk_tail(const TrkBufs& t, hipStream_t s, ProfileHook* prof)
+{
+    if (t.cur_n <= 0) return 0;                     // nmatches and nmap stay 0
+    prof_begin(prof, "k_trk_tail", s);
+    hipLaunchKernelGGL(k_trk_tail, dim3((t.cur_n + kT - 1) / kT), dim3(kT), 0, s, t);
     prof_end(prof, s);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

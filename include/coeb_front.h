@@ -71,6 +71,11 @@
  *                                      include/ORBmatcher.h:65, src/ORBmatcher.cc:159-288; the calls
  *                                      in TrackReferenceKeyFrame  src/Tracking.cc:833 and
  *                                      Relocalization  src/Tracking.cc:1456
+ *   coeb_track_reference_keyframe   <- Tracking::TrackReferenceKeyFrame  src/Tracking.cc:823-865:
+ *                                      ComputeBoW (:826), SearchByBoW (:833), the nmatches < 15 gate
+ *                                      (:835), Optimizer::PoseOptimization (:841) and the outlier
+ *                                      discard with nmatchesMap (:843-862) on one host frame, one
+ *                                      call and one synchronisation
  *   coeb_bow_vector                 <- DBoW2 BowVector::addWeight / normalize(L1) as transform() fills
  *                                      mBowVec (host only; restated, parity against DBoW2 UNPINNED)
  *   coeb_kfdb_add / _erase / _clear <- KeyFrameDatabase::add / erase / clear
@@ -467,6 +472,48 @@ typedef struct {
  * At most 4095 features per side. */
 int coeb_match_bow(coeb_ctx* ctx, const coeb_bow_keyframe* kf, const coeb_bow_frame* cur, float nnratio,
                    int check_orientation, int32_t* match_out, int* nmatches);
+
+/* mpReferenceKF as TrackReferenceKeyFrame reads it: the SearchByBoW fields, plus what
+ * PoseOptimization and the discard loop read from the matched MapPoints. */
+typedef struct {
+    coeb_bow_keyframe bow;            /* n, valid, descriptor, node_id, angle */
+    const float* world_pos;           /* n x 3, GetWorldPos(), read where valid */
+    const int32_t* observations;      /* Observations(), read where valid */
+} coeb_ref_keyframe;
+
+/* ---- Tracking::TrackReferenceKeyFrame (Tracking.cc:823-865) on one host frame ----
+ * One upload, one download and one synchronisation; in the reference's order:
+ *   - ComputeBoW (Frame.cc:570-577).  cur_node_id == NULL: the transform of cur->descriptors runs
+ *     with levelsup as coeb_bow_transform's does, and word_out / node_out / weight_out (each may be
+ *     NULL) receive what that call writes.  cur_node_id != NULL (length cur->n, the mFeatVec node
+ *     that lists feature i or -1): mBowVec is already filled, the transform is skipped, no
+ *     vocabulary is needed and the three outputs are not written.
+ *   - SearchByBoW(pKF, F, vpMapPointMatches) with nnratio and check_orientation, as coeb_match_bow.
+ *     The frame's angles are cur->keys_un[i].angle: UndistortKeyPoints copies the key and changes
+ *     only pt, so this is mvKeys[i].angle.  *nmatches_bow = the return value.
+ *   - the gate (:835): with *nmatches_bow < min_matches (the reference uses 15) the call stops:
+ *     match_out holds SearchByBoW's assignments, discarded_out is all -1, Tcw is untouched,
+ *     *ninliers_pose = 0, *nmatches = *nmatches_bow and *nmatches_map = 0.
+ *   - PoseOptimization (:841) from Tcw (mLastFrame.mTcw, row-major 4x4) over the keypoints that got
+ *     a match: position kf->world_pos[match], measurement cur->keys_un[i] with cur->u_right[i]
+ *     (< 0: monocular edge), information the context's mvInvLevelSigma2.  Tcw holds the optimised
+ *     pose on return; with fewer than 3 edges it is untouched and *ninliers_pose = 0, as in
+ *     coeb_pose_optimization (reachable with min_matches <= 2).
+ *   - the discard loop (:843-862): a matched keypoint flagged outlier loses its point, match_out[i]
+ *     = -1 and discarded_out[i] = the KeyFrame index it had (the caller sets mbTrackInView = false
+ *     and mnLastFrameSeen on that MapPoint); discarded_out is -1 everywhere else and may be NULL.
+ *     *nmatches = *nmatches_bow minus the discarded; *nmatches_map = the kept keypoints whose point
+ *     has observations > 0, which the caller compares with 10 (:864).
+ * match_out has cur->n entries.  COEB_EINVAL, with nothing written, for a missing required pointer
+ * or array, a negative size or levelsup, more than 4095 features on either side, cur_node_id ==
+ * NULL before coeb_bow_set_vocabulary, or a keypoint octave outside the pyramid.  n == 0 on either
+ * side is COEB_OK with zero counts. */
+int coeb_track_reference_keyframe(coeb_ctx* ctx, const coeb_camera* cam, const coeb_curframe* cur,
+                                  const int32_t* cur_node_id, int levelsup, const coeb_ref_keyframe* kf,
+                                  float Tcw[16], float nnratio, int check_orientation, int min_matches,
+                                  int32_t* word_out, int32_t* node_out, double* weight_out,
+                                  int32_t* match_out, int32_t* discarded_out, int* nmatches_bow,
+                                  int* ninliers_pose, int* nmatches, int* nmatches_map);
 
 /* ---- BowVector filling: addWeight in feature order, then normalize(L1) (host only, no context) ----
  * For every feature i < n with node[i] >= 0 (coeb_bow_transform's "weight > 0"), in order:
