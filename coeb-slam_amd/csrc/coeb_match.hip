@@ -1350,7 +1350,12 @@ __global__ __launch_bounds__(kMThreads) void k_match_kf(MatchCam cam, KfBufs b, 
     __syncthreads();
     const bool overflow = s_flag[0] != 0;
     bool seq = force_seq || overflow;
-    if (!seq) seq = claims_first_min(L, b.lists, kCQ, n, nq, s_flag);
+    int iters = 0;                                     // fixpoint sweeps run (0: forced / overflow)
+    if (!seq) {
+        seq = claims_first_min(L, b.lists, kCQ, n, nq, s_flag);
+        iters = s_flag[7];
+    }
+    if (tid == 0) b.path[1] = iters;
     if (seq) {
         // literal loop (ORBmatcher.cc:1489-1578), one thread; L.owner[c] >= 0: c holds a MapPoint
         const int path = force_seq ? 1 : overflow ? 2 : 3;

@@ -186,75 +186,10 @@ def test_resize_and_blur_constant_images(oracle_mod):
 
 
 # ---- local-map SearchByProjection: C oracle vs a literal Python loop (ORBmatcher.cc:44-129) ----
-def _py_search_local_map(cam, kps, desc, ur, cur_obs, mp, th, nnratio):
-    """Pure-Python restatement, small sizes only: AssignFeaturesToGrid (Frame.cc:396-411,
-    PosInGrid :553-568), GetFeaturesInArea (:503-551), the search loop (ORBmatcher.cc:44-129)."""
-    f32 = np.float32
-    cols, rows = 64, 48
-    grid = [[[] for _ in range(rows)] for _ in range(cols)]
-    for i, k in enumerate(kps):
-        px = math.floor(abs(float((f32(k["x"]) - f32(cam.min_x)) * f32(cam.grid_inv_w))) + 0.5)
-        py = math.floor(abs(float((f32(k["y"]) - f32(cam.min_y)) * f32(cam.grid_inv_h))) + 0.5)
-        if (f32(k["x"]) - f32(cam.min_x)) < 0:
-            px = -px
-        if (f32(k["y"]) - f32(cam.min_y)) < 0:
-            py = -py
-        if 0 <= px < cols and 0 <= py < rows:
-            grid[px][py].append(i)
-
-    def in_area(x, y, r, minL, maxL):
-        out = []
-        x0 = max(0, math.floor(float((f32(x) - f32(cam.min_x) - f32(r)) * f32(cam.grid_inv_w))))
-        if x0 >= cols:
-            return out
-        x1 = min(cols - 1, math.ceil(float((f32(x) - f32(cam.min_x) + f32(r)) * f32(cam.grid_inv_w))))
-        if x1 < 0:
-            return out
-        y0 = max(0, math.floor(float((f32(y) - f32(cam.min_y) - f32(r)) * f32(cam.grid_inv_h))))
-        if y0 >= rows:
-            return out
-        y1 = min(rows - 1, math.ceil(float((f32(y) - f32(cam.min_y) + f32(r)) * f32(cam.grid_inv_h))))
-        if y1 < 0:
-            return out
-        chk = minL > 0 or maxL >= 0
-        for ix in range(x0, x1 + 1):
-            for iy in range(y0, y1 + 1):
-                for j in grid[ix][iy]:
-                    if chk and (kps[j]["octave"] < minL or (maxL >= 0 and kps[j]["octave"] > maxL)):
-                        continue
-                    if abs(f32(kps[j]["x"]) - f32(x)) < f32(r) and abs(f32(kps[j]["y"]) - f32(y)) < f32(r):
-                        out.append(j)
-        return out
-
-    holder = list(cur_obs)
-    match = [-1] * len(kps)
-    nm = 0
-    for q in range(len(mp["in_view"])):
-        if not mp["in_view"][q]:
-            continue
-        lvl = int(mp["level"][q])
-        r = f32(2.5) if f32(mp["view_cos"][q]) > f32(0.998) else f32(4.0)
-        if th != 1.0:
-            r = f32(r * f32(th))
-        rs = f32(r * f32(cam.scale[lvl]))
-        best, bl, best2, bl2, bi = 256, -1, 256, -1, -1
-        for idx in in_area(mp["proj_x"][q], mp["proj_y"][q], rs, lvl - 1, lvl):
-            if holder[idx] > 0:
-                continue
-            if ur[idx] > 0 and abs(f32(mp["proj_xr"][q]) - f32(ur[idx])) > rs:
-                continue
-            d = sum(bin(int(a) ^ int(b)).count("1") for a, b in zip(mp["descriptor"][q], desc[idx]))
-            if d < best:
-                best2, bl2, best, bl, bi = best, bl, d, int(kps[idx]["octave"]), idx
-            elif d < best2:
-                bl2, best2 = int(kps[idx]["octave"]), d
-        if best <= 100:
-            if bl == bl2 and f32(best) > f32(nnratio) * f32(best2):
-                continue
-            match[bi] = q
-            holder[bi] = int(mp["observations"][q])
-            nm += 1
-    return nm, np.array(match, np.int32)
+# (the models live in tests/match_ref.py, with the directed scenes that use them)
+from match_ref import py_search_by_projection as _py_search_by_projection  # noqa: E402
+from match_ref import py_search_keyframe as _py_search_keyframe  # noqa: E402
+from match_ref import py_search_local_map as _py_search_local_map  # noqa: E402
 
 
 def _kat_camera(oracle_mod, bounds=None):
@@ -320,105 +255,6 @@ def _local_map_case(oracle_mod, seed, cam):
 
 
 # ---- relocalisation SearchByProjection: C oracle vs a literal Python loop (ORBmatcher.cc:1473-1600) ----
-def _py_search_keyframe(cam, kps, desc, cur_has, kf, T, th, orb_dist, check_ori):
-    f32, f64 = np.float32, np.float64
-    cols, rows = 64, 48
-    grid = [[[] for _ in range(rows)] for _ in range(cols)]
-    for i, k in enumerate(kps):
-        gx = float((f32(k["x"]) - f32(cam.min_x)) * f32(cam.grid_inv_w))
-        gy = float((f32(k["y"]) - f32(cam.min_y)) * f32(cam.grid_inv_h))
-        px = int(math.copysign(math.floor(abs(gx) + 0.5), gx))
-        py = int(math.copysign(math.floor(abs(gy) + 0.5), gy))
-        if 0 <= px < cols and 0 <= py < rows:
-            grid[px][py].append(i)
-    T = np.asarray(T, f32)
-    Ow = [f32(-(f64(T[0, k]) * f64(T[0, 3]) + f64(T[1, k]) * f64(T[1, 3]) + f64(T[2, k]) * f64(T[2, 3])))
-          for k in range(3)]
-    log_sf = f32(math.log(f64(f32(cam.scale[1]))))
-    taken = [bool(h) for h in cur_has]
-    match = [-1] * len(kps)
-    hist = []
-    nm = 0
-    for q in range(len(kf["valid"])):
-        if not kf["valid"][q]:
-            continue
-        X = kf["world_pos"][q].astype(f32)
-        p3 = []
-        for k in range(3):
-            t = f32(T[k, 0] * X[0]) + f32(T[k, 1] * X[1])
-            t = f32(t + f32(T[k, 2] * X[2]))
-            p3.append(f32(f64(t) + f64(T[k, 3])))
-        invz = f32(1.0 / f64(p3[2]))
-        u = f32(f64(f32(f32(cam.fx) * p3[0])) * f64(invz) + f64(f32(cam.cx)))    # fmaf, exact in double
-        v = f32(f64(f32(f32(cam.fy) * p3[1])) * f64(invz) + f64(f32(cam.cy)))
-        if u < f32(cam.min_x) or u > f32(cam.max_x) or v < f32(cam.min_y) or v > f32(cam.max_y):
-            continue
-        d = [f32(X[k] - Ow[k]) for k in range(3)]
-        ss = 0.0
-        for k in range(3):
-            ss += f64(d[k]) * f64(d[k])
-        dist3 = f32(math.sqrt(ss))
-        if dist3 < f32(f32(0.8) * f32(kf["min_distance"][q])) or dist3 > f32(f32(1.2) * f32(kf["max_distance"][q])):
-            continue
-        ratio = f32(f32(kf["max_distance"][q]) / dist3)
-        lvl = int(math.ceil(f32(f32(math.log(f64(ratio))) / log_sf)))
-        lvl = min(max(lvl, 0), cam.nlevels - 1)
-        r = f32(f32(th) * f32(cam.scale[lvl]))
-        x0 = max(0, math.floor(f32(f32(u - f32(cam.min_x)) - r) * f32(cam.grid_inv_w)))
-        x1 = min(cols - 1, math.ceil(f32(f32(u - f32(cam.min_x)) + r) * f32(cam.grid_inv_w)))
-        y0 = max(0, math.floor(f32(f32(v - f32(cam.min_y)) - r) * f32(cam.grid_inv_h)))
-        y1 = min(rows - 1, math.ceil(f32(f32(v - f32(cam.min_y)) + r) * f32(cam.grid_inv_h)))
-        if x0 >= cols or x1 < 0 or y0 >= rows or y1 < 0:
-            continue
-        best, bi = 256, -1
-        for ix in range(x0, x1 + 1):
-            for iy in range(y0, y1 + 1):
-                for j in grid[ix][iy]:
-                    o = int(kps[j]["octave"])
-                    if o < lvl - 1 or o > lvl + 1:
-                        continue
-                    if not (abs(f32(kps[j]["x"]) - u) < r and abs(f32(kps[j]["y"]) - v) < r):
-                        continue
-                    if taken[j]:
-                        continue
-                    dd = sum(bin(int(a) ^ int(b)).count("1") for a, b in zip(kf["descriptor"][q], desc[j]))
-                    if dd < best:
-                        best, bi = dd, j
-        if best <= orb_dist:
-            taken[bi] = True
-            match[bi] = q
-            nm += 1
-            if check_ori:
-                rot = f32(f32(kf["angle"][q]) - f32(kps[bi]["angle"]))
-                if rot < 0:
-                    rot = f32(rot + f32(360.0))
-                x = float(f32(rot * f32(1.0 / 30)))
-                b = int(math.floor(x + 0.5))
-                hist.append((bi, 0 if b == 30 else b))
-    if check_ori:
-        h = [0] * 30
-        for _, b in hist:
-            h[b] += 1
-        m1 = m2 = m3 = 0
-        i1 = i2 = i3 = -1
-        for i in range(30):
-            if h[i] > m1:
-                m3, m2, m1, i3, i2, i1 = m2, m1, h[i], i2, i1, i
-            elif h[i] > m2:
-                m3, m2, i3, i2 = m2, h[i], i2, i
-            elif h[i] > m3:
-                m3, i3 = h[i], i
-        if m2 < f32(0.1) * f32(m1):
-            i2 = i3 = -1
-        elif m3 < f32(0.1) * f32(m1):
-            i3 = -1
-        for bi, b in hist:
-            if b not in (i1, i2, i3):
-                match[bi] = -1
-                nm -= 1
-    return nm, np.array(match, np.int32)
-
-
 @pytest.mark.parametrize("seed", [0, 1])
 def test_search_keyframe_oracle_vs_python(oracle_mod, seed):
     _keyframe_case(oracle_mod, seed, _kat_camera(oracle_mod))
@@ -464,6 +300,62 @@ def _keyframe_case(oracle_mod, seed, cam):
     for th, od, ori in ((10.0, 100, True), (3.0, 64, True), (15.0, 80, False)):
         nm, mt = oracle_mod.search_keyframe(cam, kps, desc, has, kf, T, th, od, ori)
         nm_py, mt_py = _py_search_keyframe(cam, kps, desc, has, kf, T, th, od, ori)
+        assert nm == nm_py and np.array_equal(mt, mt_py), (nm, nm_py)
+        assert nm > 0
+        out.append(mt)
+    return out
+
+
+# ---- tracking SearchByProjection: C oracle vs a literal Python loop (ORBmatcher.cc:1329-1471) ----
+@pytest.mark.parametrize("seed", [0, 1, 2])
+def test_search_by_projection_oracle_vs_python(oracle_mod, seed):
+    _lastframe_case(oracle_mod, seed, _kat_camera(oracle_mod))
+
+
+@pytest.mark.parametrize("bounds", _kat_bounds(), ids=["inside", "outside"])
+def test_search_by_projection_oracle_vs_python_image_bounds(oracle_mod, bounds):
+    import chain_util as cu
+    res = _lastframe_case(oracle_mod, 0, _kat_camera(oracle_mod, bounds))
+    if bounds == cu.BOUNDS_INSIDE:
+        ref = _lastframe_case(oracle_mod, 0, _kat_camera(oracle_mod))
+        assert any(not np.array_equal(a, b) for a, b in zip(res, ref))
+
+
+def _lastframe_case(oracle_mod, seed, cam):
+    """The random frame of _keyframe_case as CurrentFrame; LastFrame points that project near its
+    keypoints under a small motion, some without MapPoint, outliers, or with Observations() = 0
+    (their claims can be overwritten); forward, backward and monocular level windows."""
+    rng = np.random.default_rng(seed)
+    n, m = 300, 260
+    kps = np.zeros(n, oracle_mod.KP_DTYPE)
+    kps["x"] = rng.uniform(0, 640, n)
+    kps["y"] = rng.uniform(0, 480, n)
+    kps["octave"] = rng.integers(0, 8, n)
+    kps["angle"] = rng.uniform(0, 360, n)
+    desc = rng.integers(0, 256, (n, 32)).astype(np.uint8)
+    ur = np.where(rng.random(n) < 0.7, kps["x"] - rng.uniform(5, 30, n), -1).astype(np.float32)
+    src = rng.integers(0, n, m)
+    z = rng.uniform(1.0, 4.0, m).astype(np.float32)
+    xw = np.stack([((kps["x"][src] + rng.normal(0, 3, m) - 320.1) * z / 535.4),
+                   ((kps["y"][src] + rng.normal(0, 3, m) - 247.6) * z / 539.2), z], 1).astype(np.float32)
+    d = desc[src].copy()
+    for q in range(m):
+        for b in rng.integers(0, 256, rng.integers(0, 60)):
+            d[q, b >> 3] ^= np.uint8(1 << (b & 7))
+    lk = np.zeros(m, oracle_mod.KP_DTYPE)
+    lk["octave"] = np.clip(kps["octave"][src] + rng.integers(-1, 2, m), 0, 7)
+    lk["angle"] = (kps["angle"][src] + rng.normal(0, 8, m)) % 360
+    last = dict(has_mp=(rng.random(m) < 0.9).astype(np.uint8), outlier=(rng.random(m) < 0.1).astype(np.uint8),
+                xw=np.ascontiguousarray(xw), mp_desc=d, mp_nobs=rng.choice(np.array([0, 1, 2], np.int32), m).astype(np.int32),
+                keys_un=lk)
+    Tl = np.eye(4, dtype=np.float32)
+    out = []
+    for tz, th, bmono, ori in ((0.015, 15.0, False, True), (0.5, 7.0, False, True), (-0.5, 15.0, False, False),
+                               (0.5, 30.0, True, True)):
+        Tc = np.eye(4, dtype=np.float32)
+        Tc[:3, 3] = [0.01, -0.02, tz]
+        nm, mt = oracle_mod.search_by_projection(cam, kps, desc, ur, last, Tc, Tl, th, bmono, ori)
+        nm_py, mt_py = _py_search_by_projection(cam, kps, desc, ur, last, Tc, Tl, th, bmono, ori)
         assert nm == nm_py and np.array_equal(mt, mt_py), (nm, nm_py)
         assert nm > 0
         out.append(mt)
