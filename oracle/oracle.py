@@ -402,6 +402,36 @@ def gaussian_blur7(img):
     return out
 
 
+def level_candidates(lvl, ini_th=20, min_th=7):
+    """The FAST stage of ComputeKeyPointsOctTree on one level (ORBextractor.cc:795-850): (xs, ys,
+    score) int32 arrays of vToDistributeKeys, relative to (16, 16), in the reference's order."""
+    lvl = np.ascontiguousarray(lvl, np.uint8)
+    h, w = lvl.shape
+    cap = w * h
+    xs, ys, sc = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+    n = lib().oc_level_candidates(ptr(lvl), w, h, w, int(ini_th), int(min_th), ptr(xs), ptr(ys), ptr(sc), cap)
+    assert 0 <= n <= cap
+    return xs[:n].copy(), ys[:n].copy(), sc[:n].copy()
+
+
+def ic_angle_moments(lvl, x, y, umax):
+    """IC_Angle's (m01, m10) at (x, y) of a level (ORBextractor.cc:80-104)."""
+    lvl = np.ascontiguousarray(lvl, np.uint8)
+    um = (C.c_int * 16)(*umax)
+    m01, m10 = C.c_int(), C.c_int()
+    lib().oc_ic_angle_moments(ptr(lvl), lvl.shape[1], int(x), int(y), um, C.byref(m01), C.byref(m10))
+    return m01.value, m10.value
+
+
+def orb_descriptor(blurred, x, y, angle, pattern):
+    """computeOrbDescriptor (ORBextractor.cc:110-156) at (x, y) of a blurred level: uint8[32]."""
+    blurred = np.ascontiguousarray(blurred, np.uint8)
+    pat = np.ascontiguousarray(pattern, np.int32).reshape(512, 2)
+    out = np.zeros(32, np.uint8)
+    lib().oc_orb_descriptor(ptr(blurred), blurred.shape[1], int(x), int(y), C.c_float(angle), ptr(pat), ptr(out))
+    return out
+
+
 def gauss_kernel7():
     k = (C.c_int * 7)()
     lib().oc_gauss_kernel7(k)
