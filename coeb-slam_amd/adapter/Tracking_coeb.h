@@ -1,9 +1,9 @@
 /*
  * Tracking_coeb.h -- MI355X bodies for Tracking::SearchLocalPoints, Tracking::TrackLocalMap
- * (src/Tracking.cc:1222-1272, 996-1047) and Tracking::TrackReferenceKeyFrame (:823-865, further
- * down).  The first two: Frame::isInFrustum over the local map, the local-map projection search,
- * the pose optimisation and the inlier count in one library call with one synchronisation
- * (coeb_search_local_points / coeb_track_local_map).
+ * (src/Tracking.cc:1222-1272, 996-1047), Tracking::TrackReferenceKeyFrame (:823-865) and
+ * Tracking::TrackWithMotionModel (:933-994, both further down).  The first two: Frame::isInFrustum
+ * over the local map, the local-map projection search, the pose optimisation and the inlier count in
+ * one library call with one synchronisation (coeb_search_local_points / coeb_track_local_map).
  *
  * Included from the reference's src/Tracking.cc.  SearchLocalPoints' body becomes
  *
@@ -50,16 +50,45 @@
  *     with fewer than 3 edges);
  *   - mbTrackInView = false and mnLastFrameSeen = F.mnId on the discarded MapPoints (:855-856);
  *   - the return value is nmatchesMap >= 10.
+ *
+ * Tracking::TrackWithMotionModel (src/Tracking.cc:933-994) becomes, with UpdateLastFrame cut down to
+ * its first lines (:870-873, the pose from mlRelativeFramePoses),
+ *
+ *     UpdateLastFramePose();
+ *     const bool bCreateVO = mnLastKeyFrameId != mLastFrame.mnId && mSensor != System::MONOCULAR && mbOnlyTracking;
+ *     return coeb::TrackWithMotionModel(mCurrentFrame, mLastFrame, mVelocity, mSensor != System::STEREO ? 15 : 7,
+ *                mSensor == System::MONOCULAR, mbOnlyTracking, bCreateVO, mThDepth,
+ *                [&](const cv::Mat& x3D, int i) { return new MapPoint(x3D, mpMap, &mLastFrame, i); },
+ *                mlpTemporalPoints, &mbVO);
+ *
+ * one library call with one synchronisation (coeb_track_motion_model).  In the reference's order:
+ *   - snapshot of mLastFrame: per keypoint whether it holds a MapPoint, mvbOutlier, and GetWorldPos() /
+ *     GetDescriptor() / Observations() of the point under MapPoint::mGlobalMutex; with bCreateVO also
+ *     mvDepth and mDescriptors;
+ *   - F.SetPose(mVelocity * mLastFrame.mTcw) (:941), the product in the caller's matrix type;
+ *   - the call: the visual-odometry points, the search with its 2*th retry, the gate, the pose
+ *     optimisation and the discard;
+ *   - with bCreateVO the temporary MapPoints (:913-922): for every created slot, in the order of the
+ *     depth sort, newTemporalPoint(x3D, i) goes into mLastFrame.mvpMapPoints[i] and to the back of
+ *     mlpTemporalPoints;
+ *   - F.mvpMapPoints = the search's assignments less the optimiser's outliers; nmatches < 20 (:960):
+ *     false, with the predicted pose; else F.SetPose(the optimised pose), mvbOutlier false on every
+ *     matched keypoint, mbTrackInView = false and mnLastFrameSeen = F.mnId on the discarded MapPoints;
+ *   - :987-993: in localisation mode mbVO = nmatchesMap < 10 and the return value is nmatches > 20,
+ *     otherwise nmatchesMap >= 10.
+ *
  * The vocabulary's context has ORB-SLAM2's pyramid (8 levels, 1.2): its mvInvLevelSigma2 weigh the
  * edges, so a frame with another pyramid is refused.
  */
 #ifndef COEB_ADAPTER_TRACKING_H
 #define COEB_ADAPTER_TRACKING_H
 
+#include <algorithm>
 #include <cstring>
 #include <mutex>
 #include <stdexcept>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include <opencv2/core/core.hpp>
@@ -268,6 +297,98 @@ inline bool TrackReferenceKeyFrame(FrameT& F, KeyFrameT* pRefKF, const MatT& las
         MapPointT* pMP = vpMapPointsKF[disc[i]];    // :851-856
         pMP->mbTrackInView = false;
         pMP->mnLastFrameSeen = F.mnId;
+    }
+    return nmatchesMap >= 10;
+}
+
+// Tracking::TrackWithMotionModel after UpdateLastFrame has set mLastFrame's pose (:870-873 stay with
+// the caller: they read mlRelativeFramePoses).  bCreateVO is UpdateLastFrame's condition to go on
+// (:875 negated: mnLastKeyFrameId != mLastFrame.mnId && mSensor != MONOCULAR && mbOnlyTracking);
+// newTemporalPoint(x3D, i) returns `new MapPoint(x3D, mpMap, &mLastFrame, i)`.  *pbVO receives mbVO
+// in localisation mode and is left alone otherwise; *pnMatchesMap (when given) receives nmatchesMap.
+template <class FrameT, class MatT, class ListT, class NewPointF>
+inline bool TrackWithMotionModel(FrameT& F, FrameT& LastFrame, const MatT& mVelocity, float th, bool bMono,
+                                 bool bOnlyTracking, bool bCreateVO, float thDepth, NewPointF newTemporalPoint,
+                                 ListT& mlpTemporalPoints, bool* pbVO, bool bCheckOrientation = true,
+                                 int* pnMatchesMap = nullptr, coeb_ctx* ctx = nullptr)
+{
+    typedef typename std::remove_pointer<typename std::decay<decltype(LastFrame.mvpMapPoints[0])>::type>::type MapPointT;
+    if (!ctx) ctx = matcher_ctx(F.mnScaleLevels, F.mfScaleFactor);
+    const int N = F.N, nl = LastFrame.N;
+    std::vector<uint8_t> has(nl), outl(nl), mpdesc((size_t)nl * 32);
+    std::vector<float> xw((size_t)nl * 3);
+    std::vector<int32_t> nobs(nl);
+    {
+        std::unique_lock<std::mutex> lock(MapPointT::mGlobalMutex);
+        for (int i = 0; i < nl; ++i) {
+            MapPointT* pMP = LastFrame.mvpMapPoints[i];
+            has[i] = pMP != nullptr;
+            outl[i] = LastFrame.mvbOutlier[i];
+            if (!pMP) continue;
+            cv::Mat P = pMP->GetWorldPos();
+            for (int k = 0; k < 3; ++k) xw[3 * i + k] = P.at<float>(k);
+            cv::Mat d = pMP->GetDescriptor();
+            std::memcpy(&mpdesc[32 * (size_t)i], d.ptr<uint8_t>(0), 32);
+            nobs[i] = pMP->Observations();
+        }
+    }
+    coeb_lastframe last{nl, has.data(), outl.data(), xw.data(), mpdesc.data(), nobs.data(),
+                        reinterpret_cast<const coeb_keypoint*>(LastFrame.mvKeysUn.data())};
+    cv::Mat curDesc = F.mDescriptors.isContinuous() ? F.mDescriptors : F.mDescriptors.clone();
+    cv::Mat lastDesc = LastFrame.mDescriptors.isContinuous() ? LastFrame.mDescriptors : LastFrame.mDescriptors.clone();
+    coeb_curframe cur{N, reinterpret_cast<const coeb_keypoint*>(F.mvKeysUn.data()),
+                      curDesc.empty() ? nullptr : curDesc.ptr<uint8_t>(0), F.mvuRight.data()};
+    std::vector<uint8_t> created(nl);
+    std::vector<float> cpos((size_t)nl * 3);
+    coeb_vo_points vo{LastFrame.mvDepth.data(), lastDesc.empty() ? nullptr : lastDesc.ptr<uint8_t>(0), thDepth,
+                      created.data(), cpos.data()};
+    const coeb_camera cam = frame_camera(F);
+    F.SetPose(mVelocity * LastFrame.mTcw);          // :941
+    float T[16], Tl[16];
+    for (int r = 0; r < 4; ++r)
+        for (int k = 0; k < 4; ++k) {
+            T[4 * r + k] = F.mTcw.template at<float>(r, k);
+            Tl[4 * r + k] = LastFrame.mTcw.template at<float>(r, k);
+        }
+    std::vector<int32_t> match((size_t)N), disc((size_t)N);
+    int nmatchesSearch = 0, ninl = 0, nmatches = 0, nmatchesMap = 0;
+    const int rc = coeb_track_motion_model(ctx, &cam, &cur, &last, bCreateVO ? &vo : nullptr, Tl, T, th, bMono ? 1 : 0,
+                                           bCheckOrientation ? 1 : 0, 20, match.data(), disc.data(), nullptr,
+                                           &nmatchesSearch, &ninl, &nmatches, &nmatchesMap);
+    if (rc != COEB_OK) throw std::runtime_error(coeb_last_error(ctx));
+    if (bCreateVO) {                                // :913-922, in the order of the depth sort
+        std::vector<std::pair<float, int>> vDepthIdx;
+        for (int i = 0; i < nl; ++i)
+            if (created[i]) vDepthIdx.push_back(std::make_pair(LastFrame.mvDepth[i], i));
+        std::sort(vDepthIdx.begin(), vDepthIdx.end());
+        for (size_t j = 0; j < vDepthIdx.size(); ++j) {
+            const int i = vDepthIdx[j].second;
+            cv::Mat x3D(3, 1, CV_32F);
+            for (int k = 0; k < 3; ++k) x3D.at<float>(k) = cpos[3 * (size_t)i + k];
+            MapPointT* pNewMP = newTemporalPoint(x3D, i);
+            LastFrame.mvpMapPoints[i] = pNewMP;
+            mlpTemporalPoints.push_back(pNewMP);
+        }
+    }
+    // :943, :956 and the search's assignments less the discards
+    for (int i = 0; i < N; ++i)
+        F.mvpMapPoints[i] = match[i] >= 0 ? LastFrame.mvpMapPoints[match[i]] : static_cast<MapPointT*>(nullptr);
+    if (pnMatchesMap) *pnMatchesMap = nmatchesMap;
+    if (nmatchesSearch < 20) return false;          // :960
+    cv::Mat Tcw(4, 4, CV_32F);
+    for (int r = 0; r < 4; ++r)
+        for (int k = 0; k < 4; ++k) Tcw.at<float>(r, k) = T[4 * r + k];
+    F.SetPose(Tcw);
+    for (int i = 0; i < N; ++i) {
+        if (match[i] >= 0 || disc[i] >= 0) F.mvbOutlier[i] = false;    // Optimizer.cc:302, Tracking.cc:977
+        if (disc[i] < 0) continue;
+        MapPointT* pMP = LastFrame.mvpMapPoints[disc[i]];              // :974-979
+        pMP->mbTrackInView = false;
+        pMP->mnLastFrameSeen = F.mnId;
+    }
+    if (bOnlyTracking) {                            // :987-991
+        if (pbVO) *pbVO = nmatchesMap < 10;
+        return nmatches > 20;
     }
     return nmatchesMap >= 10;
 }

@@ -79,6 +79,7 @@ ABI_SYMBOLS = [
     "coeb_bow_vector", "coeb_kfdb_create", "coeb_kfdb_destroy", "coeb_kfdb_add", "coeb_kfdb_erase", "coeb_kfdb_clear",
     "coeb_kfdb_size", "coeb_kfdb_query", "coeb_match_bow_kfdb",
     "coeb_search_local_points", "coeb_track_local_map", "coeb_track_reference_keyframe",
+    "coeb_track_motion_model",
 ]
 # COEB_ABI_VERSION of the include/coeb_front.h these argtypes are written against; lib() refuses
 # a library that reports another (tests/test_capi_symbols.py keeps the two equal)
@@ -145,6 +146,14 @@ class BowKeyFrameC(C.Structure):
 
 class RefKeyFrameC(C.Structure):
     _fields_ = [("bow", BowKeyFrameC), ("world_pos", C.c_void_p), ("observations", C.c_void_p)]
+
+
+class VoPointsC(C.Structure):
+    _fields_ = [("depth", C.c_void_p), ("descriptors", C.c_void_p), ("th_depth", C.c_float),
+                ("created_out", C.c_void_p), ("created_pos", C.c_void_p)]
+
+
+VO_MAX_LAST = 16384     # COEB_VO_MAX_LAST
 
 
 class BowFrameC(C.Structure):
@@ -225,6 +234,10 @@ def lib():
         L.coeb_track_reference_keyframe.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(CurFrameC), C.c_void_p,
                                                     C.c_int, C.POINTER(RefKeyFrameC), C.c_void_p, C.c_float, C.c_int,
                                                     C.c_int] + [C.c_void_p] * 5 + [C.POINTER(C.c_int)] * 4
+        L.coeb_track_motion_model.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(CurFrameC),
+                                              C.POINTER(LastFrameC), C.POINTER(VoPointsC), C.c_void_p, C.c_void_p,
+                                              C.c_float, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3 + \
+            [C.POINTER(C.c_int)] * 4
         L.coeb_match_keyframe.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(CurFrameC), C.c_void_p,
                                           C.POINTER(KeyFramePointsC), C.c_void_p, C.c_float, C.c_int, C.c_int,
                                           C.c_void_p, C.POINTER(C.c_int)]
@@ -548,6 +561,57 @@ class Context:
         return dict(word=cut(word), node=cut(node), weight=cut(weight), match=match[:n], discarded=disc[:n],
                     Tcw=T.reshape(4, 4), nmatches_bow=nb.value, ninliers_pose=nin.value, nmatches=nm.value,
                     nmatches_map=nmap.value)
+
+    def track_with_motion_model(self, camera, F, LastFrame, th=15.0, bMono=False, check_orientation=True,
+                                min_matches=20, depth=None, th_depth=None):
+        """Tracking::TrackWithMotionModel (src/Tracking.cc:933-994) in one call
+        (coeb_track_motion_model): SearchByProjection(F, LastFrame, th, bMono) from F.mTcw (the
+        caller's mVelocity * mLastFrame.mTcw), the 2*th retry and the gate at min_matches,
+        PoseOptimization and the outlier discard.  LastFrame is a Frame with map_points as
+        ORBmatcher.SearchByProjection takes it.  depth (LastFrame.mvDepth) with th_depth (mThDepth)
+        selects localisation mode: UpdateLastFrame's visual-odometry points (:878-930) are created
+        on the device first, with LastFrame.mDescriptors as their descriptors.  Neither frame is
+        modified.  Returns a dict: match (i32[F.N], LastFrame slot or -1, after the discard),
+        discarded (i32[F.N], the slot a discarded keypoint had, else -1), outlier (u8[F.N], the
+        optimiser's flags), Tcw (4x4 f32), nmatches_search, ninliers_pose, nmatches, nmatches_map,
+        and in localisation mode created (u8[LastFrame.N]) and created_pos (f32[LastFrame.N, 3],
+        zero where nothing was created), else None for both."""
+        n, m = F.N, max(F.N, 1)
+        nl = LastFrame.N
+        mp = LastFrame.map_points
+        has = np.ascontiguousarray(mp["valid"], np.uint8)
+        outl = np.ascontiguousarray(LastFrame.mvbOutlier, np.uint8)
+        xw = np.ascontiguousarray(mp["world_pos"], np.float32).reshape(nl, 3)
+        desc = np.ascontiguousarray(mp["descriptor"], np.uint8).reshape(nl, 32)
+        nobs = np.ascontiguousarray(mp["observations"], np.int32)
+        keys = np.ascontiguousarray(LastFrame.mvKeysUn)
+        if not (len(has) == len(outl) == len(nobs) == nl):
+            raise ValueError("track_with_motion_model: LastFrame arrays differ in length")
+        lf = LastFrameC(nl, has.ctypes.data, outl.ctypes.data, xw.ctypes.data, desc.ctypes.data, nobs.ctypes.data,
+                        keys.ctypes.data)
+        cf = CurFrameC(n, C.c_void_p(F.mvKeysUn.ctypes.data), C.c_void_p(F.mDescriptors.ctypes.data),
+                       C.c_void_p(F.mvuRight.ctypes.data))
+        vo = created = cpos = None
+        if depth is not None:
+            if th_depth is None:
+                raise ValueError("track_with_motion_model: depth without th_depth")
+            z = np.ascontiguousarray(depth, np.float32)
+            if len(z) != nl:
+                raise ValueError("track_with_motion_model: depth must have LastFrame.N entries")
+            created, cpos = np.zeros(max(nl, 1), np.uint8), np.zeros((max(nl, 1), 3), np.float32)
+            vo = VoPointsC(z.ctypes.data, LastFrame.mDescriptors.ctypes.data, float(th_depth), created.ctypes.data,
+                           cpos.ctypes.data)
+        T = np.ascontiguousarray(F.mTcw, np.float32).copy()
+        Tl = np.ascontiguousarray(LastFrame.mTcw, np.float32)
+        match, disc, out = np.full(m, -1, np.int32), np.full(m, -1, np.int32), np.zeros(m, np.uint8)
+        ns, nin, nm, nmap = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        self.check(lib().coeb_track_motion_model(
+            self.h, C.byref(camera), C.byref(cf), C.byref(lf), None if vo is None else C.byref(vo), _p(Tl), _p(T), th,
+            int(bool(bMono)), int(bool(check_orientation)), int(min_matches), _p(match), _p(disc), _p(out),
+            C.byref(ns), C.byref(nin), C.byref(nm), C.byref(nmap)))
+        return dict(match=match[:n], discarded=disc[:n], outlier=out[:n], Tcw=T.reshape(4, 4),
+                    nmatches_search=ns.value, ninliers_pose=nin.value, nmatches=nm.value, nmatches_map=nmap.value,
+                    created=None if created is None else created[:nl], created_pos=None if cpos is None else cpos[:nl])
 
     def bow_batch_device(self, levelsup=4):
         """The transform over the last extracted batch; results: batch_bow_results()."""

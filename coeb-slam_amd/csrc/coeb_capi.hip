@@ -979,6 +979,8 @@ int coeb_match_lastframe(coeb_ctx* c, const coeb_camera* cam, const coeb_curfram
     for (int i = 0; i < nl; i++)
         if (last->has_mappoint[i] && (last->keys_un[i].octave < 0 || last->keys_un[i].octave >= c->params.nlevels))
             return set_err(c, COEB_EINVAL, "coeb_match_lastframe: LastFrame keypoint octave outside the pyramid");
+    if (!match_lastframe_fits(cur->n, nl))
+        return set_err(c, COEB_ERANGE, "coeb_match_lastframe: the two frames exceed the LDS budget");
     (void)hipSetDevice(c->device);
     const int cs = std::max(n, 1), ls = std::max(nl, 1);
     int rc;
@@ -1430,6 +1432,137 @@ int coeb_track_reference_keyframe(coeb_ctx* c, const coeb_camera* cam, const coe
     if (n && discarded_out) memcpy(discarded_out, c->pin + o_dis, (size_t)n * 4);
     memcpy(Tcw, c->pin + o_T, 64);
     *nmatches_bow = hm[cs];
+    *ninliers_pose = hc[1];
+    *nmatches = hc[2];
+    *nmatches_map = hc[3];
+    return COEB_OK;
+}
+
+// One staged region on the device, as coeb_track_reference_keyframe's: the inputs (the last frame's
+// MapPoint arrays among them, which k_vo_points updates in place before k_match reads them), then the
+// results (counts and pose uploaded as their initial values; matches, discards, outlier flags and the
+// created points written by the kernels) copied back in one piece, then scratch.
+static_assert(kVoMaxLast == COEB_VO_MAX_LAST, "k_vo_points' limit is the header's");
+int coeb_track_motion_model(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe* cur, const coeb_lastframe* last,
+                            const coeb_vo_points* vo, const float Tcw_last[16], float Tcw[16], float th, int bmono,
+                            int check_orientation, int min_matches, int32_t* match_out, int32_t* discarded_out,
+                            uint8_t* outlier_out, int* nmatches_search, int* ninliers_pose, int* nmatches,
+                            int* nmatches_map)
+{
+    const std::string w("coeb_track_motion_model");
+    if (!c || !cam || !cur || !last || !Tcw_last || !Tcw || !nmatches_search || !ninliers_pose || !nmatches || !nmatches_map)
+        return set_err(c, COEB_EINVAL, w + ": invalid arguments");
+    const int n = cur->n, nl = last->n;
+    if (n < 0 || nl < 0) return set_err(c, COEB_EINVAL, w + ": negative frame size");
+    if (n > kCurMax) return set_err(c, COEB_EINVAL, w + ": more than 4095 current keypoints");
+    if (n && (!cur->keys_un || !cur->descriptors || !cur->u_right || !match_out))
+        return set_err(c, COEB_EINVAL, w + ": missing current-frame arrays");
+    if (nl && (!last->has_mappoint || !last->outlier || !last->world_pos || !last->mp_descriptor ||
+               !last->mp_observations || !last->keys_un))
+        return set_err(c, COEB_EINVAL, w + ": missing LastFrame arrays");
+    if (vo && nl && (!vo->depth || !vo->descriptors)) return set_err(c, COEB_EINVAL, w + ": missing visual-odometry arrays");
+    if (vo && nl > COEB_VO_MAX_LAST) return set_err(c, COEB_EINVAL, w + ": more LastFrame keypoints than COEB_VO_MAX_LAST");
+    if (!match_lastframe_fits(n, nl)) return set_err(c, COEB_ERANGE, w + ": the two frames exceed the LDS budget");
+    // which keypoints take a point, and which LastFrame slots get one, is decided on the device: k_pose
+    // indexes mvInvLevelSigma2[octave] of the former, k_match mvScaleFactors[octave] of the latter
+    for (int i = 0; i < n; i++)
+        if (cur->keys_un[i].octave < 0 || cur->keys_un[i].octave >= c->tab.nlevels)
+            return set_err(c, COEB_EINVAL, w + ": keypoint octave outside the pyramid");
+    for (int i = 0; i < nl; i++)
+        if (last->keys_un[i].octave < 0 || last->keys_un[i].octave >= c->tab.nlevels)
+            return set_err(c, COEB_EINVAL, w + ": LastFrame keypoint octave outside the pyramid");
+    (void)hipSetDevice(c->device);
+    const int cs = std::max(n, 1), ls = std::max(nl, 1);
+    const bool run_vo = vo && nl;
+    int rc;
+    uint8_t* dbase;
+    SingleFrameBufs& sf = c->sf;
+    if ((rc = ensure(c, sf.m_scr, (size_t)ls * kCQ)) || (rc = ensure(c, sf.m_qn, (size_t)ls + kMaxSplit)) ||
+        (rc = ensure(c, c->ex.err, 4)) || (rc = ensure(c, sf.p_act, cs)) || (rc = ensure(c, sf.p_edge, cs)) ||
+        (rc = ensure(c, sf.p_chi, cs)))
+        return rc;
+    hipStream_t s = main_stream(c);
+    const int32_t cnts[2] = {n, nl};
+    Pack pk;
+    const size_t o_cn = pk.add(cnts, 8), o_T0 = pk.add(Tcw, 64), o_Tl = pk.add(Tcw_last, 64);
+    const size_t o_ck = pk.add(cur->keys_un, (size_t)n * sizeof(coeb_keypoint)), o_cd = pk.add(cur->descriptors, (size_t)n * 32);
+    const size_t o_ur = pk.add(cur->u_right, (size_t)n * 4);
+    const size_t o_lk = pk.add(last->keys_un, (size_t)nl * sizeof(coeb_keypoint));
+    const size_t o_ld = pk.add(last->mp_descriptor, (size_t)nl * 32), o_h = pk.add(last->has_mappoint, (size_t)nl);
+    const size_t o_o = pk.add(last->outlier, (size_t)nl), o_xw = pk.add(last->world_pos, (size_t)nl * 12);
+    const size_t o_nb = pk.add(last->mp_observations, (size_t)nl * 4);
+    const size_t o_vz = run_vo ? pk.add(vo->depth, (size_t)nl * 4) : 0, o_vd = run_vo ? pk.add(vo->descriptors, (size_t)nl * 32) : 0;
+    const size_t o_is = pk.add(c->tab.inv_sigma2, sizeof(float) * COEB_MAXL);
+    // results with an initial value: {the optimiser's n, ninliers_pose, nmatches, nmatches_map}, the pose k_pose updates
+    const int32_t cnt[4] = {0, 0, 0, 0};
+    const size_t o_cnt = pk.add(cnt, 16), o_T = pk.add(Tcw, 64);
+    // results the kernels write (not uploaded), then scratch
+    size_t at = pk.total;
+    auto take = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 15) & ~(size_t)15; return o; };
+    const size_t o_m = take(((size_t)cs + 1) * 4), o_dis = take((size_t)cs * 4), o_out = take((size_t)cs);
+    const size_t o_cr = take(run_vo ? (size_t)nl : 0), o_cp = take(run_vo ? (size_t)nl * 12 : 0);
+    const size_t back_end = at;
+    const size_t o_has = take((size_t)cs), o_px = take((size_t)cs * 12);
+    const size_t o_err = at;
+    if ((rc = pinned(c, o_err + 16)) || (rc = ensure(c, c->ex.stage, at)) || (rc = stage_in(c, pk, &dbase, s))) return rc;
+    int32_t* dcnt = (int32_t*)(dbase + o_cnt);
+    if (run_vo) {
+        VoBufs v;
+        v.n = nl; v.kps = dbase + o_lk; v.depth = (const float*)(dbase + o_vz); v.desc_in = dbase + o_vd;
+        v.Tcw_last = (const float*)(dbase + o_Tl); v.th_depth = vo->th_depth;
+        v.fx = cam->fx; v.fy = cam->fy; v.cx = cam->cx; v.cy = cam->cy;
+        v.has = dbase + o_h; v.xw = (float*)(dbase + o_xw); v.desc = dbase + o_ld; v.nobs = (int*)(dbase + o_nb);
+        v.created = dbase + o_cr; v.created_pos = (float*)(dbase + o_cp);
+        if (launch_vo_points(v, s, &c->hook)) return hip_err(c, hipGetLastError(), "launch_vo_points");
+    }
+    MatchBufs mb;
+    memset(&mb, 0, sizeof(mb));
+    mb.cur_kps = dbase + o_ck; mb.cur_desc = dbase + o_cd; mb.cur_n = (const int32_t*)(dbase + o_cn);
+    mb.cur_ur = (const float*)(dbase + o_ur); mb.cur_stride = cs;
+    mb.last_kps = dbase + o_lk; mb.last_desc = dbase + o_ld; mb.last_n = (const int32_t*)(dbase + o_cn) + 1;
+    mb.last_has = dbase + o_h; mb.last_out = dbase + o_o; mb.last_xw = (const float*)(dbase + o_xw);
+    mb.last_nobs = (const int32_t*)(dbase + o_nb); mb.last_stride = ls;
+    mb.Tcw_cur = (const float*)(dbase + o_T0); mb.Tcw_last = (const float*)(dbase + o_Tl);
+    mb.match = (int*)(dbase + o_m); mb.nmatch = mb.match + cs; mb.scratch = sf.m_scr.p; mb.scratch_stride = ls * kCQ;
+    mb.err = c->ex.err.p; mb.qn = sf.m_qn.p; mb.qn_stride = mb.last_stride + kMaxSplit;
+    // the 2*th retry below min_matches (:954-958) runs inside k_match
+    if (launch_match(make_cam(c, cam), mb, 1, th, bmono, check_orientation, min_matches, s, &c->hook))
+        return hip_err(c, hipGetLastError(), "launch_match");
+    // the gate (:960) and the gather are TrackReferenceKeyFrame's with the last frame's slots in the
+    // KeyFrame's place
+    TrkBufs t;
+    t.cur_n = n; t.match = mb.match; t.nm_bow = mb.nmatch; t.min_matches = min_matches;
+    t.kf_xw = mb.last_xw; t.kf_nobs = mb.last_nobs;
+    t.has = dbase + o_has; t.xw = (float*)(dbase + o_px); t.pose_n = dcnt; t.outl = dbase + o_out;
+    t.discarded = (int*)(dbase + o_dis); t.nmatches = dcnt + 2; t.nmap = dcnt + 3;
+    if (launch_trk_pose_prep(t, s, &c->hook)) return hip_err(c, hipGetLastError(), "launch_trk_pose_prep");
+    PoseBufs p;
+    p.n = dcnt; p.has_mp = t.has; p.xw = t.xw; p.kps = dbase + o_ck; p.ur = (const float*)(dbase + o_ur);
+    p.inv_sigma2 = (const float*)(dbase + o_is); p.Tcw = (float*)(dbase + o_T); p.outlier = t.outl;
+    p.result = dcnt + 1; p.edges = sf.p_edge.p; p.active = sf.p_act.p; p.chi2 = sf.p_chi.p;
+    p.stride = cs; p.timing = nullptr;
+    if (launch_pose(p, 1, cam->fx, cam->fy, cam->cx, cam->cy, cam->bf, s, &c->hook))
+        return hip_err(c, hipGetLastError(), "launch_pose");
+    if (launch_mm_tail(t, s, &c->hook)) return hip_err(c, hipGetLastError(), "launch_mm_tail");
+    HIP_TRY(c, hipMemcpyAsync(c->pin + o_cnt, dbase + o_cnt, back_end - o_cnt, hipMemcpyDeviceToHost, s));
+    if ((rc = err_word_async(c, c->pin + o_err))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if ((rc = err_word_seen(c, c->pin + o_err))) return rc;
+    int32_t hc[4];
+    memcpy(hc, c->pin + o_cnt, 16);
+    const int32_t* hm = reinterpret_cast<const int32_t*>(c->pin + o_m);
+    if (n) memcpy(match_out, hm, (size_t)n * 4);
+    if (n && discarded_out) memcpy(discarded_out, c->pin + o_dis, (size_t)n * 4);
+    if (n && outlier_out) memcpy(outlier_out, c->pin + o_out, (size_t)n);
+    if (run_vo) {
+        const uint8_t* hcr = c->pin + o_cr;
+        if (vo->created_out) memcpy(vo->created_out, hcr, (size_t)nl);
+        if (vo->created_pos)
+            for (int i = 0; i < nl; i++)
+                if (hcr[i]) memcpy(vo->created_pos + 3 * (size_t)i, c->pin + o_cp + 12 * (size_t)i, 12);
+    }
+    memcpy(Tcw, c->pin + o_T, 64);
+    *nmatches_search = hm[cs];
     *ninliers_pose = hc[1];
     *nmatches = hc[2];
     *nmatches_map = hc[3];

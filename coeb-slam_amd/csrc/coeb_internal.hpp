@@ -346,6 +346,32 @@ struct TrkBufs {
 int launch_trk_pose_prep(const TrkBufs& t, hipStream_t s, ProfileHook* prof);
 int launch_trk_tail(const TrkBufs& t, hipStream_t s, ProfileHook* prof);
 
+// Tracking::TrackWithMotionModel on one host frame (coeb_track.hip), every array in device memory:
+// k_vo_points (localisation mode only) -> k_match_lists -> k_match (retry in-kernel) ->
+// k_trk_pose_prep -> k_pose -> k_mm_tail, no host step between.  The gate and the gather are
+// TrackReferenceKeyFrame's with the last frame's slots in the KeyFrame's place (TrkBufs.kf_xw /
+// kf_nobs = the arrays below); the tail counts nmatches as the reference does here (k_mm_tail).
+//
+// k_vo_points: Tracking::UpdateLastFrame's "visual odometry" points (Tracking.cc:878-930) written
+// into the last-frame arrays k_match reads.
+constexpr int kVoMaxLast = 16384;   // last-frame keypoints k_vo_points ranks (their depths sit in LDS)
+struct VoBufs {
+    int n;                        // LastFrame.N
+    const void* kps;              // [n] coeb_keypoint, LastFrame.mvKeysUn
+    const float* depth;           // [n] LastFrame.mvDepth
+    const uint8_t* desc_in;       // [n][32] LastFrame.mDescriptors
+    const float* Tcw_last;        // [16] LastFrame.mTcw
+    float th_depth, fx, fy, cx, cy;
+    // the last frame as the caller snapshot it; a created point replaces slot i in place
+    uint8_t* has; float* xw; uint8_t* desc; int* nobs;
+    uint8_t* created;             // [n] 1 where a point was created, else 0
+    float* created_pos;           // [n][3] written where created
+};
+int launch_vo_points(const VoBufs& v, hipStream_t s, ProfileHook* prof);
+int launch_mm_tail(const TrkBufs& t, hipStream_t s, ProfileHook* prof);
+// launch_match's LDS-budget verdict for one pair of cur_n x last_n keypoints, before anything is enqueued
+bool match_lastframe_fits(int cur_n, int last_n);
+
 // relocalisation projection search (ORBmatcher::SearchByProjection(Frame&, KeyFrame*, set, th, ORBdist))
 struct KfBufs {
     const void* cur_kps; const uint8_t* cur_desc; const uint8_t* cur_has; int cur_n;

@@ -1493,6 +1493,12 @@ int launch_match_local(const MatchCam& cam, const LocalBufs& b, float th, float 
 }
 
 bool match_local_fits(int cur_n, int mp_n) { return lds_form(std::max(cur_n, 1), std::max(mp_n, 1)).fits; }
+// One pair takes split lists, so k_match runs unstaged; its static LDS (histogram, flags and the
+// claim phase's: 336 bytes) comes on top of the dynamic bytes, more than lds_form's 256 allow for.
+bool match_lastframe_fits(int cur_n, int last_n)
+{
+    return match_lds_bytes(std::max(cur_n, 1), std::max(last_n, 1), false, nullptr) + 512 <= (size_t)kLdsLimit;
+}
 
 int launch_match_kf(const MatchCam& cam, const KfBufs& b, float th, int orb_dist, int check_ori, hipStream_t s,
                     ProfileHook* prof)

@@ -20,6 +20,10 @@
 // Tracking::TrackReferenceKeyFrame on one host frame (coeb_track_reference_keyframe,
 // src/Tracking.cc:823-865): behind SearchByBoW (coeb_bow.hip) k_trk_pose_prep -> k_pose -> k_trk_tail.
 //
+// Tracking::TrackWithMotionModel on one host frame (coeb_track_motion_model, src/Tracking.cc:933-994
+// with UpdateLastFrame's visual-odometry points, :878-930): k_vo_points in front of the last-frame
+// search (coeb_match.hip), then k_trk_pose_prep -> k_pose -> k_mm_tail.
+//
 // Batch launch order: k_tlm_snapshot on the context stream (it copies every batch array the rest
 // reads, so the next batch's extraction may overwrite them), then on the pose stream after
 // the first k_pose: k_tlm_discard -> k_tlm_frustum -> k_match_local -> k_tlm_pose_prep -> k_pose.
@@ -288,7 +292,126 @@ __global__ __launch_bounds__(kT) void k_trk_tail(TrkBufs t)
     if (threadIdx.x == 1 && s_cnt[1]) atomicAdd(t.nmap, s_cnt[1]);
 }
 
+// ---- k_mm_tail: TrackWithMotionModel's "Discard outliers" (:966-985) ----
+// As k_trk_tail over the last frame's slots, but for nmatches: SearchByProjection's return counts
+// assignments, and a keypoint two last-frame points were assigned to counts twice while holding one
+// point (ORBmatcher.cc:1425-1426), so nmatches is that return less the discards (`nmatches--`),
+// not the number of keypoints that keep a point.  nmatches / nmap zero on entry.
+__global__ __launch_bounds__(kT) void k_mm_tail(TrkBufs t)
+{
+    __shared__ int s_cnt[2];
+    const int i = blockIdx.x * kT + threadIdx.x;
+    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int nm = *t.nm_bow;
+    const bool go = nm >= t.min_matches;
+    bool out = false, map = false;
+    if (i < t.cur_n) {
+        const int m = t.match[i];
+        out = go && m >= 0 && t.outl[i];
+        t.discarded[i] = out ? m : -1;
+        if (out) t.match[i] = -1;
+        map = go && m >= 0 && !out && t.kf_nobs[m] > 0;
+    }
+    const uint64_t bo = __ballot(out), bm = __ballot(map);
+    if ((threadIdx.x & 63) == 0) {
+        if (bo) atomicAdd(&s_cnt[0], (int)__popcll(bo));
+        if (bm) atomicAdd(&s_cnt[1], (int)__popcll(bm));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int d = (blockIdx.x == 0 ? nm : 0) - s_cnt[0];
+        if (d) atomicAdd(t.nmatches, d);
+    }
+    if (threadIdx.x == 1 && s_cnt[1]) atomicAdd(t.nmap, s_cnt[1]);
+}
+
+// ---- k_vo_points: UpdateLastFrame's "visual odometry" points (Tracking.cc:878-930) ----
+// The reference sorts (depth, index) over the keypoints with depth > 0 and walks the order,
+// counting every entry, until one is farther than th_depth with more than 100 counted.  With M
+// entries, c of them not farther than th_depth, entry j (from 0) is reached iff no earlier entry
+// stopped the walk, and entry j' stops it iff j' >= 100 and j' >= c: the visited entries are
+// j <= max(c, 100).  Every workgroup stages all depths in LDS (-1 where not > 0: NaN, 0,
+// negative); thread i counts the entries that precede its own, (z_j, j) < (z_i, i), and c.  A
+// visited keypoint whose slot holds no point or one nobody observes gets Frame::UnprojectStereo(i)
+// (Frame.cc:844-858) with mRwc / mOw from Tcw_last as UpdatePoseMatrices forms them, its own
+// descriptor and Observations() = 0.
+__global__ __launch_bounds__(kT) void k_vo_points(VoBufs v)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_z[];    // n rounded up to 4 entries, the pad -1
+    const int n = v.n, n4 = (n + 3) & ~3;
+    for (int j = threadIdx.x; j < n4; j += kT) {
+        const float z = j < n ? v.depth[j] : -1.0f;
+        s_z[j] = z > 0 ? z : -1.0f;
+    }
+    __syncthreads();
+    const int i = blockIdx.x * kT + threadIdx.x;
+    if (i >= n) return;
+    const float zi = s_z[i];
+    int before = 0, close = 0;
+#pragma unroll 4
+    for (int j = 0; j < n4; j += 4) {                      // four depths per LDS read
+        const float4 q = *reinterpret_cast<const float4*>(s_z + j);
+        const float zq[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const float zj = zq[k];
+            const bool in = zj > 0;
+            before += in && (zj < zi || (zj == zi && j + k < i));
+            close += in && !(zj > v.th_depth);             // the walk stops on `z > mThDepth` only
+        }
+    }
+    const bool visited = zi > 0 && before <= max(close, 100);
+    const bool create = visited && (!v.has[i] || v.nobs[i] < 1);
+    v.created[i] = create ? 1 : 0;
+    if (!create) return;
+    const KpT kp = reinterpret_cast<const KpT*>(v.kps)[i];
+    const float invfx = 1.0f / v.fx, invfy = 1.0f / v.fy;
+    const float Xc[3] = {(kp.x - v.cx) * zi * invfx, (kp.y - v.cy) * zi * invfy, zi};
+    const float* T = v.Tcw_last;
+    float Twc[12], P[3];
+    for (int k = 0; k < 3; k++) {                          // mRwc = mRcw.t(), mOw = -mRcw.t()*mtcw (GEMM_1_T)
+        double s = (double)T[0 * 4 + k] * T[3] + (double)T[1 * 4 + k] * T[7];
+        s = s + (double)T[2 * 4 + k] * T[11];
+        Twc[k * 4 + 0] = T[0 * 4 + k];
+        Twc[k * 4 + 1] = T[1 * 4 + k];
+        Twc[k * 4 + 2] = T[2 * 4 + k];
+        Twc[k * 4 + 3] = (float)(s * -1.0);
+    }
+    gemm_add(Twc, Xc, P);                                  // mRwc*x3Dc + mOw
+    for (int k = 0; k < 3; k++) {
+        v.xw[3 * i + k] = P[k];
+        v.created_pos[3 * i + k] = P[k];
+    }
+    v.has[i] = 1;
+    v.nobs[i] = 0;
+    const uint4* src = reinterpret_cast<const uint4*>(v.desc_in + (int64_t)i * 32);
+    uint4* dst = reinterpret_cast<uint4*>(v.desc + (int64_t)i * 32);
+    dst[0] = src[0];
+    dst[1] = src[1];
+}
+
 }  // namespace
+
+int launch_mm_tail(const TrkBufs& t, hipStream_t s, ProfileHook* prof)
+{
+    if (t.cur_n <= 0) return 0;                     // nothing can match: nmatches and nmap stay 0
+    prof_begin(prof, "k_mm_tail", s);
+    hipLaunchKernelGGL(k_mm_tail, dim3((t.cur_n + kT - 1) / kT), dim3(kT), 0, s, t);
+    prof_end(prof, s);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_vo_points(const VoBufs& v, hipStream_t s, ProfileHook* prof)
+{
+    if (v.n <= 0) return 0;
+    if (v.n > kVoMaxLast) return -2;
+    lds_limit_max((const void*)k_vo_points);        // kVoMaxLast depths are the default limit exactly
+    prof_begin(prof, "k_vo_points", s);
+    hipLaunchKernelGGL(k_vo_points, dim3((v.n + kT - 1) / kT), dim3(kT), (size_t)((v.n + 3) & ~3) * sizeof(float), s, v);
+    prof_end(prof, s);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 
 int launch_frustum(const MatchCam& cam, const LmBufs& t, hipStream_t s, ProfileHook* prof)
 {

@@ -76,6 +76,12 @@
  *                                      (:835), Optimizer::PoseOptimization (:841) and the outlier
  *                                      discard with nmatchesMap (:843-862) on one host frame, one
  *                                      call and one synchronisation
+ *   coeb_track_motion_model         <- Tracking::TrackWithMotionModel  src/Tracking.cc:933-994 with
+ *                                      UpdateLastFrame's visual-odometry points (:878-930):
+ *                                      SearchByProjection (:951), the 2*th retry (:954-958), the
+ *                                      nmatches < 20 gate (:960), Optimizer::PoseOptimization (:964)
+ *                                      and the outlier discard with nmatchesMap (:966-985) on one
+ *                                      host frame, one call and one synchronisation
  *   coeb_bow_vector                 <- DBoW2 BowVector::addWeight / normalize(L1) as transform() fills
  *                                      mBowVec (host only; restated, parity against DBoW2 UNPINNED)
  *   coeb_kfdb_add / _erase / _clear <- KeyFrameDatabase::add / erase / clear
@@ -514,6 +520,67 @@ int coeb_track_reference_keyframe(coeb_ctx* ctx, const coeb_camera* cam, const c
                                   int32_t* word_out, int32_t* node_out, double* weight_out,
                                   int32_t* match_out, int32_t* discarded_out, int* nmatches_bow,
                                   int* ninliers_pose, int* nmatches, int* nmatches_map);
+
+/* What Tracking::UpdateLastFrame (Tracking.cc:867-931) needs in localisation mode (mbOnlyTracking)
+ * to create its "visual odometry" MapPoints on the last frame. */
+typedef struct {
+    const float* depth;               /* last->n, LastFrame.mvDepth */
+    const uint8_t* descriptors;       /* last->n x 32, LastFrame.mDescriptors (a new MapPoint copies its row) */
+    float th_depth;                   /* mThDepth */
+    uint8_t* created_out;             /* last->n, 1 where a temporary MapPoint was created, else 0; may be NULL */
+    float* created_pos;               /* last->n x 3, its position, written where created; may be NULL */
+} coeb_vo_points;
+
+/* The most LastFrame keypoints coeb_track_motion_model accepts with vo != NULL. */
+#define COEB_VO_MAX_LAST 16384
+
+/* ---- Tracking::TrackWithMotionModel (Tracking.cc:933-994) on one host frame ----
+ * One upload, one download and one synchronisation; in the reference's order:
+ *   - UpdateLastFrame's visual-odometry points (:878-930), only with vo != NULL (NULL: SLAM mode,
+ *     :875 returns early).  The keypoints of `last` with vo->depth > 0 (NaN, 0 and negative are out)
+ *     are taken in the order of sort(vector<pair<float,int>>), by depth then index, and walked until
+ *     the first one farther than vo->th_depth with more than 100 counted.  A visited keypoint whose
+ *     slot has !has_mappoint or mp_observations < 1 gets a new MapPoint: position
+ *     Frame::UnprojectStereo(i) (Frame.cc:844-858: ((u - cx) z / fx, (v - cy) z / fy, z) from
+ *     last->keys_un and cam, taken to the world by mRwc and mOw of Tcw_last), descriptor
+ *     vo->descriptors[i], Observations() = 0.  last->outlier is left as it is: a replaced slot with
+ *     mvbOutlier set is still skipped by the search.  The caller's arrays are not modified;
+ *     vo->created_out / created_pos report what was created (the caller news the MapPoints and
+ *     appends them to mlpTemporalPoints).  At most COEB_VO_MAX_LAST last-frame keypoints.
+ *   - SearchByProjection(CurrentFrame, LastFrame, th, bMono) as coeb_match_lastframe, over the last
+ *     frame as the step above left it, from the pose Tcw (mVelocity * mLastFrame.mTcw); with fewer
+ *     than min_matches (the reference uses 20) the search runs again with 2 * th (:954-958).
+ *     *nmatches_search = the final return value.
+ *   - the gate (:960): with *nmatches_search < min_matches the call stops: match_out holds the last
+ *     search's assignments, discarded_out is all -1, outlier_out all 0, Tcw is untouched,
+ *     *ninliers_pose = 0, *nmatches = *nmatches_search and *nmatches_map = 0.
+ *   - PoseOptimization (:964) from Tcw over the keypoints that got a match: position = that of the
+ *     last-frame slot match_out[i] (created points included), measurement cur->keys_un[i] with
+ *     cur->u_right[i] (< 0: monocular edge), information the context's mvInvLevelSigma2.  Tcw holds
+ *     the optimised pose on return; with fewer than 3 edges it is untouched and *ninliers_pose = 0
+ *     (reachable with min_matches <= 2).
+ *   - the discard loop (:966-985): a matched keypoint flagged outlier loses its point, match_out[i] =
+ *     -1 and discarded_out[i] = the last-frame slot it held (the caller sets mbTrackInView = false and
+ *     mnLastFrameSeen on that MapPoint); discarded_out is -1 everywhere else.  outlier_out[i] = the
+ *     optimiser's flag, 1 exactly on the discarded keypoints (the reference resets mvbOutlier there).
+ *     *nmatches = *nmatches_search minus the discarded (the search's return counts assignments, so
+ *     both can exceed the number of keypoints that hold a point); *nmatches_map = the kept keypoints whose point
+ *     has Observations() > 0, so created points never count.  The caller applies :987-993: in
+ *     localisation mode mbVO = *nmatches_map < 10 and the verdict is *nmatches > 20, otherwise the
+ *     verdict is *nmatches_map >= 10.
+ * match_out has cur->n entries; discarded_out and outlier_out (cur->n each) may be NULL.
+ * COEB_EINVAL, with nothing written, for a missing required pointer or array, a negative size, more
+ * than 4095 current keypoints, a last-frame or current keypoint octave outside the pyramid (every
+ * keypoint of both frames is checked: which slots take a point is decided on the device), vo given
+ * with depth or descriptors missing, or vo given with last->n > COEB_VO_MAX_LAST.  COEB_ERANGE, with
+ * nothing written, when the two frames exceed the matcher's LDS budget (as coeb_match_lastframe
+ * fails: 4095 current keypoints leave room for 14780 last-frame ones).  n == 0 on either side is
+ * COEB_OK with zero counts. */
+int coeb_track_motion_model(coeb_ctx* ctx, const coeb_camera* cam, const coeb_curframe* cur,
+                            const coeb_lastframe* last, const coeb_vo_points* vo, const float Tcw_last[16],
+                            float Tcw[16], float th, int bmono, int check_orientation, int min_matches,
+                            int32_t* match_out, int32_t* discarded_out, uint8_t* outlier_out,
+                            int* nmatches_search, int* ninliers_pose, int* nmatches, int* nmatches_map);
 
 /* ---- BowVector filling: addWeight in feature order, then normalize(L1) (host only, no context) ----
  * For every feature i < n with node[i] >= 0 (coeb_bow_transform's "weight > 0"), in order:
