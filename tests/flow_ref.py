@@ -7,10 +7,20 @@ runs the comparisons; every bound below is stated in the model's own quantities.
 
 u = 2^-24 is the float32 unit roundoff throughout.
 
-Left out: the RANSAC / LMeDS loops of findFundamentalMat draw their samples from OpenCV's RNG and
-stop by its iteration rule; they cannot be restated independently and stay with the bit-for-bit
-tests (tests/test_gpu_flow.py, tests/test_oracle_flow.py).  Only the 7-point solver is modelled.
+findFundamentalMat's sampling loops are modelled too (find_fundamental, moving_tail below): the
+RNG, getSubset and its retry rule, the last-point collinearity test, RANSACUpdateNumIters, the
+RANSAC acceptance scan and the LMedS median, sigma and inlier rule, from ptsetreg.cpp and
+fundam.cpp.  The 7-point models themselves are passed in (the tests pass the oracle's run7Point,
+which test_seven_point holds against the SVD model seven_point), so the loops are compared bit for
+bit: the same models scored by the same float32 errors give the same winner.
+
+Still not reached or pinned: "subset not found" after iteration 0 is reached in LMedS only (1000
+attempts, fm_sets.rare_subset); under RANSAC's 10000 attempts no input found produces it.  An
+LMedS result dropped for fewer than 7 inliers and a non-finite error were not found either: a
+model fits its own seven points.  Parity with a real OpenCV build stays unpinned, as OpenCV is
+absent here.
 """
+import math
 from fractions import Fraction
 
 import numpy as np
@@ -296,3 +306,239 @@ def epipolar_residuals(F, m1, m2):
     nF = np.linalg.norm(F)
     r = np.abs(np.einsum("ni,ij,nj->n", h2, F, h1)) / (nF * np.linalg.norm(h1, axis=1) * np.linalg.norm(h2, axis=1))
     return r, abs(np.linalg.det(F)) / nF ** 3
+
+
+# ============================================================ findFundamentalMat's sampling loops
+# the decisions a reading of OpenCV can get wrong, each switchable (find_fundamental / moving_tail
+# `mut`), so that tests/test_flow_ref.py can show that a directed set notices every one of them
+MUTATIONS = ("accept_gt_max_good",        # RANSAC accepts on good > max_good, without the floor of 6
+             "retry_not_counted",         # a collinear redraw does not count towards maxAttempts
+             "collinear_all_triples",     # every triple of the subset instead of those with the 7th point
+             "collinear_first_six",       # the test stops one point short: triples with the 6th point
+             "median_low",                # element (n - 1) // 2 of the sorted errors
+             "no_min_three",              # LMedS without max(niters, 3)
+             "good_gt_7",                 # LMedS keeps its model on good > 7
+             "d_lt_1",                    # T_M takes d < 1 in place of not (d <= 1)
+             "edge_off_by_one")           # the upper edge bound admits n - edge
+DBL_MIN, DBL_MAX, DBL_EPSILON = 2.0 ** -1022, float(np.finfo(np.float64).max), 2.0 ** -52
+
+
+class Rng:
+    """cv::RNG((uint64)-1): multiply-with-carry on a 64-bit state, the output its low 32 bits."""
+
+    def __init__(self):
+        self.state = 2 ** 64 - 1
+
+    def __call__(self):
+        self.state = (self.state & 0xffffffff) * 4164903690 + (self.state >> 32)      # < 2^64: no wrap to model
+        return self.state & 0xffffffff
+
+
+def update_iters(p, ep, max_iters, halves=None):
+    """RANSACUpdateNumIters(p, ep, 7, max_iters) = round(log(1 - p) / log(1 - (1 - ep)^7)), capped at
+    max_iters, 0 when no outlier is left.  `halves` collects |frac(num / denom) - 1/2|, the distance
+    of the rounded quotient from a tie: the oracle takes its log from fdlibm, this one from libm."""
+    p, ep = min(max(p, 0.0), 1.0), min(max(ep, 0.0), 1.0)
+    num = max(1.0 - p, DBL_MIN)
+    denom = 1.0 - (1.0 - ep) ** 7
+    if denom < DBL_MIN:
+        return 0
+    num, denom = math.log(num), math.log(denom)
+    if denom >= 0 or -num >= max_iters * -denom:
+        return max_iters
+    q = num / denom
+    if halves is not None:
+        halves.append(abs(q - math.floor(q) - 0.5))
+    return round(q)                                             # cvRound: ties to even, as Python's
+
+
+def collinear(s, mut=frozenset()):
+    """haveCollinearPoints on a (7, 2) float32 subset: a triple with the last point is collinear when
+    |dx2 dy1 - dy2 dx1| <= FLT_EPSILON (|dx1| + |dy1| + |dx2| + |dy2|), the differences taken in
+    float32 and widened."""
+    lasts = range(2, 7) if "collinear_all_triples" in mut else (5,) if "collinear_first_six" in mut else (6,)
+    for i in lasts:
+        d = (s[:i] - s[i]).astype(np.float64).tolist()
+        for j in range(i):
+            dx1, dy1 = d[j]
+            for k in range(j):
+                dx2, dy2 = d[k]
+                if abs(dx2 * dy1 - dy2 * dx1) <= FLT_EPSILON * (abs(dx1) + abs(dy1) + abs(dx2) + abs(dy2)):
+                    return True
+    return False
+
+
+def get_subset(m1, m2, rng, max_attempts, mut=frozenset()):
+    """getSubset: seven distinct indices rng() % n (a repeated index is drawn again); a subset with a
+    collinear triple on either side costs one attempt and is drawn afresh.  (indices or None after
+    max_attempts, number of redraws)."""
+    n, attempts, retries = len(m1), 0, 0
+    while attempts < max_attempts and retries < 50 * max_attempts:      # the second bound ends the mutated form
+        idx = []
+        while len(idx) < 7:
+            i = rng() % n
+            if i not in idx:
+                idx.append(i)
+        if not (collinear(m1[idx], mut) or collinear(m2[idx], mut)):
+            return idx, retries
+        retries += 1
+        attempts += "retry_not_counted" not in mut
+    return None, retries
+
+
+def fm_errors(F, m1, m2, dtype=np.float64):
+    """FMEstimatorCallback::computeError: the larger of the two squared point-to-epipolar-line
+    distances, every operation elementwise in `dtype` and in OpenCV's written order, rounded once
+    to float32."""
+    f = [dtype(v) for v in np.asarray(F, np.float64).ravel()]
+    x1, y1, x2, y2 = m1[:, 0].astype(dtype), m1[:, 1].astype(dtype), m2[:, 0].astype(dtype), m2[:, 1].astype(dtype)
+    one = dtype(1)
+    with np.errstate(all="ignore"):
+        a = f[0] * x1 + f[1] * y1 + f[2]
+        b = f[3] * x1 + f[4] * y1 + f[5]
+        c = f[6] * x1 + f[7] * y1 + f[8]
+        s2 = one / (a * a + b * b)
+        d2 = x2 * a + y2 * b + c
+        a = f[0] * x2 + f[3] * y2 + f[6]
+        b = f[1] * x2 + f[4] * y2 + f[7]
+        c = f[2] * x2 + f[5] * y2 + f[8]
+        s1 = one / (a * a + b * b)
+        d1 = x1 * a + y1 * b + c
+        e1, e2 = d1 * d1 * s1, d2 * d2 * s2
+        return np.where(e1 < e2, e2, e1).astype(np.float32)             # std::max(e1, e2)
+
+
+def svd_solver(s1, s2):
+    """The module's own 7-point models in the solver interface, scaled to F33 = 1."""
+    Fs = seven_point(s1, s2)[0]
+    return len(Fs), [F / F[2, 2] if abs(F[2, 2]) > DBL_EPSILON else F for F in Fs]
+
+
+def _fm_run(m1, m2, thr, conf, solver, mut, dtype):
+    n = len(m1)
+    info = dict(branch="few" if n < 7 else "seven" if n == 7 else "lmeds" if n < 15 else "ransac", iterations=[],
+                winner=None, nonfinite=0, halves=[], niters=None, ran=0, good=None, not_found=False)
+    if n < 7:
+        return None, info
+    if n == 7:
+        cnt, models = solver(m1, m2)
+        info["iterations"].append(dict(subset=list(range(7)), retries=0, nmodels=cnt, scores=[], niters=[]))
+        if cnt <= 0:
+            return None, info
+        info["winner"] = (0, 0)
+        return np.array(models[0], np.float64).reshape(3, 3), info
+    ransac = n >= 15
+    rng, best = Rng(), None
+    if ransac:
+        niters, max_good, t = 1000, 0, np.float32(thr * thr)
+    else:
+        niters = update_iters(conf, 0.45, 1000, info["halves"])
+        niters = niters if "no_min_three" in mut else max(niters, 3)
+        min_med = DBL_MAX
+    it = 0
+    while it < niters:
+        idx, retries = get_subset(m1, m2, rng, 10000 if ransac else 1000, mut)
+        rec = dict(subset=idx, retries=retries, nmodels=None, scores=[], niters=[])
+        info["iterations"].append(rec)
+        if idx is None:
+            info["not_found"] = True
+            if it == 0:
+                info["niters"], info["ran"] = niters, 1
+                return None, info
+            break
+        cnt, models = solver(m1[idx], m2[idx])
+        rec["nmodels"] = cnt
+        for k in range(max(cnt, 0)):
+            e = fm_errors(models[k], m1, m2, dtype)
+            info["nonfinite"] += int(np.count_nonzero(~np.isfinite(e)))
+            if ransac:
+                good = int(np.count_nonzero(e <= t))
+                rec["scores"].append(good)
+                if good > max(max_good, 0 if "accept_gt_max_good" in mut else 6):
+                    best, max_good, info["winner"] = np.array(models[k], np.float64).reshape(3, 3), good, (it, k)
+                    niters = update_iters(conf, (n - good) / n, niters, info["halves"])
+                    rec["niters"].append(niters)
+            else:
+                med = float(np.sort(e)[(n - 1) // 2 if "median_low" in mut else n // 2])
+                rec["scores"].append(med)
+                if med < min_med:
+                    best, min_med, info["winner"] = np.array(models[k], np.float64).reshape(3, 3), med, (it, k)
+        it += 1
+    info["niters"], info["ran"] = niters, len(info["iterations"])
+    if ransac:
+        info["good"] = max_good
+        return (best if max_good > 0 else None), info
+    if not min_med < DBL_MAX:
+        return None, info
+    sigma = max(2.5 * 1.4826 * (1 + 5.0 / (n - 7)) * math.sqrt(min_med), 0.001)
+    e = fm_errors(best, m1, m2, dtype)
+    info["good"] = int(np.count_nonzero(e <= np.float32(sigma * sigma)))
+    ok = info["good"] > 7 if "good_gt_7" in mut else info["good"] >= 7
+    return (best if ok else None), info
+
+
+def find_fundamental(m1, m2, thr=0.1, conf=0.99, solver=svd_solver, mut=frozenset(), trace=None):
+    """cv::findFundamentalMat(m1, m2, FM_RANSAC, thr, conf) on float32 pairs: 3x3 float64 or None.
+    n < 7: empty.  n == 7: the solver's first model.  8 <= n <= 14: LMedS, max(update(conf, 0.45,
+    1000), 3) iterations, the model with the strictly smallest median (element n // 2 of the sorted
+    float32 errors), kept when at least 7 errors are <= float32(sigma^2),
+    sigma = max(2.5 * 1.4826 (1 + 5 / (n - 7)) sqrt(median), 0.001).  n >= 15: RANSAC, 1000
+    iterations, every model of a subset scored in order against float32(thr^2), accepted on
+    good > max(max_good, 6), the iteration count updated on every acceptance.  A subset that cannot
+    be drawn ends the loop, with an empty result at iteration 0.
+
+    solver(s1, s2) -> (count, models).  `trace` (a dict) receives the branch, per iteration the
+    subset, the redraws, the model count, every model's good count or median and the iteration
+    count after each update; the winner (iteration, model), the final good count, niters, the
+    iterations run, the number of non-finite errors, the distances of the update quotients from a
+    half-integer, and `fragile`: the winner or the verdict changes when the errors are computed in
+    np.longdouble, so the set hangs on the last bit of a float32 error."""
+    m1 = np.ascontiguousarray(m1, np.float32).reshape(-1, 2)
+    m2 = np.ascontiguousarray(m2, np.float32).reshape(-1, 2)
+    mut = frozenset(mut)
+    assert mut <= set(MUTATIONS), mut
+    F, info = _fm_run(m1, m2, thr, conf, solver, mut, np.float64)
+    if trace is not None:
+        F2, info2 = _fm_run(m1, m2, thr, conf, solver, mut, np.longdouble)
+        info["fragile"] = info2["winner"] != info["winner"] or (F2 is None) != (F is None)
+        trace.update(info)
+    return F
+
+
+def moving_tail(prev, cur, pxy, nxy, state, edge=5, limit=2120.0, tm_cap=None, solver=svd_solver, mut=frozenset(),
+                trace=None):
+    """The tail of Frame::ProcessMovingObject on tracked pairs: a pair stays when its state is set,
+    its C-truncated coordinates lie in [edge, n - edge) on both sides and the 3x3 SAD around them
+    is at most `limit`; findFundamentalMat on the survivors in order; T_M takes the current point of
+    every survivor whose distance d to its epipolar line is not (d <= 1).
+    (T_M or None, state, F or None, number of survivors); with tm_cap, T_M is cut to it and the
+    full count goes to trace["n_tm"]."""
+    mut = frozenset(mut)
+    h, w = prev.shape
+    p = np.ascontiguousarray(pxy, np.float32).reshape(-1, 2)
+    q = np.ascontiguousarray(nxy, np.float32).reshape(-1, 2)
+    keep = np.asarray(state).reshape(-1) != 0
+    tp, tq = np.trunc(p).astype(np.int64), np.trunc(q).astype(np.int64)
+    over = 1 if "edge_off_by_one" in mut else 0
+    for t in (tp, tq):
+        keep = keep & (t[:, 0] >= edge) & (t[:, 0] < w - edge + over) & (t[:, 1] >= edge) & (t[:, 1] < h - edge + over)
+    o = np.arange(-1, 2)
+    win = lambda img, t: img.astype(np.int64)[t[:, 1, None, None] + o[None, :, None], t[:, 0, None, None] + o[None, None, :]]
+    sad = np.abs(win(prev, tp[keep]) - win(cur, tq[keep])).sum(axis=(1, 2))         # exact integers
+    keep[np.nonzero(keep)[0][sad > limit]] = False
+    m1, m2 = p[keep], q[keep]
+    F = find_fundamental(m1, m2, 0.1, 0.99, solver, mut, trace)
+    st = keep.astype(np.uint8)
+    if F is None:
+        return None, st, None, len(m1)
+    f = F.ravel()
+    px, py, qx, qy = (v.astype(np.float64) for v in (m1[:, 0], m1[:, 1], m2[:, 0], m2[:, 1]))
+    with np.errstate(all="ignore"):
+        A = f[0] * px + f[1] * py + f[2]
+        B = f[3] * px + f[4] * py + f[5]
+        Cc = f[6] * px + f[7] * py + f[8]
+        d = np.abs(A * qx + B * qy + Cc) / np.sqrt(A * A + B * B)
+        tm = m2[d < 1] if "d_lt_1" in mut else m2[~(d <= 1)]
+    if trace is not None:
+        trace["n_tm"] = len(tm)
+    return (tm if tm_cap is None else tm[:tm_cap]).copy(), st, F, len(m1)

@@ -3,6 +3,8 @@ calcOpticalFlowPyrLK, run7Point) against the independent numpy model of tests/fl
 bounds and their derivations are in flow_ref's docstrings; each test asserts the precondition its
 comparison rests on (separated decisions, or a capped share of ill-conditioned points), on the
 model alone."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -202,3 +204,194 @@ def test_seven_point(oracle_mod):
             counted += 1
             three += n == 3
     assert counted >= 100 and three >= 10 and counted - three >= 10, (counted, three)
+
+
+# ---------------------------------------------------------------- findFundamentalMat's loops
+import fm_sets as S                                      # noqa: E402
+
+_runs = {}
+
+
+def model_run(oracle_mod, name):
+    """(F, trace) of the model on a directed set, computed once."""
+    if name not in _runs:
+        tr = {}
+        F = R.find_fundamental(*S.get(name), solver=S.oracle_solver(oracle_mod), trace=tr)
+        _runs[name] = (F, tr)
+    return _runs[name]
+
+
+def same_F(a, b):
+    return (a is None) == (b is None) and (a is None or np.array_equal(a.view(np.uint64), b.view(np.uint64)))
+
+
+def same_tail(got, ref, tag):
+    (tm, st, F, nf), (rtm, rst, rF, rnf) = got, ref
+    assert np.array_equal(st, rst) and nf == rnf, (tag, nf, rnf)
+    assert same_F(F, rF), (tag, F, rF)
+    assert (tm is None) == (rtm is None), tag
+    if tm is not None:
+        assert np.array_equal(tm.view(np.uint32), rtm.view(np.uint32)), (tag, len(tm), len(rtm))
+
+
+@pytest.mark.parametrize("name", list(S.SETS))
+def test_find_fundamental_model_equals_oracle(oracle_mod, name):
+    """The model's loops around the oracle's 7-point models against oc_find_fundamental: the same
+    emptiness and F bit for bit, on every directed set; and the two tails on a flat image pair."""
+    m1, m2 = S.get(name)
+    assert S.inside(m1).all() and S.inside(m2).all()
+    F, tr = model_run(oracle_mod, name)
+    assert same_F(F, oracle_mod.find_fundamental(m1, m2)), (name, tr["winner"], tr["fragile"])
+    prev, cur = S.flat_pair()
+    st = np.ones(len(m1), np.uint8)
+    got = R.moving_tail(prev, cur, m1, m2, st, solver=S.oracle_solver(oracle_mod))
+    same_tail(got, oracle_mod.moving_tail(prev, cur, m1, m2, st), name)
+    assert same_F(got[2], F) and got[3] == len(m1)
+
+
+@pytest.mark.parametrize("name", list(S.thin_cases()))
+def test_moving_tail_model_equals_oracle_thinned(oracle_mod, name):
+    """Pairs removed by state, by the SAD check and by the edge rule: model against oracle, each
+    thinned call against the call on its survivors alone, and T_M capacities of 0 and |T_M| - 1."""
+    prev, cur, p, q, s = S.thin_cases()[name]
+    solver = S.oracle_solver(oracle_mod)
+    tr = {}
+    got = R.moving_tail(prev, cur, p, q, s, solver=solver, trace=tr)
+    ref = oracle_mod.moving_tail(prev, cur, p, q, s)
+    same_tail(got, ref, name)
+    k = ref[1] != 0
+    assert ref[3] == k.sum() and (name != "sad_block" or 15 <= k.sum() < len(p) - 15)
+    alone = oracle_mod.moving_tail(prev, cur, p[k], q[k], np.ones(k.sum(), np.uint8))
+    assert same_F(ref[2], alone[2]) and alone[1].all()
+    if ref[0] is not None:
+        assert np.array_equal(ref[0], alone[0])
+        nt = len(ref[0])
+        assert tr["n_tm"] == nt and (name in ("keep7", "keep8") or nt >= 2)
+        for cap in (0, nt - 1):
+            if cap < 0:
+                continue
+            capped = R.moving_tail(prev, cur, p, q, s, tm_cap=cap, solver=solver)
+            ont, otm = S.oracle_tail_capped(oracle_mod, prev, cur, p, q, s, cap)
+            assert ont == nt and len(capped[0]) == cap and np.array_equal(capped[0], otm[:cap])
+            assert (otm[cap:] == -7.0).all()
+
+
+def test_directed_sets_reach_their_branches(oracle_mod):
+    """What every directed set is for, on the model's trace alone."""
+    T = {n: model_run(oracle_mod, n) for n in S.SETS}
+    its = lambda n: T[n][1]["iterations"]
+    retries = lambda n: sum(i["retries"] for i in its(n))
+    counts = lambda n: [i["nmodels"] for i in its(n)]
+    updates = lambda n: [u for i in its(n) for u in i["niters"]]
+    for n in ("none", "six"):
+        assert T[n][0] is None and T[n][1]["branch"] == "few"
+    assert counts("seven_one_root") == [1] and counts("seven_three_roots") == [3] and counts("seven_repeated") == [0]
+    assert T["seven_one_root"][0] is not None and T["seven_three_roots"][0] is not None and T["seven_repeated"][0] is None
+    # LMedS: 300 iterations; the final count is exactly 7 on four sets and 8 and 14 on others
+    for n in ("clean8", "clean9", "clean14", "noisy8", "noisy9", "noisy12", "noisy14", "random12", "line7_of_12"):
+        assert T[n][1]["branch"] == "lmeds" and T[n][1]["ran"] == 300 and T[n][0] is not None, n
+    assert [T[n][1]["good"] for n in ("noisy8", "noisy9", "clean14", "noisy14")] == [7, 7, 14, 8]
+    # clean RANSAC: no outlier left after iteration 0, one iteration; two acceptances in it on five sets
+    for n in ("clean15", "clean16", "clean40", "clean129", "clean300", "clean1024", "shift45"):
+        tr = T[n][1]
+        assert tr["branch"] == "ransac" and tr["ran"] == 1 and tr["niters"] == 0 and tr["good"] == len(S.get(n)[0]), n
+    assert [len(its(n)[0]["niters"]) for n in ("clean15", "clean16", "clean40", "clean129", "clean300", "clean1024")] == \
+        [2, 2, 1, 2, 2, 2]
+    assert T["shift45"][1]["winner"] == (0, 0) and updates("shift45") == [0]     # the first model, accepted once
+    # stops inside a chunk of 32 whose draws were made, at its end, and one iteration into the next
+    assert (T["noisy15"][1]["ran"], T["noisy16"][1]["ran"]) == (162, 121)
+    assert T["chunk_boundary"][1]["ran"] == 32 and T["chunk_plus_one"][1]["ran"] == 65
+    assert T["chunk_plus_one"][1]["niters"] == 54          # lowered below the iterations already run
+    for n in ("noisy40", "noisy129", "noisy300", "noisy1024"):
+        assert T[n][1]["ran"] == 1000 and 5 <= len(updates(n)) <= 11 and T[n][0] is not None, n
+    # subsets that cannot be drawn: the iteration-0 exit, also on a set that has a drawable subset
+    for n, att in (("collinear20", 10000), ("five_points20", 10000), ("collinear12", 1000), ("rare_subset14", 1000)):
+        assert T[n][0] is None and T[n][1]["ran"] == 1 and retries(n) == att and T[n][1]["not_found"], n
+    late = T["rare_subset14_late"][1]                       # not found at iteration 58: the loop stops and keeps its model
+    assert late["not_found"] and late["ran"] == 59 and its("rare_subset14_late")[58]["subset"] is None
+    assert T["rare_subset14_late"][0] is not None and late["winner"][0] < 58
+    # redraws between good draws
+    assert retries("line14_of_24") > 1000 and T["line14_of_24"][1]["ran"] == 1000 and retries("line7_of_12") > 300
+    assert max(i["retries"] for i in its("line14_of_24")) < 100
+    # the solver's 0 and -1: skipped hypotheses, then a model that fits every pair
+    assert counts("identity20") == [0, -1, 3] and T["identity20"][1]["niters"] == 0
+    for n in ("random30", "random12"):
+        assert T[n][0] is not None and T[n][1]["good"] in (7, 8, 9), n
+    assert len(updates("random30")) >= 3
+
+
+def test_directed_sets_are_not_all_fragile(oracle_mod):
+    """Every branch has a set whose winner does not hang on the last bit of an error, and no
+    iteration-count update lies within 1e-6 of a tie (log from libm against the oracle's fdlibm)."""
+    solid = {}
+    for n in S.SETS:
+        tr = model_run(oracle_mod, n)[1]
+        assert all(h >= 1e-6 for h in tr["halves"]), (n, min(tr["halves"]))
+        assert tr["nonfinite"] == 0, n
+        if not tr["fragile"]:
+            solid.setdefault(tr["branch"], []).append(n)
+    assert {"few", "seven", "lmeds", "ransac"} <= set(solid), solid
+    for group in (("noisy8", "noisy14", "clean14"), ("noisy15", "noisy16"), ("noisy40", "noisy1024"),
+                  ("chunk_boundary", "chunk_plus_one"), ("line14_of_24", "identity20", "rare_subset14")):
+        assert any(n in solid["lmeds"] + solid["ransac"] for n in group), group
+
+
+def test_update_iters_rule(oracle_mod):
+    """RANSACUpdateNumIters: the model (math.log, pow) against the oracle (fdlibm log, a product)
+    for every inlier count of seven set sizes and three running maxima."""
+    lib = oracle_mod.lib()
+    total = skipped = 0
+    for n in (15, 16, 40, 129, 300, 1000, 1024):
+        for good in range(7, n + 1):
+            for mx in (1000, 300, 37):
+                halves = []
+                want = R.update_iters(0.99, (n - good) / n, mx, halves)
+                total += 1
+                if halves and halves[0] < 1e-6:
+                    skipped += 1
+                    continue
+                got = lib.oc_ransac_update_iters(C.c_double(0.99), C.c_double((n - good) / n), mx)
+                assert got == want, (n, good, mx, got, want)
+    assert skipped < 0.01 * total, (skipped, total)
+    assert R.update_iters(0.99, 0.45, 1000) == 300 and R.update_iters(0.99, 0.0, 1000) == 0
+
+
+# mutation -> the directed case that notices it: (set, arguments of find_fundamental) or a tail case
+MUTATION_CASES = {
+    "accept_gt_max_good": ("random30", dict(thr=1e-14)),    # no model scores 7 at that threshold; some score 1..6
+    "retry_not_counted": ("rare_subset14", {}),
+    "collinear_all_triples": ("line14_of_24", {}),
+    "collinear_first_six": ("line14_of_24", {}),
+    "median_low": ("noisy14", {}),
+    "no_min_three": ("noisy9", dict(conf=0.01)),            # update(0.01, 0.45, 1000) = 1
+    "good_gt_7": ("noisy8", {}),
+    "d_lt_1": ("tail", "keep129"),
+    "edge_off_by_one": ("tail", "edges"),
+}
+
+
+@pytest.mark.parametrize("mut", R.MUTATIONS)
+def test_every_mutation_is_noticed(oracle_mod, mut):
+    """Each wrong reading of OpenCV changes F, its emptiness, T_M or the state on a named directed
+    case, on which the unmutated model equals the oracle."""
+    solver = S.oracle_solver(oracle_mod)
+    name, arg = MUTATION_CASES[mut]
+    if name == "tail":
+        prev, cur, p, q, s = S.thin_cases()[arg]
+        ref = R.moving_tail(prev, cur, p, q, s, solver=solver)
+        same_tail(ref, oracle_mod.moving_tail(prev, cur, p, q, s), arg)
+        bad = R.moving_tail(prev, cur, p, q, s, solver=solver, mut={mut})
+        assert not (np.array_equal(ref[1], bad[1]) and same_F(ref[2], bad[2]) and np.array_equal(ref[0], bad[0]))
+        return
+    m1, m2 = S.get(name)
+    ref = R.find_fundamental(m1, m2, solver=solver, **arg)
+    assert same_F(ref, oracle_mod.find_fundamental(m1, m2, **arg)), name
+    assert not same_F(ref, R.find_fundamental(m1, m2, solver=solver, mut={mut}, **arg)), (mut, name)
+
+
+def test_find_fundamental_with_the_svd_solver():
+    """The default solver (the module's SVD 7-point models): a clean scene's F has every pair on
+    its epipolar line."""
+    m1, m2 = S.get("clean40")
+    F = R.find_fundamental(m1, m2)
+    assert F is not None and R.epipolar_residuals(F, m1, m2)[0].max() < 1e-6
