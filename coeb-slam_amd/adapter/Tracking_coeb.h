@@ -79,6 +79,23 @@
  *
  * The vocabulary's context has ORB-SLAM2's pyramid (8 levels, 1.2): its mvInvLevelSigma2 weigh the
  * edges, so a frame with another pyramid is refused.
+ *
+ * Tracking::Relocalization (src/Tracking.cc:1417-1580) keeps its front half (ComputeBoW,
+ * DetectRelocalizationCandidates, the SearchByBoW loop and the PnP solvers: KeyFrameDatabase_coeb.h,
+ * ORBmatcher_coeb.h and the integrator's own solver) and its while loop (:1477-1568) becomes
+ *
+ *     bool bMatch = coeb::Relocalization(mCurrentFrame, vpCandidateKFs, vpPnPsolvers, vvpMapPointMatches,
+ *                                        vbDiscarded, nCandidates);
+ *
+ * one library call with one synchronisation per round of the loop (coeb_reloc_refine) instead of up to
+ * five per candidate.  Per round, in the reference's order: every candidate that is not discarded runs
+ * pSolver->iterate(5, bNoMore, vbInliers, nInliers) and bNoMore discards it (:1490-1497); the
+ * candidates that returned a pose are snapshot (the KeyFrame's GetMapPointMatches(): valid = pMP &&
+ * !isBad(), GetWorldPos(), GetDescriptor(), mfMaxDistance / mfMinDistance, mvKeysUn[i].angle; the
+ * KeyFrame index of every vvpMapPointMatches[i][j]) and refined side by side; the first with nGood >= 50
+ * is the one the reference's loop breaks on, and its mvpMapPoints, mvbOutlier (where an optimisation
+ * saw a point) and pose go into the frame.  With no such candidate the frame gets the state of the
+ * last one, as the reference's sequential loop leaves it, and the next round runs.
  */
 #ifndef COEB_ADAPTER_TRACKING_H
 #define COEB_ADAPTER_TRACKING_H
@@ -88,6 +105,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <type_traits>
+#include <unordered_map>
 #include <utility>
 #include <vector>
 
@@ -391,6 +409,147 @@ inline bool TrackWithMotionModel(FrameT& F, FrameT& LastFrame, const MatT& mVelo
         return nmatches > 20;
     }
     return nmatchesMap >= 10;
+}
+
+// One PnP hypothesis as Tracking::Relocalization holds it behind vpPnPsolvers[i]->iterate (:1490)
+template <class KeyFrameT, class MapPointT>
+struct RelocHypothesis {
+    KeyFrameT* pKF;                                         // vpCandidateKFs[i]
+    const std::vector<MapPointT*>* vpMapPointMatches;       // &vvpMapPointMatches[i]
+    std::vector<bool> vbInliers;
+    cv::Mat Tcw;
+};
+
+// Tracking.cc:1502-1565 for up to COEB_RELOC_MAX_HYP hypotheses of one round in one call.  Returns the
+// index of the first hypothesis with nGood >= 50 (the one the reference breaks on), or -1; the frame
+// gets that hypothesis' mvpMapPoints, mvbOutlier and pose, or with -1 those of the last one (what the
+// reference's loop leaves behind it).  pnGood (when given) receives every hypothesis' nGood.
+template <class FrameT, class KeyFrameT, class MapPointT>
+inline int RelocalizationRefine(FrameT& F, const std::vector<RelocHypothesis<KeyFrameT, MapPointT>>& hyps,
+                                bool bCheckOrientation = true, std::vector<int>* pnGood = nullptr, coeb_ctx* ctx = nullptr)
+{
+    const int H = (int)hyps.size(), N = F.N;
+    if (H < 1 || H > COEB_RELOC_MAX_HYP) throw std::runtime_error("coeb::RelocalizationRefine: 1..COEB_RELOC_MAX_HYP hypotheses");
+    if (!ctx) ctx = matcher_ctx(F.mnScaleLevels, F.mfScaleFactor);
+    struct Snap {
+        std::vector<MapPointT*> pts;                        // by KeyFrame index; past vpMPs: matched points the KeyFrame lost
+        std::vector<uint8_t> valid, desc, inl;
+        std::vector<float> xw, maxd, mind, ang;
+        std::vector<int32_t> match;
+    };
+    std::vector<Snap> snap((size_t)H);
+    std::vector<coeb_reloc_hypothesis> hy((size_t)H);
+    for (int h = 0; h < H; ++h) {
+        Snap& s = snap[h];
+        KeyFrameT* pKF = hyps[h].pKF;
+        s.pts = pKF->GetMapPointMatches();
+        const int nkf = (int)s.pts.size();
+        std::unordered_map<MapPointT*, int> index;
+        for (int i = nkf - 1; i >= 0; --i)
+            if (s.pts[i]) index[s.pts[i]] = i;
+        s.match.assign((size_t)N, -1);
+        s.inl.assign((size_t)N, 0);
+        const std::vector<MapPointT*>& vpM = *hyps[h].vpMapPointMatches;
+        for (int j = 0; j < N; ++j) {
+            MapPointT* pMP = j < (int)vpM.size() ? vpM[j] : static_cast<MapPointT*>(nullptr);
+            if (!pMP) continue;                             // an inlier always has a point (PnPsolver.cc keeps matched keypoints only)
+            auto it = index.find(pMP);
+            if (it == index.end()) {                        // no longer in the KeyFrame: an extra slot no search can reach
+                it = index.emplace(pMP, (int)s.pts.size()).first;
+                s.pts.push_back(pMP);
+            }
+            s.match[j] = it->second;
+            s.inl[j] = j < (int)hyps[h].vbInliers.size() && hyps[h].vbInliers[j];
+        }
+        const int nq = (int)s.pts.size();
+        s.valid.assign(nq, 0); s.desc.assign((size_t)nq * 32, 0);
+        s.xw.assign((size_t)nq * 3, 0.f); s.maxd.assign(nq, 0.f); s.mind.assign(nq, 0.f); s.ang.assign(nq, 0.f);
+        {
+            std::unique_lock<std::mutex> lock(MapPointT::mGlobalMutex);
+            for (int i = 0; i < nq; ++i) {
+                MapPointT* pMP = s.pts[i];
+                if (!pMP) continue;
+                cv::Mat P = pMP->GetWorldPos();             // read for bad points too: the optimiser does not ask (Optimizer.cc:276)
+                for (int k = 0; k < 3; ++k) s.xw[3 * (size_t)i + k] = P.at<float>(k);
+                s.valid[i] = i < nkf && !pMP->isBad();
+                if (!s.valid[i]) continue;
+                cv::Mat d = pMP->GetDescriptor();
+                std::memcpy(&s.desc[32 * (size_t)i], d.ptr<uint8_t>(0), 32);
+                s.maxd[i] = pMP->GetMaxDistance();
+                s.mind[i] = pMP->GetMinDistance();
+                s.ang[i] = pKF->mvKeysUn[i].angle;
+            }
+        }
+        hy[h].kf = coeb_keyframe_points{nq, s.valid.data(), s.xw.data(), s.desc.data(), s.maxd.data(), s.mind.data(), s.ang.data()};
+        hy[h].match = s.match.data();
+        hy[h].inlier = s.inl.data();
+        for (int r = 0; r < 4; ++r)
+            for (int k = 0; k < 4; ++k) hy[h].Tcw[4 * r + k] = hyps[h].Tcw.template at<float>(r, k);
+    }
+    cv::Mat curDesc = F.mDescriptors.isContinuous() ? F.mDescriptors : F.mDescriptors.clone();
+    coeb_curframe cur{N, reinterpret_cast<const coeb_keypoint*>(F.mvKeysUn.data()),
+                      curDesc.empty() ? nullptr : curDesc.ptr<uint8_t>(0), F.mvuRight.data()};
+    const coeb_camera cam = frame_camera(F);
+    std::vector<int32_t> match((size_t)H * N), ngood(H), nadd1(H), nadd2(H), stage(H);
+    std::vector<uint8_t> outl((size_t)H * N, 2);            // 2: no optimisation saw a point there
+    int first = -1;
+    const int rc = coeb_reloc_refine(ctx, &cam, &cur, hy.data(), H, 10.f, 100, 3.f, 64, bCheckOrientation ? 1 : 0, 10, 30, 50,
+                                     match.data(), outl.data(), ngood.data(), nadd1.data(), nadd2.data(), stage.data(), &first);
+    if (rc != COEB_OK) throw std::runtime_error(coeb_last_error(ctx));
+    if (pnGood) pnGood->assign(ngood.begin(), ngood.end());
+    const int w = first >= 0 ? first : H - 1;
+    int nInliers = 0;
+    for (int j = 0; j < N; ++j) {
+        const int m = match[(size_t)w * N + j];
+        F.mvpMapPoints[j] = m >= 0 ? snap[w].pts[m] : static_cast<MapPointT*>(nullptr);
+        if (outl[(size_t)w * N + j] != 2) F.mvbOutlier[j] = outl[(size_t)w * N + j] != 0;
+        nInliers += snap[w].inl[j];
+    }
+    // Tcw.copyTo(mCurrentFrame.mTcw) (:1502), then PoseOptimization's SetPose with at least 3 edges (Optimizer.cc:361-362, 446-448)
+    F.mTcw = hyps[w].Tcw.clone();
+    if (nInliers >= 3) {
+        cv::Mat Tcw(4, 4, CV_32F);
+        for (int r = 0; r < 4; ++r)
+            for (int k = 0; k < 4; ++k) Tcw.at<float>(r, k) = hy[w].Tcw[4 * r + k];
+        F.SetPose(Tcw);
+    }
+    return first;
+}
+
+// The while loop of Tracking::Relocalization (:1477-1568) over any solver type with the reference's
+// `cv::Mat iterate(int nIterations, bool& bNoMore, vector<bool>& vbInliers, int& nInliers)`.  A round
+// collects the hypotheses of every candidate that is not discarded, refines them in one call (several
+// when a round has more than COEB_RELOC_MAX_HYP) and stops at the first with nGood >= 50.  rand() is
+// consumed in the reference's order up to the winning candidate; the candidates behind it in the
+// winning round have iterated as well, which the reference's `break` spares them: their solvers are
+// not used again.  vbDiscarded and nCandidates are updated as the reference updates them.
+template <class FrameT, class KeyFrameT, class MapPointT, class Solver>
+inline bool Relocalization(FrameT& F, const std::vector<KeyFrameT*>& vpCandidateKFs, const std::vector<Solver*>& vpPnPsolvers,
+                           const std::vector<std::vector<MapPointT*>>& vvpMapPointMatches, std::vector<bool>& vbDiscarded,
+                           int& nCandidates, bool bCheckOrientation = true, coeb_ctx* ctx = nullptr)
+{
+    const int nKFs = (int)vpCandidateKFs.size();
+    while (nCandidates > 0) {
+        std::vector<RelocHypothesis<KeyFrameT, MapPointT>> round;
+        for (int i = 0; i < nKFs; ++i) {
+            if (vbDiscarded[i]) continue;
+            std::vector<bool> vbInliers;                    // Perform 5 Ransac Iterations (:1484-1490)
+            int nInliers = 0;
+            bool bNoMore = false;
+            cv::Mat Tcw = vpPnPsolvers[i]->iterate(5, bNoMore, vbInliers, nInliers);
+            if (bNoMore) {                                  // :1493-1497
+                vbDiscarded[i] = true;
+                nCandidates--;
+            }
+            if (!Tcw.empty()) round.push_back(RelocHypothesis<KeyFrameT, MapPointT>{vpCandidateKFs[i], &vvpMapPointMatches[i], vbInliers, Tcw.clone()});
+        }
+        for (size_t at = 0; at < round.size(); at += COEB_RELOC_MAX_HYP) {
+            const size_t end = std::min(round.size(), at + (size_t)COEB_RELOC_MAX_HYP);
+            const std::vector<RelocHypothesis<KeyFrameT, MapPointT>> part(round.begin() + at, round.begin() + end);
+            if (RelocalizationRefine(F, part, bCheckOrientation, static_cast<std::vector<int>*>(nullptr), ctx) >= 0) return true;   // :1561-1565
+        }
+    }
+    return false;
 }
 
 }  // namespace coeb

@@ -79,7 +79,7 @@ ABI_SYMBOLS = [
     "coeb_bow_vector", "coeb_kfdb_create", "coeb_kfdb_destroy", "coeb_kfdb_add", "coeb_kfdb_erase", "coeb_kfdb_clear",
     "coeb_kfdb_size", "coeb_kfdb_query", "coeb_match_bow_kfdb",
     "coeb_search_local_points", "coeb_track_local_map", "coeb_track_reference_keyframe",
-    "coeb_track_motion_model",
+    "coeb_track_motion_model", "coeb_reloc_refine",
 ]
 # COEB_ABI_VERSION of the include/coeb_front.h these argtypes are written against; lib() refuses
 # a library that reports another (tests/test_capi_symbols.py keeps the two equal)
@@ -146,6 +146,13 @@ class BowKeyFrameC(C.Structure):
 
 class RefKeyFrameC(C.Structure):
     _fields_ = [("bow", BowKeyFrameC), ("world_pos", C.c_void_p), ("observations", C.c_void_p)]
+
+
+class RelocHypothesisC(C.Structure):
+    _fields_ = [("kf", KeyFramePointsC), ("match", C.c_void_p), ("inlier", C.c_void_p), ("Tcw", C.c_float * 16)]
+
+
+RELOC_MAX_HYP = 16      # COEB_RELOC_MAX_HYP
 
 
 class VoPointsC(C.Structure):
@@ -238,6 +245,9 @@ def lib():
                                               C.POINTER(LastFrameC), C.POINTER(VoPointsC), C.c_void_p, C.c_void_p,
                                               C.c_float, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3 + \
             [C.POINTER(C.c_int)] * 4
+        L.coeb_reloc_refine.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(CurFrameC),
+                                        C.POINTER(RelocHypothesisC), C.c_int, C.c_float, C.c_int, C.c_float, C.c_int,
+                                        C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.POINTER(C.c_int)]
         L.coeb_match_keyframe.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(CurFrameC), C.c_void_p,
                                           C.POINTER(KeyFramePointsC), C.c_void_p, C.c_float, C.c_int, C.c_int,
                                           C.c_void_p, C.POINTER(C.c_int)]
@@ -612,6 +622,48 @@ class Context:
         return dict(match=match[:n], discarded=disc[:n], outlier=out[:n], Tcw=T.reshape(4, 4),
                     nmatches_search=ns.value, ninliers_pose=nin.value, nmatches=nm.value, nmatches_map=nmap.value,
                     created=None if created is None else created[:nl], created_pos=None if cpos is None else cpos[:nl])
+
+    def reloc_refine(self, camera, F, hypotheses, th1=10.0, orb_dist1=100, th2=3.0, orb_dist2=64,
+                     check_orientation=True, min_good=10, low_good=30, enough_good=50):
+        """Tracking::Relocalization behind PnPsolver::iterate (src/Tracking.cc:1502-1565) for the
+        hypotheses of one round in one call (coeb_reloc_refine).  F: the current Frame (its mTcw and
+        mvpMapPoints are not read or modified).  hypotheses: up to RELOC_MAX_HYP tuples (kf, match,
+        inlier, Tcw): the candidate's KeyFramePoints (valid = pMP && !isBad() only), the KeyFrame
+        index SearchByBoW gave each keypoint (i32[F.N], -1: none), vbInliers (u8[F.N]) and the PnP
+        pose.  Returns a dict over the H hypotheses: match (i32[H, F.N], the KeyFrame index
+        mvpMapPoints holds or -1), outlier (u8[H, F.N], mvbOutlier where the keypoint held a point
+        at the last optimisation that ran, else 0), Tcw (f32[H, 4, 4]), ngood, nadditional1,
+        nadditional2, stage (i32[H] each) and first_good (the lowest h with ngood >= enough_good,
+        or -1)."""
+        n, H = F.N, len(hypotheses)
+        keep, hy = [], (RelocHypothesisC * max(H, 1))()
+        for h, (kf, match, inlier, Tcw) in enumerate(hypotheses):
+            m = np.ascontiguousarray(match, np.int32)
+            inl = np.ascontiguousarray(inlier, np.uint8)
+            if len(m) != n or len(inl) != n:
+                raise ValueError("reloc_refine: match / inlier must have F.N entries")
+            keep.append((m, inl))
+            hy[h].kf = KeyFramePointsC(kf.N, *[C.c_void_p(a.ctypes.data) for a in (
+                kf.valid, kf.world_pos, kf.descriptor, kf.max_distance, kf.min_distance, kf.angle)])
+            hy[h].match, hy[h].inlier = m.ctypes.data, inl.ctypes.data
+            C.memmove(hy[h].Tcw, np.ascontiguousarray(Tcw, np.float32).ctypes.data, 64)
+        cf = CurFrameC(n, C.c_void_p(F.mvKeysUn.ctypes.data), C.c_void_p(F.mDescriptors.ctypes.data),
+                       C.c_void_p(F.mvuRight.ctypes.data))
+        match = np.full((max(H, 1), n), -1, np.int32)
+        out = np.zeros((max(H, 1), n), np.uint8)
+        cnt = [np.zeros(max(H, 1), np.int32) for _ in range(4)]
+        first = C.c_int(-1)
+        pad = lambda a: a if a.size else np.zeros(1, a.dtype)       # a valid address for an empty array
+        m_, o_ = pad(match), pad(out)
+        self.check(lib().coeb_reloc_refine(
+            self.h, C.byref(camera), C.byref(cf), hy, H, th1, int(orb_dist1), th2, int(orb_dist2),
+            int(bool(check_orientation)), int(min_good), int(low_good), int(enough_good), _p(m_), _p(o_),
+            *[_p(a) for a in cnt], C.byref(first)))
+        T = np.zeros((H, 4, 4), np.float32)
+        for h in range(H):
+            C.memmove(T[h].ctypes.data, hy[h].Tcw, 64)
+        return dict(match=match[:H], outlier=out[:H], Tcw=T, ngood=cnt[0][:H], nadditional1=cnt[1][:H],
+                    nadditional2=cnt[2][:H], stage=cnt[3][:H], first_good=first.value)
 
     def bow_batch_device(self, levelsup=4):
         """The transform over the last extracted batch; results: batch_bow_results()."""

@@ -1096,6 +1096,7 @@ int coeb_match_keyframe(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe
     if (n && (!cur->keys_un || !cur->descriptors)) return set_err(c, COEB_EINVAL, "coeb_match_keyframe: missing current-frame arrays");
     if (nq && (!kf->valid || !kf->world_pos || !kf->descriptor || !kf->max_distance || !kf->min_distance || !kf->angle))
         return set_err(c, COEB_EINVAL, "coeb_match_keyframe: missing keyframe arrays");
+    if (!match_kf_fits(n, nq)) return set_err(c, COEB_ERANGE, "coeb_match_keyframe: frame and keyframe exceed the LDS budget");
     (void)hipSetDevice(c->device);
     const int cs = std::max(n, 1), qs = std::max(nq, 1);
     int rc;
@@ -1566,6 +1567,160 @@ int coeb_track_motion_model(coeb_ctx* c, const coeb_camera* cam, const coeb_curf
     *ninliers_pose = hc[1];
     *nmatches = hc[2];
     *nmatches_map = hc[3];
+    return COEB_OK;
+}
+
+// One staged region on the device, as coeb_track_motion_model's: the inputs (the hypotheses' arrays in
+// rows of one stride per side, cs keypoints / ks KeyFrame points, both multiples of 16 so that every
+// row of every element size starts on Pack's 16-byte grid), then the results (counts, first_good and the
+// poses uploaded as their initial values; the held indices and the packed outlier flags written by the
+// kernels) copied back in one piece, then scratch.
+static_assert(COEB_RELOC_MAX_HYP <= 64, "one workgroup per hypothesis, stack arrays below");
+int coeb_reloc_refine(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe* cur, coeb_reloc_hypothesis* hyp, int nhyp,
+                      float th1, int orb_dist1, float th2, int orb_dist2, int check_orientation, int min_good,
+                      int low_good, int enough_good, int32_t* match_out, uint8_t* outlier_out, int32_t* ngood,
+                      int32_t* nadditional1, int32_t* nadditional2, int32_t* stage, int* first_good)
+{
+    const std::string w("coeb_reloc_refine");
+    if (!c || !cam || !cur || !hyp || !ngood || !nadditional1 || !nadditional2 || !stage || !first_good)
+        return set_err(c, COEB_EINVAL, w + ": invalid arguments");
+    if (nhyp < 1 || nhyp > COEB_RELOC_MAX_HYP) return set_err(c, COEB_EINVAL, w + ": nhyp outside 1..COEB_RELOC_MAX_HYP");
+    const int n = cur->n, H = nhyp;
+    if (n < 0) return set_err(c, COEB_EINVAL, w + ": negative frame size");
+    if (n > kCurMax) return set_err(c, COEB_EINVAL, w + ": more than 4095 current keypoints");
+    if (n && (!cur->keys_un || !cur->descriptors || !cur->u_right || !match_out))
+        return set_err(c, COEB_EINVAL, w + ": missing current-frame arrays");
+    int kmax = 0;
+    for (int h = 0; h < H; h++) {
+        const coeb_keyframe_points& kf = hyp[h].kf;
+        if (kf.n < 0) return set_err(c, COEB_EINVAL, w + ": negative keyframe size");
+        if (kf.n && (!kf.valid || !kf.world_pos || !kf.descriptor || !kf.max_distance || !kf.min_distance || !kf.angle))
+            return set_err(c, COEB_EINVAL, w + ": missing keyframe arrays");
+        if (n && (!hyp[h].match || !hyp[h].inlier)) return set_err(c, COEB_EINVAL, w + ": missing match / inlier arrays");
+        for (int i = 0; i < n; i++) {
+            const int m = hyp[h].match[i];
+            if (m < -1 || m >= kf.n) return set_err(c, COEB_EINVAL, w + ": match outside [-1, kf.n)");
+            if (hyp[h].inlier[i] && m < 0) return set_err(c, COEB_EINVAL, w + ": an inlier without a match");
+        }
+        kmax = std::max(kmax, kf.n);
+    }
+    // which keypoints take a point is decided on the device: k_pose indexes mvInvLevelSigma2[octave] of any of them
+    for (int i = 0; i < n; i++)
+        if (cur->keys_un[i].octave < 0 || cur->keys_un[i].octave >= c->tab.nlevels)
+            return set_err(c, COEB_EINVAL, w + ": keypoint octave outside the pyramid");
+    for (int h = 0; h < H; h++)
+        if (!match_kf_fits(n, hyp[h].kf.n)) return set_err(c, COEB_ERANGE, w + ": frame and keyframe exceed the LDS budget");
+    if (n == 0) {                                   // no edges, nGood = 0: every hypothesis stops at the first gate
+        for (int h = 0; h < H; h++) ngood[h] = nadditional1[h] = nadditional2[h] = stage[h] = 0;
+        *first_good = -1;
+        return COEB_OK;
+    }
+    (void)hipSetDevice(c->device);
+    const int cs = (n + 15) & ~15, ks = (std::max(kmax, 1) + 15) & ~15;
+    int rc;
+    uint8_t* dbase;
+    SingleFrameBufs& sf = c->sf;
+    if ((rc = ensure(c, sf.l_list, (size_t)H * ks * kCQ)) || (rc = ensure(c, c->ex.err, 4)) ||
+        (rc = ensure(c, sf.p_act, (size_t)H * cs)) || (rc = ensure(c, sf.p_edge, (size_t)H * cs)) ||
+        (rc = ensure(c, sf.p_chi, (size_t)H * cs)))
+        return rc;
+    hipStream_t s = main_stream(c);
+    Pack pk;
+    // H rows of `stride` elements, row h holding cnt(h) of them (the rest zero)
+    auto rows = [&](auto ptr_of, auto cnt_of, size_t stride, size_t elem) {
+        const size_t o = pk.total;
+        for (int h = 0; h < H; h++) {
+            const size_t nb = (size_t)cnt_of(h) * elem;
+            pk.add(nb ? ptr_of(h) : nullptr, nb);
+            pk.fill(0, stride * elem - ((nb + 15) & ~(size_t)15));
+        }
+        return o;
+    };
+    auto all_n = [&](int) { return n; };
+    auto kf_n = [&](int h) { return hyp[h].kf.n; };
+    int32_t kfn[COEB_RELOC_MAX_HYP], cnt0[4 * COEB_RELOC_MAX_HYP + 4] = {0};
+    float T0[16 * COEB_RELOC_MAX_HYP];
+    for (int h = 0; h < H; h++) {
+        kfn[h] = hyp[h].kf.n;
+        memcpy(T0 + 16 * h, hyp[h].Tcw, 64);
+    }
+    cnt0[4 * H] = H;                                // first_good: none
+    const size_t o_k = pk.add(cur->keys_un, (size_t)n * sizeof(coeb_keypoint)), o_d = pk.add(cur->descriptors, (size_t)n * 32);
+    const size_t o_ur = pk.add(cur->u_right, (size_t)n * 4), o_is = pk.add(c->tab.inv_sigma2, sizeof(float) * COEB_MAXL);
+    const size_t o_kn = pk.add(kfn, (size_t)H * 4);
+    const size_t o_mi = rows([&](int h) { return (const void*)hyp[h].match; }, all_n, cs, 4);
+    const size_t o_in = rows([&](int h) { return (const void*)hyp[h].inlier; }, all_n, cs, 1);
+    const size_t o_v = rows([&](int h) { return (const void*)hyp[h].kf.valid; }, kf_n, ks, 1);
+    const size_t o_x = rows([&](int h) { return (const void*)hyp[h].kf.world_pos; }, kf_n, ks, 12);
+    const size_t o_qd = rows([&](int h) { return (const void*)hyp[h].kf.descriptor; }, kf_n, ks, 32);
+    const size_t o_mx = rows([&](int h) { return (const void*)hyp[h].kf.max_distance; }, kf_n, ks, 4);
+    const size_t o_mn = rows([&](int h) { return (const void*)hyp[h].kf.min_distance; }, kf_n, ks, 4);
+    const size_t o_a = rows([&](int h) { return (const void*)hyp[h].kf.angle; }, kf_n, ks, 4);
+    // results with an initial value: {stage, ngood, nadditional1, nadditional2} per hypothesis, first_good, the poses
+    const size_t o_cnt = pk.add(cnt0, ((size_t)4 * H + 4) * 4), o_T = pk.add(T0, (size_t)H * 64);
+    // results the kernels write (not uploaded), then scratch
+    size_t at = pk.total;
+    auto take = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 15) & ~(size_t)15; return o; };
+    const size_t HC = (size_t)H * cs, HK = (size_t)H * ks;
+    const size_t o_held = take(HC * 4), o_oo = take(HC);
+    const size_t back_end = at;
+    const size_t o_has = take(HC), o_px = take(HC * 12), o_out = take(HC), o_ao = take(HC);
+    const size_t o_kh = take(HC * sizeof(coeb_keypoint)), o_uh = take(HC * 4);
+    const size_t o_f = take(HK), o_vs = take(HK), o_sm = take(HC * 4), o_snm = take((size_t)H * 4);
+    const size_t o_act = take((size_t)2 * H), o_pn = take((size_t)3 * H * 4), o_pr = take((size_t)3 * H * 4);
+    const size_t o_path = take((size_t)2 * H * 4);
+    const size_t o_err = at;
+    if ((rc = pinned(c, o_err + 16)) || (rc = ensure(c, c->ex.stage, at)) || (rc = stage_in(c, pk, &dbase, s))) return rc;
+    RrBufs r;
+    r.nhyp = H; r.cur_n = n; r.cs = cs; r.ks = ks;
+    r.min_good = min_good; r.low_good = low_good; r.enough_good = enough_good;
+    r.kps = dbase + o_k; r.ur = (const float*)(dbase + o_ur);
+    r.match_in = (const int*)(dbase + o_mi); r.inlier = dbase + o_in;
+    r.kf_n = (const int*)(dbase + o_kn); r.kf_valid = dbase + o_v; r.kf_xw = (const float*)(dbase + o_x);
+    r.held = (int*)(dbase + o_held); r.has = dbase + o_has; r.xw = (float*)(dbase + o_px); r.outl = dbase + o_out;
+    r.at_opt = dbase + o_ao; r.kps_h = dbase + o_kh; r.ur_h = (float*)(dbase + o_uh);
+    r.found = dbase + o_f; r.valid_s = dbase + o_vs; r.smatch = (const int*)(dbase + o_sm); r.snm = (const int*)(dbase + o_snm);
+    r.active = dbase + o_act; r.pose_n = (int*)(dbase + o_pn); r.pose_res = (const int*)(dbase + o_pr);
+    r.cnt = (int*)(dbase + o_cnt); r.first_good = r.cnt + 4 * H; r.outl_out = dbase + o_oo;
+    const MatchCam mc = make_cam(c, cam);
+    auto pose = [&](int k) {                        // the k-th PoseOptimization: F = nhyp, gated by pose_n[k][h] = 0
+        PoseBufs p;
+        p.n = r.pose_n + k * H; p.has_mp = r.has; p.xw = r.xw; p.kps = r.kps_h; p.ur = r.ur_h;
+        p.inv_sigma2 = (const float*)(dbase + o_is); p.Tcw = (float*)(dbase + o_T); p.outlier = r.outl;
+        p.result = (int*)(dbase + o_pr) + k * H; p.edges = sf.p_edge.p; p.active = sf.p_act.p; p.chi2 = sf.p_chi.p;
+        p.stride = cs; p.timing = nullptr;
+        return launch_pose(p, H, cam->fx, cam->fy, cam->cx, cam->cy, cam->bf, s, &c->hook);
+    };
+    auto search = [&](int k, float th, int orb_dist) {
+        KfBufs b;
+        b.cur_kps = dbase + o_k; b.cur_desc = dbase + o_d; b.cur_has = r.has; b.cur_n = n;
+        b.valid = r.valid_s; b.xw = r.kf_xw; b.desc = dbase + o_qd; b.maxd = (const float*)(dbase + o_mx);
+        b.mind = (const float*)(dbase + o_mn); b.angle = (const float*)(dbase + o_a); b.kf_n = kmax;
+        b.Tcw = (const float*)(dbase + o_T); b.match = (int*)(dbase + o_sm); b.nmatch = (int*)(dbase + o_snm);
+        b.lists = sf.l_list.p; b.err = c->ex.err.p; b.path = (int*)(dbase + o_path);
+        b.kf_n_arr = r.kf_n; b.active = r.active + k * H; b.cur_stride = cs; b.kf_stride = ks; b.npairs = H;
+        return launch_match_kf(mc, b, th, orb_dist, check_orientation ? 1 : 0, s, &c->hook);
+    };
+    if (launch_rr_enter(r, s, &c->hook) || pose(0) || launch_rr_after1(r, s, &c->hook) || search(0, th1, orb_dist1) ||
+        launch_rr_merge(r, 1, s, &c->hook) || pose(1) || launch_rr_after2(r, s, &c->hook) || search(1, th2, orb_dist2) ||
+        launch_rr_merge(r, 2, s, &c->hook) || pose(2) || launch_rr_tail(r, s, &c->hook))
+        return hip_err(c, hipGetLastError(), "coeb_reloc_refine launch");
+    HIP_TRY(c, hipMemcpyAsync(c->pin + o_cnt, dbase + o_cnt, back_end - o_cnt, hipMemcpyDeviceToHost, s));
+    if ((rc = err_word_async(c, c->pin + o_err))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if ((rc = err_word_seen(c, c->pin + o_err))) return rc;
+    const int32_t* hc = reinterpret_cast<const int32_t*>(c->pin + o_cnt);
+    for (int h = 0; h < H; h++) {
+        stage[h] = hc[4 * h]; ngood[h] = hc[4 * h + 1]; nadditional1[h] = hc[4 * h + 2]; nadditional2[h] = hc[4 * h + 3];
+        memcpy(hyp[h].Tcw, c->pin + o_T + (size_t)h * 64, 64);
+        memcpy(match_out + (size_t)h * n, c->pin + o_held + (size_t)h * cs * 4, (size_t)n * 4);
+        if (outlier_out) {                          // written where the keypoint held a point at the last optimisation run
+            const uint8_t* fl = c->pin + o_oo + (size_t)h * cs;
+            for (int i = 0; i < n; i++)
+                if (fl[i] != 2) outlier_out[(size_t)h * n + i] = fl[i];
+        }
+    }
+    *first_good = hc[4 * H] < H ? hc[4 * H] : -1;
     return COEB_OK;
 }
 

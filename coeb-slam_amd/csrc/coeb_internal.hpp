@@ -380,9 +380,52 @@ struct KfBufs {
     const float* Tcw;   // device, 16 floats row-major
     int* match; int* nmatch; uint32_t* lists; int* err;
     int* path;          // as LocalBufs::path
+    // batch form (coeb_reloc_refine): npairs workgroups over ONE current frame (cur_kps, cur_desc, cur_n
+    // shared).  Pair p reads cur_has + p*cur_stride, the KeyFrame arrays + p*kf_stride (xw * 3, desc * 32;
+    // kf_n_arr[p] points; kf_n = the largest, read by the launcher only), Tcw + 16p, lists +
+    // p*kf_stride*kCQ, and writes match + p*cur_stride, nmatch[p], path[2p..]; active[p] == 0 skips the
+    // pair (nmatch[p] = 0, no assignment).  kf_n_arr == null: the single search above.
+    const int* kf_n_arr = nullptr; const uint8_t* active = nullptr;
+    int cur_stride = 0, kf_stride = 0;
+    int npairs = 1;     // read by the launcher only
 };
 int launch_match_kf(const MatchCam& cam, const KfBufs& b, float th, int orb_dist, int check_ori, hipStream_t s,
                     ProfileHook* prof);
+// launch_match_kf's LDS-budget verdict for cur_n keypoints and kf_n KeyFrame points, before anything is enqueued
+bool match_kf_fits(int cur_n, int kf_n);
+
+// Tracking::Relocalization's refinement of nhyp PnP hypotheses (src/Tracking.cc:1502-1565) on one host
+// frame (coeb_track.hip), every array in device memory, workgroup h of every launch = hypothesis h:
+// k_rr_enter -> k_pose -> k_rr_after1 -> k_match_kf -> k_rr_merge -> k_pose -> k_rr_after2 -> k_match_kf
+// -> k_rr_merge -> k_pose -> k_rr_tail, no host step between.  [H][cs] arrays have row stride cs (the
+// current frame), [H][ks] arrays row stride ks (the KeyFrames); a gated optimisation has pose_n = 0,
+// a gated search active = 0.
+struct RrBufs {
+    int nhyp, cur_n, cs, ks;
+    int min_good, low_good, enough_good;
+    // inputs: the shared current frame, per hypothesis vvpMapPointMatches / vbInliers and the KeyFrame
+    const void* kps; const float* ur;                                   // [cur_n]
+    const int* match_in; const uint8_t* inlier;                         // [H][cs]
+    const int* kf_n; const uint8_t* kf_valid; const float* kf_xw;       // [H], [H][ks], [H][ks][3]
+    // mCurrentFrame per hypothesis: mvpMapPoints as KeyFrame indices (-1: NULL), what k_pose and the
+    // search read of it, mvbOutlier, and k_pose's own copies of the keypoints
+    int* held; uint8_t* has; float* xw; uint8_t* outl;                  // [H][cs]
+    uint8_t* at_opt;                                                    // [H][cs] held a point at the last optimisation run
+    void* kps_h; float* ur_h;                                           // [H][cs]
+    // sAlreadyFound over KeyFrame indices, the `valid` of the next search, the search's result
+    uint8_t* found; uint8_t* valid_s;                                   // [H][ks]
+    const int* smatch; const int* snm;                                  // [H][cs], [H]
+    uint8_t* active;                                                    // [2][H] search 1, search 2
+    int* pose_n; const int* pose_res;                                   // [3][H] each
+    // results: {stage, ngood, nadditional1, nadditional2} per hypothesis, first_good (nhyp: none; zero /
+    // nhyp on entry), the packed mvbOutlier (2: not written)
+    int* cnt; int* first_good; uint8_t* outl_out;                       // [H][4], [1], [H][cs]
+};
+int launch_rr_enter(const RrBufs& r, hipStream_t s, ProfileHook* prof);
+int launch_rr_after1(const RrBufs& r, hipStream_t s, ProfileHook* prof);
+int launch_rr_merge(const RrBufs& r, int which, hipStream_t s, ProfileHook* prof);   // which = 1, 2: the search merged
+int launch_rr_after2(const RrBufs& r, hipStream_t s, ProfileHook* prof);
+int launch_rr_tail(const RrBufs& r, hipStream_t s, ProfileHook* prof);
 
 // frame preparation for batch matching: u_right/depth per keypoint + LastFrame map snapshot
 struct PrepBufs {

@@ -1291,14 +1291,33 @@ __device__ __forceinline__ QueryWin kf_window(const MatchCam& cam, const float* 
     return w;
 }
 
+// workgroup p's view of a batch launch: its own KeyFrame, entry holders, pose and outputs over the shared frame
+__device__ __forceinline__ KfBufs kf_at_pair(KfBufs b, int p)
+{
+    if (!b.kf_n_arr) return b;
+    const int64_t c = (int64_t)p * b.cur_stride, k = (int64_t)p * b.kf_stride;
+    b.kf_n = b.kf_n_arr[p];
+    b.cur_has += c;
+    b.valid += k; b.xw += 3 * k; b.desc += 32 * k; b.maxd += k; b.mind += k; b.angle += k;
+    b.Tcw += 16 * p;
+    b.match += c; b.nmatch += p; b.lists += k * kCQ; b.path += 2 * p;
+    return b;
+}
+
 template <bool kLds>
-__global__ __launch_bounds__(kMThreads) void k_match_kf(MatchCam cam, KfBufs b, float th, int orb_dist, int check_ori,
+__global__ __launch_bounds__(kMThreads) void k_match_kf(MatchCam cam, KfBufs b0, float th, int orb_dist, int check_ori,
                                                         int force_seq)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     __shared__ int s_hist[HISTO_LENGTH];
     __shared__ int s_flag[8];
     const int tid = threadIdx.x;
+    const KfBufs b = kf_at_pair(b0, blockIdx.x);
+    if (b0.active && !b0.active[blockIdx.x]) {                 // the hypothesis does not reach this search
+        for (int c = tid; c < b.cur_n; c += kMThreads) b.match[c] = -1;
+        if (tid == 0) *b.nmatch = 0;
+        return;
+    }
     const int n = b.cur_n, nq = b.kf_n;
     const MatchLds L = match_lds(smem, n, nq, kLds);
     const Kp* cur = reinterpret_cast<const Kp*>(b.cur_kps);
@@ -1503,12 +1522,17 @@ bool match_lastframe_fits(int cur_n, int last_n)
 int launch_match_kf(const MatchCam& cam, const KfBufs& b, float th, int orb_dist, int check_ori, hipStream_t s,
                     ProfileHook* prof)
 {
+    const int P = b.kf_n_arr ? b.npairs : 1;
+    if (P <= 0) return 0;
     const int force_seq = coeb_switch("COEB_MATCH_SEQUENTIAL") ? 1 : 0;
+    // a batch is sized by its largest KeyFrame (b.kf_n); every pair carves its own, smaller or equal, layout
     const LdsForm f = lds_form(std::max(b.cur_n, 1), std::max(b.kf_n, 1));
     if (!f.fits) return -2;
     prof_begin(prof, "k_match_kf", s);
-    if (f.staged) launch_lds(k_match_kf<true>, dim3(1), kMThreads, f.bytes, s, cam, b, th, orb_dist, check_ori, force_seq);
-    else launch_lds(k_match_kf<false>, dim3(1), kMThreads, f.bytes, s, cam, b, th, orb_dist, check_ori, force_seq);
+    if (f.staged) launch_lds(k_match_kf<true>, dim3(P), kMThreads, f.bytes, s, cam, b, th, orb_dist, check_ori, force_seq);
+    else launch_lds(k_match_kf<false>, dim3(P), kMThreads, f.bytes, s, cam, b, th, orb_dist, check_ori, force_seq);
     prof_end(prof, s);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+bool match_kf_fits(int cur_n, int kf_n) { return lds_form(std::max(cur_n, 1), std::max(kf_n, 1)).fits; }

@@ -24,6 +24,11 @@
 // with UpdateLastFrame's visual-odometry points, :878-930): k_vo_points in front of the last-frame
 // search (coeb_match.hip), then k_trk_pose_prep -> k_pose -> k_mm_tail.
 //
+// Tracking::Relocalization behind PnPsolver::iterate for a round of hypotheses on one host frame
+// (coeb_reloc_refine, src/Tracking.cc:1502-1565), workgroup h of every launch = hypothesis h: k_rr_enter ->
+// k_pose -> k_rr_after1 -> k_match_kf (batch form, coeb_match.hip) -> k_rr_merge -> k_pose -> k_rr_after2 ->
+// k_match_kf -> k_rr_merge -> k_pose -> k_rr_tail.
+//
 // Batch launch order: k_tlm_snapshot on the context stream (it copies every batch array the rest
 // reads, so the next batch's extraction may overwrite them), then on the pose stream after
 // the first k_pose: k_tlm_discard -> k_tlm_frustum -> k_match_local -> k_tlm_pose_prep -> k_pose.
@@ -391,7 +396,154 @@ __global__ __launch_bounds__(kT) void k_vo_points(VoBufs v)
     dst[1] = src[1];
 }
 
+// ---- Tracking::Relocalization after PnPsolver::iterate (Tracking.cc:1502-1565), workgroup h = hypothesis h ----
+// mvpMapPoints is `held`, the KeyFrame index a keypoint's MapPoint has in vpCandidateKFs[h] (-1: NULL);
+// sFound is a byte per KeyFrame index (a MapPoint occupies at most one index of a KeyFrame).  cnt[4h..]
+// = {stage, ngood, nadditional1, nadditional2}; every kernel that decides a branch writes the stage the
+// hypothesis ends in if nothing further runs.
+constexpr int kRrStage = 0, kRrGood = 1, kRrAdd = 2;
+
+__device__ __forceinline__ void rr_take(const RrBufs& r, int h, int64_t o, int m)
+{
+    const float* X = r.kf_xw + 3 * ((int64_t)h * r.ks + m);
+    r.held[o] = m;
+    r.has[o] = 1;
+    r.xw[3 * o + 0] = X[0];
+    r.xw[3 * o + 1] = X[1];
+    r.xw[3 * o + 2] = X[2];
+}
+
+// sFound = the KeyFrame indices of `held`, valid_s = kf_valid && !sFound
+__device__ __forceinline__ void rr_search_valid(const RrBufs& r, int h, bool rebuild)
+{
+    const int kn = r.kf_n[h];
+    uint8_t* found = r.found + (int64_t)h * r.ks;
+    if (rebuild) {                                              // sFound.clear(); insert every non-NULL mvpMapPoints (:1541-1544)
+        for (int q = threadIdx.x; q < kn; q += kT) found[q] = 0;
+        __syncthreads();
+        for (int i = threadIdx.x; i < r.cur_n; i += kT) {
+            const int m = r.held[(int64_t)h * r.cs + i];
+            if (m >= 0) found[m] = 1;
+        }
+        __syncthreads();
+    }
+    for (int q = threadIdx.x; q < kn; q += kT)
+        r.valid_s[(int64_t)h * r.ks + q] = r.kf_valid[(int64_t)h * r.ks + q] && !found[q];
+}
+
+// :1502-1517: mvpMapPoints[j] = vbInliers[j] ? vvpMapPointMatches[h][j] : NULL, sFound = the inliers' points
+__global__ __launch_bounds__(kT) void k_rr_enter(RrBufs r)
+{
+    const int h = blockIdx.x, n = r.cur_n, kn = r.kf_n[h];
+    uint8_t* found = r.found + (int64_t)h * r.ks;
+    for (int q = threadIdx.x; q < kn; q += kT) found[q] = 0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += kT) {
+        const int64_t o = (int64_t)h * r.cs + i;
+        const int m = r.inlier[o] ? r.match_in[o] : -1;
+        if (m >= 0) {
+            rr_take(r, h, o, m);
+            found[m] = 1;
+        } else {
+            r.held[o] = -1;
+            r.has[o] = 0;
+        }
+        r.at_opt[o] = m >= 0 ? 1 : 0;
+        r.outl[o] = 0;                                          // k_pose writes the flags of the edges it takes
+        reinterpret_cast<KpT*>(r.kps_h)[o] = reinterpret_cast<const KpT*>(r.kps)[i];   // k_pose indexes [h][cs]
+        r.ur_h[o] = r.ur[i];
+    }
+    if (threadIdx.x == 0) r.pose_n[h] = n;
+}
+
+// :1521-1529 behind the first PoseOptimization: `nGood < 10 -> continue`, the discard, `nGood < 50` -> search
+__global__ __launch_bounds__(kT) void k_rr_after1(RrBufs r)
+{
+    const int h = blockIdx.x, n = r.cur_n;
+    const int ng = r.pose_res[h];
+    const bool stop = ng < r.min_good, search = !stop && ng < r.enough_good;
+    if (threadIdx.x == 0) {
+        r.cnt[4 * h + kRrStage] = stop ? 0 : search ? 2 : 1;
+        r.active[h] = search ? 1 : 0;
+    }
+    if (stop) return;
+    for (int i = threadIdx.x; i < n; i += kT) {                 // outliers lose their point and stay in sFound
+        const int64_t o = (int64_t)h * r.cs + i;
+        if (r.has[o] && r.outl[o]) { r.held[o] = -1; r.has[o] = 0; }
+    }
+    if (search) rr_search_valid(r, h, false);
+}
+
+// Behind search `which`: its assignments enter mvpMapPoints (whatever the gate says), then
+// `nadditional + nGood >= 50` (:1533, :1548) lets the next PoseOptimization run
+__global__ __launch_bounds__(kT) void k_rr_merge(RrBufs r, int which)
+{
+    const int h = blockIdx.x, n = r.cur_n;
+    int* pose_n = r.pose_n + which * r.nhyp;
+    if (!r.active[(which - 1) * r.nhyp + h]) {
+        if (threadIdx.x == 0) pose_n[h] = 0;
+        return;
+    }
+    const int nadd = r.snm[h];
+    const bool go = nadd + r.pose_res[(which - 1) * r.nhyp + h] >= r.enough_good;
+    for (int i = threadIdx.x; i < n; i += kT) {
+        const int64_t o = (int64_t)h * r.cs + i;
+        const int m = r.smatch[o];
+        if (m >= 0) rr_take(r, h, o, m);
+        if (go) r.at_opt[o] = m >= 0 || r.has[o];
+    }
+    if (threadIdx.x == 0) {
+        pose_n[h] = go ? n : 0;
+        r.cnt[4 * h + kRrAdd + which - 1] = nadd;
+        r.cnt[4 * h + kRrStage] = which == 1 ? (go ? 3 : 2) : (go ? 5 : 4);
+    }
+}
+
+// :1539-1545 behind the second PoseOptimization (no discard in front of it): `nGood > 30 && nGood < 50` -> search
+__global__ __launch_bounds__(kT) void k_rr_after2(RrBufs r)
+{
+    const int h = blockIdx.x;
+    const bool ran = r.pose_n[r.nhyp + h] > 0;
+    const int ng = r.pose_res[r.nhyp + h];
+    const bool search = ran && ng > r.low_good && ng < r.enough_good;
+    if (threadIdx.x == 0) r.active[r.nhyp + h] = search ? 1 : 0;
+    if (search) rr_search_valid(r, h, true);
+}
+
+// The final discard (:1552-1554, stage 5 only), nGood of the last optimisation run, the packed
+// mvbOutlier and `nGood >= 50 -> break` (:1561) as the lowest such h
+__global__ __launch_bounds__(kT) void k_rr_tail(RrBufs r)
+{
+    const int h = blockIdx.x, n = r.cur_n;
+    const int stage = r.cnt[4 * h + kRrStage];
+    const int ng = r.pose_res[(stage >= 5 ? 2 : stage >= 3 ? 1 : 0) * r.nhyp + h];
+    for (int i = threadIdx.x; i < n; i += kT) {
+        const int64_t o = (int64_t)h * r.cs + i;
+        const uint8_t fl = r.outl[o];
+        if (stage == 5 && r.has[o] && fl) { r.held[o] = -1; r.has[o] = 0; }
+        r.outl_out[o] = r.at_opt[o] ? fl : 2;
+    }
+    if (threadIdx.x == 0) {
+        r.cnt[4 * h + kRrGood] = ng;
+        if (ng >= r.enough_good) atomicMin(r.first_good, h);
+    }
+}
+
 }  // namespace
+
+#define COEB_RR_LAUNCH(name, ...)                                                       \
+    do {                                                                                \
+        prof_begin(prof, #name, s);                                                     \
+        hipLaunchKernelGGL(name, dim3(r.nhyp), dim3(kT), 0, s, __VA_ARGS__);            \
+        prof_end(prof, s);                                                              \
+        return hipGetLastError() == hipSuccess ? 0 : -1;                                \
+    } while (0)
+int launch_rr_enter(const RrBufs& r, hipStream_t s, ProfileHook* prof) { COEB_RR_LAUNCH(k_rr_enter, r); }
+int launch_rr_after1(const RrBufs& r, hipStream_t s, ProfileHook* prof) { COEB_RR_LAUNCH(k_rr_after1, r); }
+int launch_rr_merge(const RrBufs& r, int which, hipStream_t s, ProfileHook* prof) { COEB_RR_LAUNCH(k_rr_merge, r, which); }
+int launch_rr_after2(const RrBufs& r, hipStream_t s, ProfileHook* prof) { COEB_RR_LAUNCH(k_rr_after2, r); }
+int launch_rr_tail(const RrBufs& r, hipStream_t s, ProfileHook* prof) { COEB_RR_LAUNCH(k_rr_tail, r); }
+#undef COEB_RR_LAUNCH
 
 int launch_mm_tail(const TrkBufs& t, hipStream_t s, ProfileHook* prof)
 {

@@ -82,7 +82,16 @@
  *                                      nmatches < 20 gate (:960), Optimizer::PoseOptimization (:964)
  *                                      and the outlier discard with nmatchesMap (:966-985) on one
  *                                      host frame, one call and one synchronisation
- *   coeb_bow_vector                 <- DBoW2 BowVector::addWeight / normalize(L1) as transform() fills
+ *   coeb_reloc_refine               <- Tracking::Relocalization behind PnPsolver::iterate
+ *                                      src/Tracking.cc:1502-1565, for the hypotheses of one round of
+ *                                      the while loop (:1477-1568) side by side: the inliers (:1508-1517),
+ *                                      PoseOptimization (:1519), the nGood < 10 gate and the discard
+ *                                      (:1521-1526), SearchByProjection(.., 10, 100) (:1531),
+ *                                      PoseOptimization (:1535), SearchByProjection(.., 3, 64) over the
+ *                                      rebuilt sFound (:1541-1545), PoseOptimization and the discard
+ *                                      (:1550-1554); one call and one synchronisation.  The PnP solver
+ *                                      stays the caller's
+ *   coeb_bow_vector                <- DBoW2 BowVector::addWeight / normalize(L1) as transform() fills
  *                                      mBowVec (host only; restated, parity against DBoW2 UNPINNED)
  *   coeb_kfdb_add / _erase / _clear <- KeyFrameDatabase::add / erase / clear
  *                                      src/KeyFrameDatabase.cc:40-73
@@ -581,6 +590,67 @@ int coeb_track_motion_model(coeb_ctx* ctx, const coeb_camera* cam, const coeb_cu
                             float Tcw[16], float th, int bmono, int check_orientation, int min_matches,
                             int32_t* match_out, int32_t* discarded_out, uint8_t* outlier_out,
                             int* nmatches_search, int* ninliers_pose, int* nmatches, int* nmatches_map);
+
+/* The most hypotheses one coeb_reloc_refine call refines. */
+#define COEB_RELOC_MAX_HYP 16
+
+/* One PnP hypothesis of Tracking::Relocalization: candidate KeyFrame i with the result of
+ * vpPnPsolvers[i]->iterate (Tracking.cc:1490). */
+typedef struct {
+    coeb_keyframe_points kf;   /* vpCandidateKFs[i]->GetMapPointMatches(); valid = pMP && !isBad()
+                                  only: sAlreadyFound is built by the call */
+    const int32_t* match;      /* cur->n: KeyFrame index of vvpMapPointMatches[i][j], -1: none */
+    const uint8_t* inlier;     /* cur->n: vbInliers[j] of PnPsolver::iterate */
+    float Tcw[16];             /* in: the PnP pose; out: mCurrentFrame.mTcw as the reference leaves it */
+} coeb_reloc_hypothesis;
+
+/* ---- Tracking::Relocalization behind PnPsolver::iterate (Tracking.cc:1502-1565), nhyp hypotheses ----
+ * The hypotheses of one round of the while loop (:1477-1568) do not depend on each other until the
+ * first reaches nGood >= 50, so they are refined side by side: one upload, one download and one
+ * synchronisation for all of them.  Each hypothesis h follows the reference literally:
+ *   - entry (:1508-1517): mvpMapPoints[j] = inlier[j] ? match[j] : NULL; sFound = the inliers' points.
+ *   - PoseOptimization (:1519) from Tcw, as coeb_pose_optimization: measurement cur->keys_un[j] with
+ *     cur->u_right[j] (< 0: monocular edge), information the context's mvInvLevelSigma2, position
+ *     kf.world_pos[match[j]], read whether or not kf.valid is set there.  With nGood < min_good (the
+ *     reference uses 10) the hypothesis stops and keeps its inlier points, as `continue` does (stage 0).
+ *   - the discard (:1524-1526): outliers lose their point and stay in sFound.  With nGood >=
+ *     enough_good (50) the hypothesis is done (stage 1).
+ *   - SearchByProjection(CurrentFrame, pKF, sFound, th1, orb_dist1) (:1531; 10, 100), as
+ *     coeb_match_keyframe with cur_has_mappoint = mvpMapPoints != NULL, valid = kf.valid && !sFound and
+ *     the optimised pose.  Its assignments enter mvpMapPoints even when nadditional1 + nGood <
+ *     enough_good stops the hypothesis (stage 2).
+ *   - PoseOptimization (:1535), with no discard in front of it: outlier-flagged keypoints keep their
+ *     point.  With nGood outside (low_good, enough_good) (30, 50) the hypothesis is done (stage 3).
+ *   - sFound rebuilt from every non-NULL mvpMapPoints, outlier-flagged ones included (:1541-1544), and
+ *     SearchByProjection(.., th2, orb_dist2) (:1545; 3, 64).  nGood + nadditional2 < enough_good stops
+ *     the hypothesis with the assignments made (stage 4).
+ *   - PoseOptimization and the discard (:1550-1554) (stage 5).
+ * check_orientation is matcher2's mbCheckOrientation (true in the reference).
+ * Outputs, per hypothesis h, exactly what the reference leaves in mCurrentFrame after it, the failing
+ * branches included: match_out[h * cur->n + j] = the KeyFrame index mvpMapPoints[j] holds or -1;
+ * outlier_out[h * cur->n + j] = mvbOutlier[j], written only where keypoint j held a point at the last
+ * optimisation that ran (elsewhere the reference's flag is whatever an earlier call left; the entry
+ * is not touched); hyp[h].Tcw = mTcw; stage[h] = the branch that ended it (above); ngood[h] = the last
+ * PoseOptimization return; nadditional1/2[h] = the searches' returns, 0 where a search did not run.
+ * *first_good = the lowest h with ngood[h] >= enough_good, or -1: the candidate the reference's loop
+ * breaks on (:1561-1565); the state of later hypotheses is what the reference would not have computed.
+ * Assumption: a MapPoint occupies at most one index of a KeyFrame, so sFound over KeyFrame indices
+ * equals the reference's set<MapPoint*>.
+ * COEB_EINVAL, with nothing written and no Tcw touched, for a missing pointer or array (outlier_out
+ * may be NULL), nhyp outside 1..COEB_RELOC_MAX_HYP, a negative size, cur->n > 4095, a match outside
+ * [-1, kf.n), an inlier with match < 0, or a keypoint octave outside the pyramid (every keypoint is
+ * checked: which take a point is decided on the device).  COEB_ERANGE, with nothing written, when any
+ * (cur->n, kf.n) pair exceeds the relocalisation matcher's LDS budget (as coeb_match_keyframe fails),
+ * decided before anything is enqueued.  cur->n == 0 is COEB_OK with zero counts and stage 0. */
+int coeb_reloc_refine(coeb_ctx* ctx, const coeb_camera* cam, const coeb_curframe* cur,
+                      coeb_reloc_hypothesis* hyp, int nhyp,
+                      float th1, int orb_dist1, float th2, int orb_dist2,   /* 10,100, 3,64 */
+                      int check_orientation,                               /* matcher2(0.9,true) */
+                      int min_good, int low_good, int enough_good,         /* 10, 30, 50 */
+                      int32_t* match_out,   /* nhyp x cur->n: KeyFrame index mvpMapPoints[j] holds, -1 */
+                      uint8_t* outlier_out, /* nhyp x cur->n, may be NULL */
+                      int32_t* ngood, int32_t* nadditional1, int32_t* nadditional2,
+                      int32_t* stage, int* first_good);
 
 /* ---- BowVector filling: addWeight in feature order, then normalize(L1) (host only, no context) ----
  * For every feature i < n with node[i] >= 0 (coeb_bow_transform's "weight > 0"), in order:
