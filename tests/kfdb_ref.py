@@ -30,9 +30,52 @@ def bow_vector(word, weight, node, normalize_l1=True):
     return bv
 
 
-def l1_score(v, w):
+MUTATIONS = ("min_common_f64", "common_ge", "sum_reversed", "sum_pairwise", "sum_blocks64", "carry_zero_block")
+
+
+def pairwise(t):
+    """A balanced tree over the terms: the halves summed first, then added."""
+    if len(t) <= 1:
+        return t[0] if t else 0.0
+    return pairwise(t[:len(t) // 2]) + pairwise(t[len(t) // 2:])
+
+
+def score_terms(v, w):
+    """-> per 64 words of w in ascending order (the device's unit of work) the list of the
+    common words' terms fabs(vi - wi) - fabs(vi) - fabs(wi)."""
+    keys = sorted(w)
+    return [[abs(v[k] - w[k]) - abs(v[k]) - abs(w[k]) for k in keys[b:b + 64] if k in v] for b in range(0, len(keys), 64)]
+
+
+def l1_score(v, w, mut=frozenset()):
     """L1Scoring::score(v, w): both maps in ascending word order; per common word
-    s += fabs(vi - wi) - fabs(vi) - fabs(wi), left to right; -s / 2.0."""
+    s += fabs(vi - wi) - fabs(vi) - fabs(wi), left to right; -s / 2.0.
+    mut: other orders of the same double sum (sum_reversed, sum_pairwise, sum_blocks64: per 64 of
+    w's words a partial sum, the partial sums added in order) and carry_zero_block (a block of 64
+    words without a common word adds the previous block's terms once more)."""
+    if mut & set(MUTATIONS[2:]):
+        blocks = score_terms(v, w)
+        flat = [t for b in blocks for t in b]
+        if "sum_reversed" in mut:
+            s = 0.0
+            for t in reversed(flat):
+                s += t
+        elif "sum_pairwise" in mut:
+            s = pairwise(flat)
+        elif "sum_blocks64" in mut:
+            s = 0.0
+            for b in blocks:
+                part = 0.0
+                for t in b:
+                    part += t
+                s += part
+        else:
+            s, last = 0.0, []
+            for b in blocks:
+                last = b or last
+                for t in last:
+                    s += t
+        return -s / 2.0
     s = 0.0
     for word in sorted(v):
         if word in w:
@@ -74,10 +117,17 @@ class Database:
         self.inverted = {}
 
 
-def detect_reloc(F_bow, db, frame_id, neighbours):
+def min_common_words(max_common, mut=frozenset()):
+    """int minCommonWords = maxCommonWords*0.8f: a float32 product, truncated."""
+    if "min_common_f64" in mut:
+        return int(float(max_common) * 0.8)
+    return int(np.float32(max_common) * np.float32(0.8))
+
+
+def detect_reloc(F_bow, db, frame_id, neighbours, mut=frozenset()):
     """DetectRelocalizationCandidates(F).  neighbours(kf) -> GetBestCovisibilityKeyFrames(10).
     -> dict(sharing: lKFsSharingWords, max_common, min_common, scored: [(float32 score, kf)] =
-    lScoreAndMatch, candidates: vpRelocCandidates)."""
+    lScoreAndMatch, candidates: vpRelocCandidates).  mut: MUTATIONS."""
     sharing = []
     for word in sorted(F_bow):
         for kf in db.inverted.get(word, []):
@@ -93,12 +143,12 @@ def detect_reloc(F_bow, db, frame_id, neighbours):
     for kf in sharing:
         if kf.reloc_words > max_common:
             max_common = kf.reloc_words
-    min_common = int(np.float32(max_common) * np.float32(0.8))      # int minCommonWords = maxCommonWords*0.8f
+    min_common = min_common_words(max_common, mut)
     out["max_common"], out["min_common"] = max_common, min_common
     scored = []
     for kf in sharing:
-        if kf.reloc_words > min_common:
-            si = np.float32(l1_score(F_bow, kf.bow))
+        if kf.reloc_words > min_common or ("common_ge" in mut and kf.reloc_words == min_common):
+            si = np.float32(l1_score(F_bow, kf.bow, mut))
             kf.reloc_score = si
             scored.append((si, kf))
     out["scored"] = scored

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import bow_ref as R
+from bow_cases import depths as _depths
 
 
 @functools.lru_cache(maxsize=None)
@@ -91,14 +92,6 @@ def test_transform_matches_reference(voc_ctx, name):
         depth = _depths(ref)
         assert any(depth[nd] == 2 and want["node"][i] == nd for i, nd in enumerate(leaves))
         assert (want["node"] < 0).sum() > 10 and min(len(ch) for ch in ref.children if ch) == 1
-
-
-def _depths(ref):
-    depth = {0: 0}
-    for nd in range(ref.nnodes):
-        for ch in ref.children[nd]:
-            depth[ch] = depth[nd] + 1
-    return depth
 
 
 @pytest.mark.gpu
