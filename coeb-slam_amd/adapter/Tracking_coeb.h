@@ -121,6 +121,21 @@ namespace coeb
 namespace detail
 {
 
+// a 4x4 CV_32F pose as the C-ABI's row-major float[16], and back
+template <class MatT>
+inline void pose_to_array(const MatT& M, float T[16])
+{
+    for (int r = 0; r < 4; ++r)
+        for (int k = 0; k < 4; ++k) T[4 * r + k] = M.template at<float>(r, k);
+}
+inline cv::Mat pose_to_mat(const float T[16])
+{
+    cv::Mat M(4, 4, CV_32F);
+    for (int r = 0; r < 4; ++r)
+        for (int k = 0; k < 4; ++k) M.at<float>(r, k) = T[4 * r + k];
+    return M;
+}
+
 // pose: TrackLocalMap (search + optimisation + inlier count), else SearchLocalPoints alone.
 // Returns mnMatchesInliers, or nToMatch for the search alone.
 template <class FrameT, class MapPointT>
@@ -175,8 +190,7 @@ inline int track_local_map(FrameT& F, const std::vector<MapPointT*>& vpLocalMapP
                       curDesc.empty() ? nullptr : curDesc.ptr<uint8_t>(0), F.mvuRight.data()};
     const coeb_camera cam = frame_camera(F);
     float T[16];
-    for (int r = 0; r < 4; ++r)
-        for (int k = 0; k < 4; ++k) T[4 * r + k] = F.mTcw.template at<float>(r, k);
+    pose_to_array(F.mTcw, T);
     std::vector<uint8_t> view(nq), outl((size_t)N);
     std::vector<float> px(nq), py(nq), pxr(nq), vcos(nq);
     std::vector<int32_t> lvl(nq), match((size_t)N);
@@ -208,12 +222,7 @@ inline int track_local_map(FrameT& F, const std::vector<MapPointT*>& vpLocalMapP
     int nInitial = 0;
     for (int i = 0; i < N; ++i)
         if (F.mvpMapPoints[i]) { F.mvbOutlier[i] = outl[i] != 0; nInitial++; }
-    if (nInitial >= 3) {
-        cv::Mat Tcw(4, 4, CV_32F);
-        for (int r = 0; r < 4; ++r)
-            for (int k = 0; k < 4; ++k) Tcw.at<float>(r, k) = T[4 * r + k];
-        F.SetPose(Tcw);
-    }
+    if (nInitial >= 3) F.SetPose(pose_to_mat(T));
     // Update MapPoints Statistics (:1010-1027); the count is the call's
     for (int i = 0; i < N; ++i) {
         if (!F.mvpMapPoints[i]) continue;
@@ -282,8 +291,7 @@ inline bool TrackReferenceKeyFrame(FrameT& F, KeyFrameT* pRefKF, const MatT& las
                       curDesc.empty() ? nullptr : curDesc.ptr<uint8_t>(0), F.mvuRight.data()};
     const coeb_camera cam = frame_camera(F);
     float T[16];
-    for (int r = 0; r < 4; ++r)
-        for (int k = 0; k < 4; ++k) T[4 * r + k] = lastTcw.template at<float>(r, k);
+    detail::pose_to_array(lastTcw, T);
     std::vector<int32_t> word((size_t)N), node((size_t)N), match((size_t)N), disc((size_t)N);
     std::vector<double> weight((size_t)N);
     int nmatchesBoW = 0, ninl = 0, nmatches = 0, nmatchesMap = 0;
@@ -304,10 +312,7 @@ inline bool TrackReferenceKeyFrame(FrameT& F, KeyFrameT* pRefKF, const MatT& las
     }
     if (pnMatchesMap) *pnMatchesMap = nmatchesMap;
     if (nmatchesBoW < 15) return false;             // :835
-    cv::Mat Tcw(4, 4, CV_32F);
-    for (int r = 0; r < 4; ++r)
-        for (int k = 0; k < 4; ++k) Tcw.at<float>(r, k) = T[4 * r + k];
-    F.SetPose(Tcw);
+    F.SetPose(detail::pose_to_mat(T));
     for (int i = 0; i < N; ++i) {
         F.mvpMapPoints[i] = match[i] >= 0 ? vpMapPointsKF[match[i]] : static_cast<MapPointT*>(nullptr);
         if (match[i] >= 0 || disc[i] >= 0) F.mvbOutlier[i] = false;
@@ -363,11 +368,8 @@ inline bool TrackWithMotionModel(FrameT& F, FrameT& LastFrame, const MatT& mVelo
     const coeb_camera cam = frame_camera(F);
     F.SetPose(mVelocity * LastFrame.mTcw);          // :941
     float T[16], Tl[16];
-    for (int r = 0; r < 4; ++r)
-        for (int k = 0; k < 4; ++k) {
-            T[4 * r + k] = F.mTcw.template at<float>(r, k);
-            Tl[4 * r + k] = LastFrame.mTcw.template at<float>(r, k);
-        }
+    detail::pose_to_array(F.mTcw, T);
+    detail::pose_to_array(LastFrame.mTcw, Tl);
     std::vector<int32_t> match((size_t)N), disc((size_t)N);
     int nmatchesSearch = 0, ninl = 0, nmatches = 0, nmatchesMap = 0;
     const int rc = coeb_track_motion_model(ctx, &cam, &cur, &last, bCreateVO ? &vo : nullptr, Tl, T, th, bMono ? 1 : 0,
@@ -393,10 +395,7 @@ inline bool TrackWithMotionModel(FrameT& F, FrameT& LastFrame, const MatT& mVelo
         F.mvpMapPoints[i] = match[i] >= 0 ? LastFrame.mvpMapPoints[match[i]] : static_cast<MapPointT*>(nullptr);
     if (pnMatchesMap) *pnMatchesMap = nmatchesMap;
     if (nmatchesSearch < 20) return false;          // :960
-    cv::Mat Tcw(4, 4, CV_32F);
-    for (int r = 0; r < 4; ++r)
-        for (int k = 0; k < 4; ++k) Tcw.at<float>(r, k) = T[4 * r + k];
-    F.SetPose(Tcw);
+    F.SetPose(detail::pose_to_mat(T));
     for (int i = 0; i < N; ++i) {
         if (match[i] >= 0 || disc[i] >= 0) F.mvbOutlier[i] = false;    // Optimizer.cc:302, Tracking.cc:977
         if (disc[i] < 0) continue;
@@ -483,8 +482,7 @@ inline int RelocalizationRefine(FrameT& F, const std::vector<RelocHypothesis<Key
         hy[h].kf = coeb_keyframe_points{nq, s.valid.data(), s.xw.data(), s.desc.data(), s.maxd.data(), s.mind.data(), s.ang.data()};
         hy[h].match = s.match.data();
         hy[h].inlier = s.inl.data();
-        for (int r = 0; r < 4; ++r)
-            for (int k = 0; k < 4; ++k) hy[h].Tcw[4 * r + k] = hyps[h].Tcw.template at<float>(r, k);
+        detail::pose_to_array(hyps[h].Tcw, hy[h].Tcw);
     }
     cv::Mat curDesc = F.mDescriptors.isContinuous() ? F.mDescriptors : F.mDescriptors.clone();
     coeb_curframe cur{N, reinterpret_cast<const coeb_keypoint*>(F.mvKeysUn.data()),
@@ -507,12 +505,7 @@ inline int RelocalizationRefine(FrameT& F, const std::vector<RelocHypothesis<Key
     }
     // Tcw.copyTo(mCurrentFrame.mTcw) (:1502), then PoseOptimization's SetPose with at least 3 edges (Optimizer.cc:361-362, 446-448)
     F.mTcw = hyps[w].Tcw.clone();
-    if (nInliers >= 3) {
-        cv::Mat Tcw(4, 4, CV_32F);
-        for (int r = 0; r < 4; ++r)
-            for (int k = 0; k < 4; ++k) Tcw.at<float>(r, k) = hy[w].Tcw[4 * r + k];
-        F.SetPose(Tcw);
-    }
+    if (nInliers >= 3) F.SetPose(detail::pose_to_mat(hy[w].Tcw));
     return first;
 }
 

@@ -193,6 +193,30 @@ int stage_in(coeb_ctx* c, const Pack& pk, uint8_t** dbase, hipStream_t s)
 }
 
 namespace {
+int err_word_async(coeb_ctx* c, uint8_t* dst);
+int err_word_seen(coeb_ctx* c, const uint8_t* src);
+}  // namespace
+
+int Staged::stage(coeb_ctx* c, hipStream_t s, bool with_err)
+{
+    int rc;
+    if ((rc = pinned(c, end() + (with_err ? 16 : 0))) || (rc = ensure(c, c->ex.stage, end())) || (rc = stage_in(c, pk, &dbase, s)))
+        return rc;
+    pin = c->pin;
+    return 0;
+}
+
+int Staged::finish(coeb_ctx* c, hipStream_t s, size_t from, size_t to, bool with_err)
+{
+    int rc;
+    HIP_TRY(c, hipMemcpyAsync(pin + from, dbase + from, to - from, hipMemcpyDeviceToHost, s));
+    if (with_err && (rc = err_word_async(c, pin + end()))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (with_err && (rc = err_word_seen(c, pin + end()))) return rc;
+    return 0;
+}
+
+namespace {
 
 int ensure_plan(coeb_ctx* c, int W, int H)
 {
@@ -566,6 +590,97 @@ int projection_finish(coeb_ctx* c, hipStream_t s, int n, int cs, int32_t* match_
     if (int rc = check_err_word(c)) return rc;
     match_copy_out(hout, n, cs, match_out, nmatches);
     return COEB_OK;
+}
+
+// ---- shared by the single-frame tracking calls ----
+// Each of them works in one staged region (Staged, coeb_ctx.hpp): the inputs are packed and uploaded
+// in one copy, the results that have an initial value (counts, the pose) last among them; the results
+// the kernels write follow, so that one copy brings every result back; scratch comes last.  A call
+// reads as what differs: which arrays go in, which kernels run, which results come back.
+
+// the current frame's mvKeysUn, mDescriptors and mvuRight, consecutive in the staged inputs
+struct CurOff { size_t k, d, ur; };
+CurOff pack_cur(Staged& st, const coeb_curframe* cur)
+{
+    const size_t n = (size_t)cur->n;
+    CurOff o;
+    o.k = st.add(cur->keys_un, n * sizeof(coeb_keypoint));
+    o.d = st.add(cur->descriptors, n * 32);
+    o.ur = st.add(cur->u_right, n * 4);
+    return o;
+}
+
+// every one of the n keypoints lies on a pyramid level (the kernels index the per-level tables with it)
+bool octaves_in_pyramid(const coeb_ctx* c, const coeb_keypoint* kps, int n)
+{
+    for (int i = 0; i < n; i++)
+        if (kps[i].octave < 0 || kps[i].octave >= c->tab.nlevels) return false;
+    return true;
+}
+
+// k_pose's scratch for `count` keypoints in all
+int pose_scratch(coeb_ctx* c, size_t count)
+{
+    SingleFrameBufs& sf = c->sf;
+    int rc;
+    if ((rc = ensure(c, sf.p_act, count)) || (rc = ensure(c, sf.p_edge, count)) || (rc = ensure(c, sf.p_chi, count))) return rc;
+    return 0;
+}
+
+// k_pose's arguments over device arrays, on pose_scratch()'s buffers
+PoseBufs pose_bufs(coeb_ctx* c, const int* n, const uint8_t* has, const float* xw, const void* kps, const float* ur,
+                   const float* inv_sigma2, float* Tcw, uint8_t* outlier, int* result, int stride)
+{
+    PoseBufs b;
+    b.n = n; b.has_mp = has; b.xw = xw; b.kps = kps; b.ur = ur; b.inv_sigma2 = inv_sigma2; b.Tcw = Tcw;
+    b.outlier = outlier; b.result = result; b.edges = c->sf.p_edge.p; b.active = c->sf.p_act.p; b.chi2 = c->sf.p_chi.p;
+    b.stride = stride; b.timing = nullptr;
+    return b;
+}
+
+// The current / last frame pair of SearchByProjection(CurrentFrame, LastFrame), as coeb_match_lastframe
+// and coeb_track_motion_model stage it: {n, nl}, the two poses, the current frame, the last frame's
+// six arrays.
+bool last_arrays_missing(const coeb_lastframe* last)
+{
+    return last->n && (!last->has_mappoint || !last->outlier || !last->world_pos || !last->mp_descriptor ||
+                       !last->mp_observations || !last->keys_un);
+}
+
+struct LastPair {
+    int32_t cnts[2];            // uploaded from here: lives as long as the Pack
+    size_t cn, T, Tl, lk, ld, h, o, xw, nb;
+    CurOff cur;
+};
+void pack_last_pair(Staged& st, const coeb_curframe* cur, const coeb_lastframe* last, const float* Tcw_cur,
+                    const float* Tcw_last, LastPair& p)
+{
+    const size_t nl = (size_t)last->n;
+    p.cnts[0] = cur->n; p.cnts[1] = last->n;
+    p.cn = st.add(p.cnts, 8); p.T = st.add(Tcw_cur, 64); p.Tl = st.add(Tcw_last, 64);
+    p.cur = pack_cur(st, cur);
+    p.lk = st.add(last->keys_un, nl * sizeof(coeb_keypoint));
+    p.ld = st.add(last->mp_descriptor, nl * 32); p.h = st.add(last->has_mappoint, nl);
+    p.o = st.add(last->outlier, nl); p.xw = st.add(last->world_pos, nl * 12);
+    p.nb = st.add(last->mp_observations, nl * 4);
+}
+
+// k_match's arguments for that pair, all but where match / nmatch live; m_scr, m_qn and the error
+// word have been ensured for ls LastFrame slots.  One pair: its candidate lists are built by 8
+// workgroups (k_match_lists), as for a small batch, instead of by the pair's one workgroup.
+MatchBufs last_pair_bufs(coeb_ctx* c, const Staged& st, const LastPair& p, int cs, int ls)
+{
+    MatchBufs mb;
+    memset(&mb, 0, sizeof(mb));
+    mb.cur_kps = st.dev<void>(p.cur.k); mb.cur_desc = st.dev<uint8_t>(p.cur.d); mb.cur_n = st.dev<int32_t>(p.cn);
+    mb.cur_ur = st.dev<float>(p.cur.ur); mb.cur_stride = cs;
+    mb.last_kps = st.dev<void>(p.lk); mb.last_desc = st.dev<uint8_t>(p.ld); mb.last_n = st.dev<int32_t>(p.cn) + 1;
+    mb.last_has = st.dev<uint8_t>(p.h); mb.last_out = st.dev<uint8_t>(p.o); mb.last_xw = st.dev<float>(p.xw);
+    mb.last_nobs = st.dev<int32_t>(p.nb); mb.last_stride = ls;
+    mb.Tcw_cur = st.dev<float>(p.T); mb.Tcw_last = st.dev<float>(p.Tl);
+    mb.scratch = c->sf.m_scr.p; mb.scratch_stride = ls * kCQ; mb.err = c->ex.err.p;
+    mb.qn = c->sf.m_qn.p; mb.qn_stride = ls + kMaxSplit;
+    return mb;
 }
 
 }  // namespace
@@ -972,9 +1087,7 @@ int coeb_match_lastframe(coeb_ctx* c, const coeb_camera* cam, const coeb_curfram
     const int n = cur->n, nl = last->n;
     if (n && (!cur->keys_un || !cur->descriptors || !cur->u_right))
         return set_err(c, COEB_EINVAL, "coeb_match_lastframe: missing current-frame arrays");
-    if (nl && (!last->has_mappoint || !last->outlier || !last->world_pos || !last->mp_descriptor ||
-               !last->mp_observations || !last->keys_un))
-        return set_err(c, COEB_EINVAL, "coeb_match_lastframe: missing LastFrame arrays");
+    if (last_arrays_missing(last)) return set_err(c, COEB_EINVAL, "coeb_match_lastframe: missing LastFrame arrays");
     // the kernel indexes mvScaleFactors[octave] of every LastFrame point with a MapPoint
     for (int i = 0; i < nl; i++)
         if (last->has_mappoint[i] && (last->keys_un[i].octave < 0 || last->keys_un[i].octave >= c->params.nlevels))
@@ -984,49 +1097,22 @@ int coeb_match_lastframe(coeb_ctx* c, const coeb_camera* cam, const coeb_curfram
     (void)hipSetDevice(c->device);
     const int cs = std::max(n, 1), ls = std::max(nl, 1);
     int rc;
-    uint8_t* dbase;
     SingleFrameBufs& sf = c->sf;
     if ((rc = ensure(c, sf.m_scr, (size_t)ls * kCQ)) || (rc = ensure(c, sf.m_qn, (size_t)ls + kMaxSplit)) ||
         (rc = ensure(c, c->ex.err, 4)))
         return rc;
     hipStream_t s = main_stream(c);
     // every input in one pinned staged copy (ten small pageable copies cost more than the kernel)
-    const int32_t cnts[2] = {n, nl};
-    Pack pk;
-    const size_t o_cn = pk.add(cnts, 8), o_T = pk.add(Tcw_cur, 64), o_Tl = pk.add(Tcw_last, 64);
-    const size_t o_ck = pk.add(cur->keys_un, (size_t)n * sizeof(coeb_keypoint)), o_cd = pk.add(cur->descriptors, (size_t)n * 32);
-    const size_t o_ur = pk.add(cur->u_right, (size_t)n * 4);
-    const size_t o_lk = pk.add(last->keys_un, (size_t)nl * sizeof(coeb_keypoint));
-    const size_t o_ld = pk.add(last->mp_descriptor, (size_t)nl * 32), o_h = pk.add(last->has_mappoint, (size_t)nl);
-    const size_t o_o = pk.add(last->outlier, (size_t)nl), o_xw = pk.add(last->world_pos, (size_t)nl * 12);
-    const size_t o_nb = pk.add(last->mp_observations, (size_t)nl * 4);
+    Staged st;
+    LastPair lp;
+    pack_last_pair(st, cur, last, Tcw_cur, Tcw_last, lp);
     // k_match writes match[cs] and nmatches straight behind the staged inputs (page-locked, no
-    // copy back)
-    const size_t o_res = (pk.total + 255) & ~(size_t)255;
+    // copy back): the region is the inputs alone, and nothing is copied back but the error word
+    const size_t o_res = (st.pk.total + 255) & ~(size_t)255;
     const size_t o_err = (o_res + ((size_t)cs + 1) * 4 + 15) & ~(size_t)15;
-    if ((rc = pinned(c, o_err + 16)) || (rc = stage_in(c, pk, &dbase, s))) return rc;
-    int32_t* dout = reinterpret_cast<int32_t*>(c->pin_dev + o_res);
-    MatchBufs mb;
-    memset(&mb, 0, sizeof(mb));
-    mb.cur_kps = reinterpret_cast<const coeb_keypoint*>(dbase + o_ck);
-    mb.cur_desc = dbase + o_cd;
-    mb.cur_n = reinterpret_cast<const int32_t*>(dbase + o_cn);
-    mb.cur_ur = reinterpret_cast<const float*>(dbase + o_ur);
-    mb.cur_stride = cs;
-    mb.last_kps = reinterpret_cast<const coeb_keypoint*>(dbase + o_lk);
-    mb.last_desc = dbase + o_ld;
-    mb.last_n = reinterpret_cast<const int32_t*>(dbase + o_cn) + 1;
-    mb.last_has = dbase + o_h;
-    mb.last_out = dbase + o_o;
-    mb.last_xw = reinterpret_cast<const float*>(dbase + o_xw);
-    mb.last_nobs = reinterpret_cast<const int32_t*>(dbase + o_nb);
-    mb.last_stride = ls;
-    mb.Tcw_cur = reinterpret_cast<const float*>(dbase + o_T);
-    mb.Tcw_last = reinterpret_cast<const float*>(dbase + o_Tl);
-    mb.match = dout; mb.nmatch = dout + cs; mb.scratch = sf.m_scr.p; mb.scratch_stride = ls * kCQ; mb.err = c->ex.err.p;
-    // one pair: its candidate lists are built by 8 workgroups (k_match_lists), as for a small
-    // batch, instead of by the pair's one workgroup
-    mb.qn = sf.m_qn.p; mb.qn_stride = mb.last_stride + kMaxSplit;
+    if ((rc = pinned(c, o_err + 16)) || (rc = stage_in(c, st.pk, &st.dbase, s))) return rc;
+    MatchBufs mb = last_pair_bufs(c, st, lp, cs, ls);
+    mb.match = reinterpret_cast<int32_t*>(c->pin_dev + o_res); mb.nmatch = mb.match + cs;
     if (launch_match(make_cam(c, cam), mb, 1, th, bmono, check_ori, 0, s, &c->hook))
         return hip_err(c, hipGetLastError(), "launch_match");
     if ((rc = err_word_async(c, c->pin + o_err))) return rc;
@@ -1057,26 +1143,24 @@ int coeb_match_localmap(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe
     (void)hipSetDevice(c->device);
     const int cs = std::max(n, 1), qs = std::max(nq, 1);
     int rc;
-    uint8_t* dbase;
     SingleFrameBufs& sf = c->sf;
     if ((rc = projection_bufs(c, cs, qs))) return rc;
     int32_t* dout = sf.l_out.p;
     hipStream_t s = main_stream(c);
-    Pack pk;
-    const size_t o_k = pk.add(cur->keys_un, (size_t)n * sizeof(coeb_keypoint)), o_d = pk.add(cur->descriptors, (size_t)n * 32);
-    const size_t o_ur =pk.add(cur->u_right, (size_t)n * 4);
-    const size_t o_co = cur_obs ? pk.add(cur_obs, (size_t)n * 4) : pk.fill(0xff, (size_t)n * 4);   // -1: all NULL
-    const size_t o_v = pk.add(mp->in_view, (size_t)nq), o_px = pk.add(mp->proj_x, (size_t)nq * 4);
-    const size_t o_py = pk.add(mp->proj_y, (size_t)nq * 4), o_pxr = pk.add(mp->proj_xr, (size_t)nq * 4);
-    const size_t o_l = pk.add(mp->level, (size_t)nq * 4), o_c = pk.add(mp->view_cos, (size_t)nq * 4);
-    const size_t o_qd = pk.add(mp->descriptor, (size_t)nq * 32), o_no = pk.add(mp->observations, (size_t)nq * 4);
-    if ((rc = stage_in(c, pk, &dbase, s))) return rc;
+    Staged st;
+    const CurOff o_c = pack_cur(st, cur);
+    const size_t o_co = cur_obs ? st.add(cur_obs, (size_t)n * 4) : st.fill(0xff, (size_t)n * 4);   // -1: all NULL
+    const size_t o_v = st.add(mp->in_view, (size_t)nq), o_px = st.add(mp->proj_x, (size_t)nq * 4);
+    const size_t o_py = st.add(mp->proj_y, (size_t)nq * 4), o_pxr = st.add(mp->proj_xr, (size_t)nq * 4);
+    const size_t o_l = st.add(mp->level, (size_t)nq * 4), o_vc = st.add(mp->view_cos, (size_t)nq * 4);
+    const size_t o_qd = st.add(mp->descriptor, (size_t)nq * 32), o_no = st.add(mp->observations, (size_t)nq * 4);
+    if ((rc = st.stage(c, s, false))) return rc;
     LocalBufs b;
-    b.cur_kps = dbase + o_k; b.cur_desc = dbase + o_d; b.cur_ur = (const float*)(dbase + o_ur);
-    b.cur_obs = (const int*)(dbase + o_co); b.cur_n = n;
-    b.in_view = dbase + o_v; b.proj_x = (const float*)(dbase + o_px); b.proj_y = (const float*)(dbase + o_py);
-    b.proj_xr = (const float*)(dbase + o_pxr); b.level = (const int*)(dbase + o_l); b.view_cos = (const float*)(dbase + o_c);
-    b.desc = dbase + o_qd; b.nobs = (const int*)(dbase + o_no); b.mp_n = nq;
+    b.cur_kps = st.dev<void>(o_c.k); b.cur_desc = st.dev<uint8_t>(o_c.d); b.cur_ur = st.dev<float>(o_c.ur);
+    b.cur_obs = st.dev<int>(o_co); b.cur_n = n;
+    b.in_view = st.dev<uint8_t>(o_v); b.proj_x = st.dev<float>(o_px); b.proj_y = st.dev<float>(o_py);
+    b.proj_xr = st.dev<float>(o_pxr); b.level = st.dev<int>(o_l); b.view_cos = st.dev<float>(o_vc);
+    b.desc = st.dev<uint8_t>(o_qd); b.nobs = st.dev<int>(o_no); b.mp_n = nq;
     b.match = dout; b.nmatch = dout + cs; b.lists = sf.l_list.p; b.err = c->ex.err.p; b.path = sf.l_path.p;
     rc = launch_match_local(make_cam(c, cam), b, th, nnratio, s, &c->hook);
     if (rc == -2) return set_err(c, COEB_ERANGE, "coeb_match_localmap: frame and local map exceed the LDS budget");
@@ -1100,24 +1184,23 @@ int coeb_match_keyframe(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe
     (void)hipSetDevice(c->device);
     const int cs = std::max(n, 1), qs = std::max(nq, 1);
     int rc;
-    uint8_t* dbase;
     SingleFrameBufs& sf = c->sf;
     if ((rc = projection_bufs(c, cs, qs))) return rc;
     int32_t* dout = sf.l_out.p;
     hipStream_t s = main_stream(c);
-    Pack pk;
-    const size_t o_k = pk.add(cur->keys_un, (size_t)n * sizeof(coeb_keypoint)), o_d = pk.add(cur->descriptors, (size_t)n * 32);
-    const size_t o_h =cur_has ? pk.add(cur_has, (size_t)n) : pk.fill(0, (size_t)n);
-    const size_t o_v = pk.add(kf->valid, (size_t)nq), o_x = pk.add(kf->world_pos, (size_t)nq * 12);
-    const size_t o_qd = pk.add(kf->descriptor, (size_t)nq * 32), o_mx = pk.add(kf->max_distance, (size_t)nq * 4);
-    const size_t o_mn = pk.add(kf->min_distance, (size_t)nq * 4), o_a = pk.add(kf->angle, (size_t)nq * 4);
-    const size_t o_T = pk.add(Tcw, 64);
-    if ((rc = stage_in(c, pk, &dbase, s))) return rc;
+    Staged st;
+    const size_t o_k = st.add(cur->keys_un, (size_t)n * sizeof(coeb_keypoint)), o_d = st.add(cur->descriptors, (size_t)n * 32);
+    const size_t o_h = cur_has ? st.add(cur_has, (size_t)n) : st.fill(0, (size_t)n);
+    const size_t o_v = st.add(kf->valid, (size_t)nq), o_x = st.add(kf->world_pos, (size_t)nq * 12);
+    const size_t o_qd = st.add(kf->descriptor, (size_t)nq * 32), o_mx = st.add(kf->max_distance, (size_t)nq * 4);
+    const size_t o_mn = st.add(kf->min_distance, (size_t)nq * 4), o_a = st.add(kf->angle, (size_t)nq * 4);
+    const size_t o_T = st.add(Tcw, 64);
+    if ((rc = st.stage(c, s, false))) return rc;
     KfBufs b;
-    b.cur_kps = dbase + o_k; b.cur_desc = dbase + o_d; b.cur_has = dbase + o_h; b.cur_n = n;
-    b.valid = dbase + o_v; b.xw = (const float*)(dbase + o_x); b.desc = dbase + o_qd;
-    b.maxd = (const float*)(dbase + o_mx); b.mind = (const float*)(dbase + o_mn); b.angle = (const float*)(dbase + o_a);
-    b.kf_n = nq; b.Tcw = (const float*)(dbase + o_T);
+    b.cur_kps = st.dev<void>(o_k); b.cur_desc = st.dev<uint8_t>(o_d); b.cur_has = st.dev<uint8_t>(o_h); b.cur_n = n;
+    b.valid = st.dev<uint8_t>(o_v); b.xw = st.dev<float>(o_x); b.desc = st.dev<uint8_t>(o_qd);
+    b.maxd = st.dev<float>(o_mx); b.mind = st.dev<float>(o_mn); b.angle = st.dev<float>(o_a);
+    b.kf_n = nq; b.Tcw = st.dev<float>(o_T);
     b.match = dout; b.nmatch = dout + cs; b.lists = sf.l_list.p; b.err = c->ex.err.p; b.path = sf.l_path.p;
     rc = launch_match_kf(make_cam(c, cam), b, th, orb_dist, check_ori ? 1 : 0, s, &c->hook);
     if (rc == -2) return set_err(c, COEB_ERANGE, "coeb_match_keyframe: frame and keyframe exceed the LDS budget");
@@ -1140,44 +1223,34 @@ int coeb_pose_optimization(coeb_ctx* c, const coeb_camera* cam, const coeb_pose_
     (void)hipSetDevice(c->device);
     const int cs = std::max(n, 1);
     int rc;
-    uint8_t* dbase;
-    SingleFrameBufs& sf = c->sf;
-    if ((rc = ensure(c, sf.p_act, cs)) || (rc = ensure(c, sf.p_edge, cs)) || (rc = ensure(c, sf.p_chi, cs))) return rc;
+    if ((rc = pose_scratch(c, cs))) return rc;
     hipStream_t s = main_stream(c);
-    // one staged region: outputs first (result, pose, outlier flags; copied back in one go), then inputs
-    Pack pk;
-    const size_t o_n = pk.add(&fr->n, 4), o_res = pk.fill(0, 4), o_T = pk.add(Tcw, 64), o_out = pk.fill(0, (size_t)cs);
+    // the results first (result, pose, outlier flags: all uploaded, copied back in one go), then the inputs
+    Staged st;
+    const size_t o_n = st.add(&fr->n, 4), o_res = st.fill(0, 4), o_T = st.add(Tcw, 64), o_out = st.fill(0, (size_t)cs);
     const size_t head = o_out + (size_t)cs;
-    const size_t o_h = pk.add(fr->has_mappoint, (size_t)n), o_x = pk.add(fr->world_pos, (size_t)n * 12);
-    const size_t o_k = pk.add(fr->keys_un, (size_t)n * sizeof(coeb_keypoint)), o_ur = pk.add(fr->u_right, (size_t)n * 4);
-    const size_t o_is = pk.add(c->tab.inv_sigma2, sizeof(float) * COEB_MAXL);
-    if ((rc = stage_in(c, pk, &dbase, s))) return rc;
-    PoseBufs b;
-    b.n = (const int*)(dbase + o_n); b.has_mp = dbase + o_h; b.xw = (const float*)(dbase + o_x); b.kps = dbase + o_k;
-    b.ur = (const float*)(dbase + o_ur); b.inv_sigma2 = (const float*)(dbase + o_is); b.Tcw = (float*)(dbase + o_T);
-    b.outlier = dbase + o_out; b.result = (int*)(dbase + o_res); b.edges = sf.p_edge.p; b.active = sf.p_act.p; b.chi2 = sf.p_chi.p;
-    b.timing = nullptr;
-    b.stride = cs;
+    const size_t o_h = st.add(fr->has_mappoint, (size_t)n), o_x = st.add(fr->world_pos, (size_t)n * 12);
+    const size_t o_k = st.add(fr->keys_un, (size_t)n * sizeof(coeb_keypoint)), o_ur = st.add(fr->u_right, (size_t)n * 4);
+    const size_t o_is = st.add(c->tab.inv_sigma2, sizeof(float) * COEB_MAXL);
+    if ((rc = st.stage(c, s, false))) return rc;
+    const PoseBufs b = pose_bufs(c, st.dev<int>(o_n), st.dev<uint8_t>(o_h), st.dev<float>(o_x), st.dev<void>(o_k),
+                                 st.dev<float>(o_ur), st.dev<float>(o_is), st.dev<float>(o_T), st.dev<uint8_t>(o_out),
+                                 st.dev<int>(o_res), cs);
     if (launch_pose(b, 1, cam->fx, cam->fy, cam->cx, cam->cy, cam->bf, s, &c->hook))
         return hip_err(c, hipGetLastError(), "launch_pose");
-    HIP_TRY(c, hipMemcpyAsync(c->pin, dbase, head, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    int res;
-    memcpy(&res, c->pin + o_res, 4);
-    memcpy(Tcw, c->pin + o_T, 64);
+    if ((rc = st.finish(c, s, 0, head, false))) return rc;
+    memcpy(Tcw, st.host<float>(o_T), 64);
     if (n && outlier_out)
         for (int i = 0; i < n; i++)
-            if (fr->has_mappoint[i]) outlier_out[i] = c->pin[o_out + i];
-    *ninliers = res;
+            if (fr->has_mappoint[i]) outlier_out[i] = st.pin[o_out + i];
+    *ninliers = *st.host<int>(o_res);
     return COEB_OK;
 }
 
 namespace {
 
-// Common body of coeb_search_local_points and coeb_track_local_map (pose: the latter).  One staged
-// region on the device: the inputs (uploaded), then the results (counts and pose, uploaded with
-// the inputs as their initial values; matches, outlier flags and track fields, written by the
-// kernels) copied back in one piece, then scratch.
+// Common body of coeb_search_local_points and coeb_track_local_map (pose: the latter).  Copied back:
+// the counts and the pose, matches and outlier flags, and the track fields where asked for.
 int track_local_map_impl(coeb_ctx* c, const char* who, bool pose, const coeb_camera* cam, const coeb_curframe* cur,
                          const int32_t* cur_obs, const float* cur_xw, float* Tcw, const coeb_local_points* mp,
                          float cos_limit, float th, float nnratio, int only_tracking, const coeb_track_fields* tf,
@@ -1197,9 +1270,7 @@ int track_local_map_impl(coeb_ctx* c, const char* who, bool pose, const coeb_cam
         return set_err(c, COEB_EINVAL, w + ": missing local-map arrays");
     if (pose && n && cur_obs && !cur_xw) return set_err(c, COEB_EINVAL, w + ": cur_observations without cur_world_pos");
     // which keypoints take a point is decided on the device: k_pose indexes mvInvLevelSigma2[octave] of any of them
-    for (int i = 0; i < n; i++)
-        if (cur->keys_un[i].octave < 0 || cur->keys_un[i].octave >= c->tab.nlevels)
-            return set_err(c, COEB_EINVAL, w + ": keypoint octave outside the pyramid");
+    if (!octaves_in_pyramid(c, cur->keys_un, n)) return set_err(c, COEB_EINVAL, w + ": keypoint octave outside the pyramid");
     // PredictScale's (int)ceil(log(mfMaxDistance / dist) / mfLogScaleFactor) is undefined otherwise
     for (int q = 0; q < nq; q++) {
         if (!mp->valid[q]) continue;
@@ -1214,95 +1285,82 @@ int track_local_map_impl(coeb_ctx* c, const char* who, bool pose, const coeb_cam
     (void)hipSetDevice(c->device);
     const int cs = std::max(n, 1), qs = std::max(nq, 1);
     int rc;
-    uint8_t* dbase;
     SingleFrameBufs& sf = c->sf;
     if ((rc = ensure(c, sf.l_list, (size_t)qs * kCQ)) || (rc = ensure(c, sf.l_path, 2)) || (rc = ensure(c, c->ex.err, 4)) ||
-        (rc = ensure(c, sf.p_act, cs)) || (rc = ensure(c, sf.p_edge, cs)) || (rc = ensure(c, sf.p_chi, cs)))
+        (rc = pose_scratch(c, cs)))
         return rc;
     hipStream_t s = main_stream(c);
-    Pack pk;
-    const size_t o_k = pk.add(cur->keys_un, (size_t)n * sizeof(coeb_keypoint)), o_d = pk.add(cur->descriptors, (size_t)n * 32);
-    const size_t o_ur = pk.add(cur->u_right, (size_t)n * 4);
-    const size_t o_co = cur_obs ? pk.add(cur_obs, (size_t)n * 4) : pk.fill(0xff, (size_t)n * 4);   // -1: all NULL
+    Staged st;
+    const CurOff o_c = pack_cur(st, cur);
+    const size_t o_co = cur_obs ? st.add(cur_obs, (size_t)n * 4) : st.fill(0xff, (size_t)n * 4);   // -1: all NULL
     const size_t nx = pose ? (size_t)n * 12 : 0;    // entry MapPoint positions: the optimiser's only
-    const size_t o_cx = cur_obs && cur_xw ? pk.add(cur_xw, nx) : pk.fill(0, nx);
-    const size_t o_v = pk.add(mp->valid, (size_t)nq), o_x = pk.add(mp->world_pos, (size_t)nq * 12);
-    const size_t o_nr = pk.add(mp->normal, (size_t)nq * 12), o_mx = pk.add(mp->max_distance, (size_t)nq * 4);
-    const size_t o_mn = pk.add(mp->min_distance, (size_t)nq * 4), o_qd = pk.add(mp->descriptor, (size_t)nq * 32);
-    const size_t o_no = pk.add(mp->observations, (size_t)nq * 4), o_is = pk.add(c->tab.inv_sigma2, sizeof(float) * COEB_MAXL);
-    const size_t o_T0 = pk.add(Tcw, 64);            // the pose the frustum reads
+    const size_t o_cx = cur_obs && cur_xw ? st.add(cur_xw, nx) : st.fill(0, nx);
+    const size_t o_v = st.add(mp->valid, (size_t)nq), o_x = st.add(mp->world_pos, (size_t)nq * 12);
+    const size_t o_nr = st.add(mp->normal, (size_t)nq * 12), o_mx = st.add(mp->max_distance, (size_t)nq * 4);
+    const size_t o_mn = st.add(mp->min_distance, (size_t)nq * 4), o_qd = st.add(mp->descriptor, (size_t)nq * 32);
+    const size_t o_no = st.add(mp->observations, (size_t)nq * 4), o_is = st.add(c->tab.inv_sigma2, sizeof(float) * COEB_MAXL);
+    const size_t o_T0 = st.add(Tcw, 64);            // the pose the frustum reads
     // results with an initial value: {n, nToMatch, ninliers_pose, mnMatchesInliers}, the pose k_pose updates
     const int32_t cnt[4] = {n, 0, 0, 0};
-    const size_t o_cnt = pk.add(cnt, 16), o_T = pk.add(Tcw, 64);
-    // results the kernels write (not uploaded), then scratch
-    size_t at = pk.total;
-    auto take = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 15) & ~(size_t)15; return o; };
-    const size_t o_m = take(((size_t)cs + 1) * 4), o_out = take((size_t)cs);
-    const size_t head_end = at;
-    const size_t o_iv = take((size_t)qs), o_px = take((size_t)qs * 4), o_py = take((size_t)qs * 4), o_pxr = take((size_t)qs * 4);
-    const size_t o_lv = take((size_t)qs * 4), o_vc = take((size_t)qs * 4);
-    const size_t back_end = tf ? at : head_end;
-    const size_t o_h2 = take((size_t)cs), o_x2 = take((size_t)cs * 12), o_o2 = take((size_t)cs * 4);
-    const size_t o_err = at;
-    if ((rc = pinned(c, o_err + 16)) || (rc = ensure(c, c->ex.stage, at)) || (rc = stage_in(c, pk, &dbase, s))) return rc;
+    const size_t o_cnt = st.add(cnt, 16), o_T = st.add(Tcw, 64);
+    // results the kernels write (the track fields only where asked for), then scratch
+    const size_t o_m = st.take(((size_t)cs + 1) * 4), o_out = st.take((size_t)cs);
+    const size_t head_end = st.end();
+    const size_t o_iv = st.take((size_t)qs), o_px = st.take((size_t)qs * 4), o_py = st.take((size_t)qs * 4);
+    const size_t o_pxr = st.take((size_t)qs * 4), o_lv = st.take((size_t)qs * 4), o_vc = st.take((size_t)qs * 4);
+    const size_t back_end = tf ? st.end() : head_end;
+    const size_t o_h2 = st.take((size_t)cs), o_x2 = st.take((size_t)cs * 12), o_o2 = st.take((size_t)cs * 4);
+    if ((rc = st.stage(c, s, true))) return rc;
     const MatchCam mcam = make_cam(c, cam);
     LmBufs t;
     memset(&t, 0, sizeof(t));
-    int32_t* dcnt = (int32_t*)(dbase + o_cnt);
-    t.mp_n = nq; t.valid = dbase + o_v; t.xw = (const float*)(dbase + o_x); t.normal = (const float*)(dbase + o_nr);
-    t.maxd = (const float*)(dbase + o_mx); t.mind = (const float*)(dbase + o_mn); t.nobs = (const int*)(dbase + o_no);
-    t.Tcw = (const float*)(dbase + o_T0); t.cos_limit = cos_limit;
-    t.in_view = dbase + o_iv; t.px = (float*)(dbase + o_px); t.py = (float*)(dbase + o_py); t.pxr = (float*)(dbase + o_pxr);
-    t.level = (int*)(dbase + o_lv); t.vcos = (float*)(dbase + o_vc); t.n_to_match = dcnt + 1;
-    t.cur_n = n; t.cur_obs = (const int*)(dbase + o_co); t.cur_xw = (const float*)(dbase + o_cx);
-    t.lmatch = (const int*)(dbase + o_m);
-    t.has2 = dbase + o_h2; t.xw2 = (float*)(dbase + o_x2); t.obs2 = (int*)(dbase + o_o2);
-    t.outl = dbase + o_out; t.only_tracking = only_tracking ? 1 : 0; t.ninl = dcnt + 3;
+    int32_t* dcnt = st.dev<int32_t>(o_cnt);
+    t.mp_n = nq; t.valid = st.dev<uint8_t>(o_v); t.xw = st.dev<float>(o_x); t.normal = st.dev<float>(o_nr);
+    t.maxd = st.dev<float>(o_mx); t.mind = st.dev<float>(o_mn); t.nobs = st.dev<int>(o_no);
+    t.Tcw = st.dev<float>(o_T0); t.cos_limit = cos_limit;
+    t.in_view = st.dev<uint8_t>(o_iv); t.px = st.dev<float>(o_px); t.py = st.dev<float>(o_py); t.pxr = st.dev<float>(o_pxr);
+    t.level = st.dev<int>(o_lv); t.vcos = st.dev<float>(o_vc); t.n_to_match = dcnt + 1;
+    t.cur_n = n; t.cur_obs = st.dev<int>(o_co); t.cur_xw = st.dev<float>(o_cx); t.lmatch = st.dev<int>(o_m);
+    t.has2 = st.dev<uint8_t>(o_h2); t.xw2 = st.dev<float>(o_x2); t.obs2 = st.dev<int>(o_o2);
+    t.outl = st.dev<uint8_t>(o_out); t.only_tracking = only_tracking ? 1 : 0; t.ninl = dcnt + 3;
     if (launch_frustum(mcam, t, s, &c->hook)) return hip_err(c, hipGetLastError(), "launch_frustum");
     LocalBufs b;
-    b.cur_kps = dbase + o_k; b.cur_desc = dbase + o_d; b.cur_ur = (const float*)(dbase + o_ur);
+    b.cur_kps = st.dev<void>(o_c.k); b.cur_desc = st.dev<uint8_t>(o_c.d); b.cur_ur = st.dev<float>(o_c.ur);
     b.cur_obs = t.cur_obs; b.cur_n = n;
     b.in_view = t.in_view; b.proj_x = t.px; b.proj_y = t.py; b.proj_xr = t.pxr; b.level = t.level; b.view_cos = t.vcos;
-    b.desc = dbase + o_qd; b.nobs = t.nobs; b.mp_n = nq;
-    b.match = (int*)(dbase + o_m); b.nmatch = b.match + cs; b.lists = sf.l_list.p; b.err = c->ex.err.p; b.path = sf.l_path.p;
+    b.desc = st.dev<uint8_t>(o_qd); b.nobs = t.nobs; b.mp_n = nq;
+    b.match = st.dev<int>(o_m); b.nmatch = b.match + cs; b.lists = sf.l_list.p; b.err = c->ex.err.p; b.path = sf.l_path.p;
     // nothing in view: the search finds nothing (the reference skips it, Tracking.cc:1261)
     rc = launch_match_local(mcam, b, th, nnratio, s, &c->hook);
     if (rc == -2) return set_err(c, COEB_ERANGE, w + ": frame and local map exceed the LDS budget");
     if (rc) return hip_err(c, hipGetLastError(), "launch_match_local");
     if (pose) {
         if (launch_lm_pose_prep(t, s, &c->hook)) return hip_err(c, hipGetLastError(), "launch_lm_pose_prep");
-        PoseBufs p;
-        p.n = dcnt; p.has_mp = t.has2; p.xw = t.xw2; p.kps = dbase + o_k; p.ur = (const float*)(dbase + o_ur);
-        p.inv_sigma2 = (const float*)(dbase + o_is); p.Tcw = (float*)(dbase + o_T); p.outlier = dbase + o_out;
-        p.result = dcnt + 2; p.edges = sf.p_edge.p; p.active = sf.p_act.p; p.chi2 = sf.p_chi.p;
-        p.stride = cs; p.timing = nullptr;
+        const PoseBufs p = pose_bufs(c, dcnt, t.has2, t.xw2, b.cur_kps, b.cur_ur, st.dev<float>(o_is), st.dev<float>(o_T),
+                                     st.dev<uint8_t>(o_out), dcnt + 2, cs);
         if (launch_pose(p, 1, cam->fx, cam->fy, cam->cx, cam->cy, cam->bf, s, &c->hook))
             return hip_err(c, hipGetLastError(), "launch_pose");
         if (launch_lm_tail(t, s, &c->hook)) return hip_err(c, hipGetLastError(), "launch_lm_tail");
     }
-    HIP_TRY(c, hipMemcpyAsync(c->pin + o_cnt, dbase + o_cnt, back_end - o_cnt, hipMemcpyDeviceToHost, s));
-    if ((rc = err_word_async(c, c->pin + o_err))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if ((rc = err_word_seen(c, c->pin + o_err))) return rc;
-    int32_t hc[4];
-    memcpy(hc, c->pin + o_cnt, 16);
-    const int32_t* hm = reinterpret_cast<const int32_t*>(c->pin + o_m);
+    if ((rc = st.finish(c, s, o_cnt, back_end, true))) return rc;
+    const int32_t* hc = st.host<int32_t>(o_cnt);
+    const int32_t* hm = st.host<int32_t>(o_m);
     if (n && match_out) memcpy(match_out, hm, (size_t)n * 4);
     *n_to_match = hc[1];
     *nlocal = hm[cs];
     if (tf && nq) {
-        if (tf->in_view) memcpy(tf->in_view, c->pin + o_iv, (size_t)nq);
-        if (tf->proj_x) memcpy(tf->proj_x, c->pin + o_px, (size_t)nq * 4);
-        if (tf->proj_y) memcpy(tf->proj_y, c->pin + o_py, (size_t)nq * 4);
-        if (tf->proj_xr) memcpy(tf->proj_xr, c->pin + o_pxr, (size_t)nq * 4);
-        if (tf->level) memcpy(tf->level, c->pin + o_lv, (size_t)nq * 4);
-        if (tf->view_cos) memcpy(tf->view_cos, c->pin + o_vc, (size_t)nq * 4);
+        if (tf->in_view) memcpy(tf->in_view, st.pin + o_iv, (size_t)nq);
+        if (tf->proj_x) memcpy(tf->proj_x, st.pin + o_px, (size_t)nq * 4);
+        if (tf->proj_y) memcpy(tf->proj_y, st.pin + o_py, (size_t)nq * 4);
+        if (tf->proj_xr) memcpy(tf->proj_xr, st.pin + o_pxr, (size_t)nq * 4);
+        if (tf->level) memcpy(tf->level, st.pin + o_lv, (size_t)nq * 4);
+        if (tf->view_cos) memcpy(tf->view_cos, st.pin + o_vc, (size_t)nq * 4);
     }
     if (pose) {
-        memcpy(Tcw, c->pin + o_T, 64);
+        memcpy(Tcw, st.pin + o_T, 64);
         if (outlier_out)
             for (int i = 0; i < n; i++)
-                if (hm[i] >= 0 || (cur_obs && cur_obs[i] >= 0)) outlier_out[i] = c->pin[o_out + i];
+                if (hm[i] >= 0 || (cur_obs && cur_obs[i] >= 0)) outlier_out[i] = st.pin[o_out + i];
         *ninliers_pose = hc[2];
         *nmatches_inliers = hc[3];
     }
@@ -1332,9 +1390,7 @@ int coeb_track_local_map(coeb_ctx* c, const coeb_camera* cam, const coeb_curfram
                                 ninliers_pose, nmatches_inliers);
 }
 
-// One staged region on the device, as track_local_map_impl's: the inputs, then the results (counts
-// and pose uploaded as their initial values; matches, discards and the transform's ids written by the
-// kernels) copied back in one piece, then scratch.
+// Copied back: the counts and the pose, matches, discards and the transform's ids.
 int coeb_track_reference_keyframe(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe* cur,
                                   const int32_t* cur_node_id, int levelsup, const coeb_ref_keyframe* kf, float Tcw[16],
                                   float nnratio, int check_orientation, int min_matches, int32_t* word_out,
@@ -1356,73 +1412,58 @@ int coeb_track_reference_keyframe(coeb_ctx* c, const coeb_camera* cam, const coe
                !kf->observations))
         return set_err(c, COEB_EINVAL, w + ": missing keyframe arrays");
     // which keypoints take a point is decided on the device: k_pose indexes mvInvLevelSigma2[octave] of any of them
+    if (!octaves_in_pyramid(c, cur->keys_un, n)) return set_err(c, COEB_EINVAL, w + ": keypoint octave outside the pyramid");
     std::vector<float> angle((size_t)n);            // F.mvKeys[i].angle = mvKeysUn[i].angle, contiguous for the matcher
-    for (int i = 0; i < n; i++) {
-        if (cur->keys_un[i].octave < 0 || cur->keys_un[i].octave >= c->tab.nlevels)
-            return set_err(c, COEB_EINVAL, w + ": keypoint octave outside the pyramid");
-        angle[i] = cur->keys_un[i].angle;
-    }
+    for (int i = 0; i < n; i++) angle[i] = cur->keys_un[i].angle;
     (void)hipSetDevice(c->device);
     const int cs = std::max(n, 1);
     int rc;
-    uint8_t* dbase;
-    SingleFrameBufs& sf = c->sf;
-    if ((rc = bow_search_bufs(c, nq, n)) || (rc = ensure(c, sf.p_act, cs)) || (rc = ensure(c, sf.p_edge, cs)) ||
-        (rc = ensure(c, sf.p_chi, cs)))
-        return rc;
+    if ((rc = bow_search_bufs(c, nq, n)) || (rc = pose_scratch(c, cs))) return rc;
     hipStream_t s = main_stream(c);
-    Pack pk;
-    const size_t o_k = pk.add(cur->keys_un, (size_t)n * sizeof(coeb_keypoint)), o_d = pk.add(cur->descriptors, (size_t)n * 32);
-    const size_t o_ur = pk.add(cur->u_right, (size_t)n * 4), o_ca = pk.add(angle.data(), (size_t)n * 4);
-    const size_t o_cn = transform ? 0 : pk.add(cur_node_id, (size_t)n * 4);
-    const size_t o_v = pk.add(kf->bow.valid, (size_t)nq), o_kd = pk.add(kf->bow.descriptor, (size_t)nq * 32);
-    const size_t o_kn = pk.add(kf->bow.node_id, (size_t)nq * 4), o_ka = pk.add(kf->bow.angle, (size_t)nq * 4);
-    const size_t o_x = pk.add(kf->world_pos, (size_t)nq * 12), o_no = pk.add(kf->observations, (size_t)nq * 4);
-    const size_t o_is = pk.add(c->tab.inv_sigma2, sizeof(float) * COEB_MAXL);
+    Staged st;
+    const CurOff o_c = pack_cur(st, cur);
+    const size_t o_ca = st.add(angle.data(), (size_t)n * 4), o_cn = transform ? 0 : st.add(cur_node_id, (size_t)n * 4);
+    const size_t o_v = st.add(kf->bow.valid, (size_t)nq), o_kd = st.add(kf->bow.descriptor, (size_t)nq * 32);
+    const size_t o_kn = st.add(kf->bow.node_id, (size_t)nq * 4), o_ka = st.add(kf->bow.angle, (size_t)nq * 4);
+    const size_t o_x = st.add(kf->world_pos, (size_t)nq * 12), o_no = st.add(kf->observations, (size_t)nq * 4);
+    const size_t o_is = st.add(c->tab.inv_sigma2, sizeof(float) * COEB_MAXL);
     // results with an initial value: {the optimiser's n, ninliers_pose, nmatches, nmatches_map}, the pose k_pose updates
     const int32_t cnt[4] = {0, 0, 0, 0};
-    const size_t o_cnt = pk.add(cnt, 16), o_T = pk.add(Tcw, 64);
-    // results the kernels write (not uploaded), then scratch
-    size_t at = pk.total;
-    auto take = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 15) & ~(size_t)15; return o; };
-    const size_t o_m = take(((size_t)cs + 1) * 4), o_dis = take((size_t)cs * 4);
-    const size_t o_wd = take(transform ? (size_t)cs * 4 : 0), o_nd = take(transform ? (size_t)cs * 4 : 0);
-    const size_t back_end = at;
-    const size_t o_has = take((size_t)cs), o_xw = take((size_t)cs * 12), o_out = take((size_t)cs);
-    if ((rc = pinned(c, at)) || (rc = ensure(c, c->ex.stage, at)) || (rc = stage_in(c, pk, &dbase, s))) return rc;
-    int32_t* dcnt = (int32_t*)(dbase + o_cnt);
+    const size_t o_cnt = st.add(cnt, 16), o_T = st.add(Tcw, 64);
+    // results the kernels write (matches, discards, the transform's ids), then scratch
+    const size_t o_m = st.take(((size_t)cs + 1) * 4), o_dis = st.take((size_t)cs * 4);
+    const size_t o_wd = st.take(transform ? (size_t)cs * 4 : 0), o_nd = st.take(transform ? (size_t)cs * 4 : 0);
+    const size_t back_end = st.end();
+    const size_t o_has = st.take((size_t)cs), o_xw = st.take((size_t)cs * 12), o_out = st.take((size_t)cs);
+    if ((rc = st.stage(c, s, false))) return rc;    // this call does not read the error word
+    int32_t* dcnt = st.dev<int32_t>(o_cnt);
     if (transform && n &&
-        launch_transform(c, dbase + o_d, nullptr, n, n, 1, levelsup, (int*)(dbase + o_wd), (int*)(dbase + o_nd), s))
+        launch_transform(c, st.dev<uint8_t>(o_c.d), nullptr, n, n, 1, levelsup, st.dev<int>(o_wd), st.dev<int>(o_nd), s))
         return hip_err(c, hipGetLastError(), "k_bow_transform");
     BowSearch bs;
-    bs.kf_valid = dbase + o_v; bs.kf_desc = dbase + o_kd; bs.kf_node = (const int*)(dbase + o_kn);
-    bs.kf_angle = (const float*)(dbase + o_ka); bs.kf_n = nq;
-    bs.cur_desc = dbase + o_d; bs.cur_node = (const int*)(dbase + (transform ? o_nd : o_cn));
-    bs.cur_angle = (const float*)(dbase + o_ca); bs.cur_n = n; bs.match = (int*)(dbase + o_m);
+    bs.kf_valid = st.dev<uint8_t>(o_v); bs.kf_desc = st.dev<uint8_t>(o_kd); bs.kf_node = st.dev<int>(o_kn);
+    bs.kf_angle = st.dev<float>(o_ka); bs.kf_n = nq;
+    bs.cur_desc = st.dev<uint8_t>(o_c.d); bs.cur_node = st.dev<int>(transform ? o_nd : o_cn);
+    bs.cur_angle = st.dev<float>(o_ca); bs.cur_n = n; bs.match = st.dev<int>(o_m);
     if (launch_search_by_bow(c, bs, nnratio, check_orientation, s)) return hip_err(c, hipGetLastError(), "launch_search_by_bow");
     TrkBufs t;
     t.cur_n = n; t.match = bs.match; t.nm_bow = bs.match + cs; t.min_matches = min_matches;
-    t.kf_xw = (const float*)(dbase + o_x); t.kf_nobs = (const int*)(dbase + o_no);
-    t.has = dbase + o_has; t.xw = (float*)(dbase + o_xw); t.pose_n = dcnt; t.outl = dbase + o_out;
-    t.discarded = (int*)(dbase + o_dis); t.nmatches = dcnt + 2; t.nmap = dcnt + 3;
+    t.kf_xw = st.dev<float>(o_x); t.kf_nobs = st.dev<int>(o_no);
+    t.has = st.dev<uint8_t>(o_has); t.xw = st.dev<float>(o_xw); t.pose_n = dcnt; t.outl = st.dev<uint8_t>(o_out);
+    t.discarded = st.dev<int>(o_dis); t.nmatches = dcnt + 2; t.nmap = dcnt + 3;
     if (launch_trk_pose_prep(t, s, &c->hook)) return hip_err(c, hipGetLastError(), "launch_trk_pose_prep");
-    PoseBufs p;
-    p.n = dcnt; p.has_mp = t.has; p.xw = t.xw; p.kps = dbase + o_k; p.ur = (const float*)(dbase + o_ur);
-    p.inv_sigma2 = (const float*)(dbase + o_is); p.Tcw = (float*)(dbase + o_T); p.outlier = t.outl;
-    p.result = dcnt + 1; p.edges = sf.p_edge.p; p.active = sf.p_act.p; p.chi2 = sf.p_chi.p;
-    p.stride = cs; p.timing = nullptr;
+    const PoseBufs p = pose_bufs(c, dcnt, t.has, t.xw, st.dev<void>(o_c.k), st.dev<float>(o_c.ur), st.dev<float>(o_is),
+                                 st.dev<float>(o_T), t.outl, dcnt + 1, cs);
     if (launch_pose(p, 1, cam->fx, cam->fy, cam->cx, cam->cy, cam->bf, s, &c->hook))
         return hip_err(c, hipGetLastError(), "launch_pose");
     if (launch_trk_tail(t, s, &c->hook)) return hip_err(c, hipGetLastError(), "launch_trk_tail");
-    HIP_TRY(c, hipMemcpyAsync(c->pin + o_cnt, dbase + o_cnt, back_end - o_cnt, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    int32_t hc[4];
-    memcpy(hc, c->pin + o_cnt, 16);
-    const int32_t* hm = reinterpret_cast<const int32_t*>(c->pin + o_m);
+    if ((rc = st.finish(c, s, o_cnt, back_end, false))) return rc;
+    const int32_t* hc = st.host<int32_t>(o_cnt);
+    const int32_t* hm = st.host<int32_t>(o_m);
     if (transform) {
-        const int32_t* h_word = reinterpret_cast<const int32_t*>(c->pin + o_wd);
+        const int32_t* h_word = st.host<int32_t>(o_wd);
         if (word_out) memcpy(word_out, h_word, (size_t)n * 4);
-        if (node_out) memcpy(node_out, c->pin + o_nd, (size_t)n * 4);
+        if (node_out) memcpy(node_out, st.pin + o_nd, (size_t)n * 4);
         if (weight_out)
             for (int i = 0; i < n; i++) {
                 const int wd = h_word[i];
@@ -1430,8 +1471,8 @@ int coeb_track_reference_keyframe(coeb_ctx* c, const coeb_camera* cam, const coe
             }
     }
     if (n) memcpy(match_out, hm, (size_t)n * 4);
-    if (n && discarded_out) memcpy(discarded_out, c->pin + o_dis, (size_t)n * 4);
-    memcpy(Tcw, c->pin + o_T, 64);
+    if (n && discarded_out) memcpy(discarded_out, st.pin + o_dis, (size_t)n * 4);
+    memcpy(Tcw, st.pin + o_T, 64);
     *nmatches_bow = hm[cs];
     *ninliers_pose = hc[1];
     *nmatches = hc[2];
@@ -1439,10 +1480,9 @@ int coeb_track_reference_keyframe(coeb_ctx* c, const coeb_camera* cam, const coe
     return COEB_OK;
 }
 
-// One staged region on the device, as coeb_track_reference_keyframe's: the inputs (the last frame's
-// MapPoint arrays among them, which k_vo_points updates in place before k_match reads them), then the
-// results (counts and pose uploaded as their initial values; matches, discards, outlier flags and the
-// created points written by the kernels) copied back in one piece, then scratch.
+// The last frame's MapPoint arrays are among the inputs; k_vo_points updates them in place before
+// k_match reads them.  Copied back: the counts and the pose, matches, discards, outlier flags and the
+// created points.
 static_assert(kVoMaxLast == COEB_VO_MAX_LAST, "k_vo_points' limit is the header's");
 int coeb_track_motion_model(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe* cur, const coeb_lastframe* last,
                             const coeb_vo_points* vo, const float Tcw_last[16], float Tcw[16], float th, int bmono,
@@ -1458,74 +1498,50 @@ int coeb_track_motion_model(coeb_ctx* c, const coeb_camera* cam, const coeb_curf
     if (n > kCurMax) return set_err(c, COEB_EINVAL, w + ": more than 4095 current keypoints");
     if (n && (!cur->keys_un || !cur->descriptors || !cur->u_right || !match_out))
         return set_err(c, COEB_EINVAL, w + ": missing current-frame arrays");
-    if (nl && (!last->has_mappoint || !last->outlier || !last->world_pos || !last->mp_descriptor ||
-               !last->mp_observations || !last->keys_un))
-        return set_err(c, COEB_EINVAL, w + ": missing LastFrame arrays");
+    if (last_arrays_missing(last)) return set_err(c, COEB_EINVAL, w + ": missing LastFrame arrays");
     if (vo && nl && (!vo->depth || !vo->descriptors)) return set_err(c, COEB_EINVAL, w + ": missing visual-odometry arrays");
     if (vo && nl > COEB_VO_MAX_LAST) return set_err(c, COEB_EINVAL, w + ": more LastFrame keypoints than COEB_VO_MAX_LAST");
     if (!match_lastframe_fits(n, nl)) return set_err(c, COEB_ERANGE, w + ": the two frames exceed the LDS budget");
     // which keypoints take a point, and which LastFrame slots get one, is decided on the device: k_pose
     // indexes mvInvLevelSigma2[octave] of the former, k_match mvScaleFactors[octave] of the latter
-    for (int i = 0; i < n; i++)
-        if (cur->keys_un[i].octave < 0 || cur->keys_un[i].octave >= c->tab.nlevels)
-            return set_err(c, COEB_EINVAL, w + ": keypoint octave outside the pyramid");
-    for (int i = 0; i < nl; i++)
-        if (last->keys_un[i].octave < 0 || last->keys_un[i].octave >= c->tab.nlevels)
-            return set_err(c, COEB_EINVAL, w + ": LastFrame keypoint octave outside the pyramid");
+    if (!octaves_in_pyramid(c, cur->keys_un, n)) return set_err(c, COEB_EINVAL, w + ": keypoint octave outside the pyramid");
+    if (!octaves_in_pyramid(c, last->keys_un, nl))
+        return set_err(c, COEB_EINVAL, w + ": LastFrame keypoint octave outside the pyramid");
     (void)hipSetDevice(c->device);
     const int cs = std::max(n, 1), ls = std::max(nl, 1);
     const bool run_vo = vo && nl;
     int rc;
-    uint8_t* dbase;
     SingleFrameBufs& sf = c->sf;
     if ((rc = ensure(c, sf.m_scr, (size_t)ls * kCQ)) || (rc = ensure(c, sf.m_qn, (size_t)ls + kMaxSplit)) ||
-        (rc = ensure(c, c->ex.err, 4)) || (rc = ensure(c, sf.p_act, cs)) || (rc = ensure(c, sf.p_edge, cs)) ||
-        (rc = ensure(c, sf.p_chi, cs)))
+        (rc = ensure(c, c->ex.err, 4)) || (rc = pose_scratch(c, cs)))
         return rc;
     hipStream_t s = main_stream(c);
-    const int32_t cnts[2] = {n, nl};
-    Pack pk;
-    const size_t o_cn = pk.add(cnts, 8), o_T0 = pk.add(Tcw, 64), o_Tl = pk.add(Tcw_last, 64);
-    const size_t o_ck = pk.add(cur->keys_un, (size_t)n * sizeof(coeb_keypoint)), o_cd = pk.add(cur->descriptors, (size_t)n * 32);
-    const size_t o_ur = pk.add(cur->u_right, (size_t)n * 4);
-    const size_t o_lk = pk.add(last->keys_un, (size_t)nl * sizeof(coeb_keypoint));
-    const size_t o_ld = pk.add(last->mp_descriptor, (size_t)nl * 32), o_h = pk.add(last->has_mappoint, (size_t)nl);
-    const size_t o_o = pk.add(last->outlier, (size_t)nl), o_xw = pk.add(last->world_pos, (size_t)nl * 12);
-    const size_t o_nb = pk.add(last->mp_observations, (size_t)nl * 4);
-    const size_t o_vz = run_vo ? pk.add(vo->depth, (size_t)nl * 4) : 0, o_vd = run_vo ? pk.add(vo->descriptors, (size_t)nl * 32) : 0;
-    const size_t o_is = pk.add(c->tab.inv_sigma2, sizeof(float) * COEB_MAXL);
+    Staged st;
+    LastPair lp;
+    pack_last_pair(st, cur, last, Tcw, Tcw_last, lp);
+    const size_t o_vz = run_vo ? st.add(vo->depth, (size_t)nl * 4) : 0, o_vd = run_vo ? st.add(vo->descriptors, (size_t)nl * 32) : 0;
+    const size_t o_is = st.add(c->tab.inv_sigma2, sizeof(float) * COEB_MAXL);
     // results with an initial value: {the optimiser's n, ninliers_pose, nmatches, nmatches_map}, the pose k_pose updates
     const int32_t cnt[4] = {0, 0, 0, 0};
-    const size_t o_cnt = pk.add(cnt, 16), o_T = pk.add(Tcw, 64);
-    // results the kernels write (not uploaded), then scratch
-    size_t at = pk.total;
-    auto take = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 15) & ~(size_t)15; return o; };
-    const size_t o_m = take(((size_t)cs + 1) * 4), o_dis = take((size_t)cs * 4), o_out = take((size_t)cs);
-    const size_t o_cr = take(run_vo ? (size_t)nl : 0), o_cp = take(run_vo ? (size_t)nl * 12 : 0);
-    const size_t back_end = at;
-    const size_t o_has = take((size_t)cs), o_px = take((size_t)cs * 12);
-    const size_t o_err = at;
-    if ((rc = pinned(c, o_err + 16)) || (rc = ensure(c, c->ex.stage, at)) || (rc = stage_in(c, pk, &dbase, s))) return rc;
-    int32_t* dcnt = (int32_t*)(dbase + o_cnt);
-    if (run_vo) {
+    const size_t o_cnt = st.add(cnt, 16), o_T = st.add(Tcw, 64);
+    // results the kernels write (matches, discards, outlier flags, the created points), then scratch
+    const size_t o_m = st.take(((size_t)cs + 1) * 4), o_dis = st.take((size_t)cs * 4), o_out = st.take((size_t)cs);
+    const size_t o_cr = st.take(run_vo ? (size_t)nl : 0), o_cp = st.take(run_vo ? (size_t)nl * 12 : 0);
+    const size_t back_end = st.end();
+    const size_t o_has = st.take((size_t)cs), o_px = st.take((size_t)cs * 12);
+    if ((rc = st.stage(c, s, true))) return rc;
+    int32_t* dcnt = st.dev<int32_t>(o_cnt);
+    MatchBufs mb = last_pair_bufs(c, st, lp, cs, ls);
+    mb.match = st.dev<int>(o_m); mb.nmatch = mb.match + cs;
+    if (run_vo) {                                   // the created points replace last-frame slots before k_match reads them
         VoBufs v;
-        v.n = nl; v.kps = dbase + o_lk; v.depth = (const float*)(dbase + o_vz); v.desc_in = dbase + o_vd;
-        v.Tcw_last = (const float*)(dbase + o_Tl); v.th_depth = vo->th_depth;
+        v.n = nl; v.kps = mb.last_kps; v.depth = st.dev<float>(o_vz); v.desc_in = st.dev<uint8_t>(o_vd);
+        v.Tcw_last = mb.Tcw_last; v.th_depth = vo->th_depth;
         v.fx = cam->fx; v.fy = cam->fy; v.cx = cam->cx; v.cy = cam->cy;
-        v.has = dbase + o_h; v.xw = (float*)(dbase + o_xw); v.desc = dbase + o_ld; v.nobs = (int*)(dbase + o_nb);
-        v.created = dbase + o_cr; v.created_pos = (float*)(dbase + o_cp);
+        v.has = st.dev<uint8_t>(lp.h); v.xw = st.dev<float>(lp.xw); v.desc = st.dev<uint8_t>(lp.ld); v.nobs = st.dev<int>(lp.nb);
+        v.created = st.dev<uint8_t>(o_cr); v.created_pos = st.dev<float>(o_cp);
         if (launch_vo_points(v, s, &c->hook)) return hip_err(c, hipGetLastError(), "launch_vo_points");
     }
-    MatchBufs mb;
-    memset(&mb, 0, sizeof(mb));
-    mb.cur_kps = dbase + o_ck; mb.cur_desc = dbase + o_cd; mb.cur_n = (const int32_t*)(dbase + o_cn);
-    mb.cur_ur = (const float*)(dbase + o_ur); mb.cur_stride = cs;
-    mb.last_kps = dbase + o_lk; mb.last_desc = dbase + o_ld; mb.last_n = (const int32_t*)(dbase + o_cn) + 1;
-    mb.last_has = dbase + o_h; mb.last_out = dbase + o_o; mb.last_xw = (const float*)(dbase + o_xw);
-    mb.last_nobs = (const int32_t*)(dbase + o_nb); mb.last_stride = ls;
-    mb.Tcw_cur = (const float*)(dbase + o_T0); mb.Tcw_last = (const float*)(dbase + o_Tl);
-    mb.match = (int*)(dbase + o_m); mb.nmatch = mb.match + cs; mb.scratch = sf.m_scr.p; mb.scratch_stride = ls * kCQ;
-    mb.err = c->ex.err.p; mb.qn = sf.m_qn.p; mb.qn_stride = mb.last_stride + kMaxSplit;
     // the 2*th retry below min_matches (:954-958) runs inside k_match
     if (launch_match(make_cam(c, cam), mb, 1, th, bmono, check_orientation, min_matches, s, &c->hook))
         return hip_err(c, hipGetLastError(), "launch_match");
@@ -1534,35 +1550,28 @@ int coeb_track_motion_model(coeb_ctx* c, const coeb_camera* cam, const coeb_curf
     TrkBufs t;
     t.cur_n = n; t.match = mb.match; t.nm_bow = mb.nmatch; t.min_matches = min_matches;
     t.kf_xw = mb.last_xw; t.kf_nobs = mb.last_nobs;
-    t.has = dbase + o_has; t.xw = (float*)(dbase + o_px); t.pose_n = dcnt; t.outl = dbase + o_out;
-    t.discarded = (int*)(dbase + o_dis); t.nmatches = dcnt + 2; t.nmap = dcnt + 3;
+    t.has = st.dev<uint8_t>(o_has); t.xw = st.dev<float>(o_px); t.pose_n = dcnt; t.outl = st.dev<uint8_t>(o_out);
+    t.discarded = st.dev<int>(o_dis); t.nmatches = dcnt + 2; t.nmap = dcnt + 3;
     if (launch_trk_pose_prep(t, s, &c->hook)) return hip_err(c, hipGetLastError(), "launch_trk_pose_prep");
-    PoseBufs p;
-    p.n = dcnt; p.has_mp = t.has; p.xw = t.xw; p.kps = dbase + o_ck; p.ur = (const float*)(dbase + o_ur);
-    p.inv_sigma2 = (const float*)(dbase + o_is); p.Tcw = (float*)(dbase + o_T); p.outlier = t.outl;
-    p.result = dcnt + 1; p.edges = sf.p_edge.p; p.active = sf.p_act.p; p.chi2 = sf.p_chi.p;
-    p.stride = cs; p.timing = nullptr;
+    const PoseBufs p = pose_bufs(c, dcnt, t.has, t.xw, mb.cur_kps, mb.cur_ur, st.dev<float>(o_is), st.dev<float>(o_T), t.outl,
+                                 dcnt + 1, cs);
     if (launch_pose(p, 1, cam->fx, cam->fy, cam->cx, cam->cy, cam->bf, s, &c->hook))
         return hip_err(c, hipGetLastError(), "launch_pose");
     if (launch_mm_tail(t, s, &c->hook)) return hip_err(c, hipGetLastError(), "launch_mm_tail");
-    HIP_TRY(c, hipMemcpyAsync(c->pin + o_cnt, dbase + o_cnt, back_end - o_cnt, hipMemcpyDeviceToHost, s));
-    if ((rc = err_word_async(c, c->pin + o_err))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if ((rc = err_word_seen(c, c->pin + o_err))) return rc;
-    int32_t hc[4];
-    memcpy(hc, c->pin + o_cnt, 16);
-    const int32_t* hm = reinterpret_cast<const int32_t*>(c->pin + o_m);
+    if ((rc = st.finish(c, s, o_cnt, back_end, true))) return rc;
+    const int32_t* hc = st.host<int32_t>(o_cnt);
+    const int32_t* hm = st.host<int32_t>(o_m);
     if (n) memcpy(match_out, hm, (size_t)n * 4);
-    if (n && discarded_out) memcpy(discarded_out, c->pin + o_dis, (size_t)n * 4);
-    if (n && outlier_out) memcpy(outlier_out, c->pin + o_out, (size_t)n);
+    if (n && discarded_out) memcpy(discarded_out, st.pin + o_dis, (size_t)n * 4);
+    if (n && outlier_out) memcpy(outlier_out, st.pin + o_out, (size_t)n);
     if (run_vo) {
-        const uint8_t* hcr = c->pin + o_cr;
+        const uint8_t* hcr = st.pin + o_cr;
         if (vo->created_out) memcpy(vo->created_out, hcr, (size_t)nl);
         if (vo->created_pos)
             for (int i = 0; i < nl; i++)
-                if (hcr[i]) memcpy(vo->created_pos + 3 * (size_t)i, c->pin + o_cp + 12 * (size_t)i, 12);
+                if (hcr[i]) memcpy(vo->created_pos + 3 * (size_t)i, st.pin + o_cp + 12 * (size_t)i, 12);
     }
-    memcpy(Tcw, c->pin + o_T, 64);
+    memcpy(Tcw, st.pin + o_T, 64);
     *nmatches_search = hm[cs];
     *ninliers_pose = hc[1];
     *nmatches = hc[2];
@@ -1570,11 +1579,9 @@ int coeb_track_motion_model(coeb_ctx* c, const coeb_camera* cam, const coeb_curf
     return COEB_OK;
 }
 
-// One staged region on the device, as coeb_track_motion_model's: the inputs (the hypotheses' arrays in
-// rows of one stride per side, cs keypoints / ks KeyFrame points, both multiples of 16 so that every
-// row of every element size starts on Pack's 16-byte grid), then the results (counts, first_good and the
-// poses uploaded as their initial values; the held indices and the packed outlier flags written by the
-// kernels) copied back in one piece, then scratch.
+// The hypotheses' arrays are staged in rows of one stride per side, cs keypoints / ks KeyFrame points,
+// both multiples of 16 so that every row of every element size starts on Pack's 16-byte grid.  Copied
+// back: the counts, first_good and the poses, the held indices and the packed outlier flags.
 static_assert(COEB_RELOC_MAX_HYP <= 64, "one workgroup per hypothesis, stack arrays below");
 int coeb_reloc_refine(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe* cur, coeb_reloc_hypothesis* hyp, int nhyp,
                       float th1, int orb_dist1, float th2, int orb_dist2, int check_orientation, int min_good,
@@ -1605,9 +1612,7 @@ int coeb_reloc_refine(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe* 
         kmax = std::max(kmax, kf.n);
     }
     // which keypoints take a point is decided on the device: k_pose indexes mvInvLevelSigma2[octave] of any of them
-    for (int i = 0; i < n; i++)
-        if (cur->keys_un[i].octave < 0 || cur->keys_un[i].octave >= c->tab.nlevels)
-            return set_err(c, COEB_EINVAL, w + ": keypoint octave outside the pyramid");
+    if (!octaves_in_pyramid(c, cur->keys_un, n)) return set_err(c, COEB_EINVAL, w + ": keypoint octave outside the pyramid");
     for (int h = 0; h < H; h++)
         if (!match_kf_fits(n, hyp[h].kf.n)) return set_err(c, COEB_ERANGE, w + ": frame and keyframe exceed the LDS budget");
     if (n == 0) {                                   // no edges, nGood = 0: every hypothesis stops at the first gate
@@ -1618,21 +1623,17 @@ int coeb_reloc_refine(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe* 
     (void)hipSetDevice(c->device);
     const int cs = (n + 15) & ~15, ks = (std::max(kmax, 1) + 15) & ~15;
     int rc;
-    uint8_t* dbase;
-    SingleFrameBufs& sf = c->sf;
-    if ((rc = ensure(c, sf.l_list, (size_t)H * ks * kCQ)) || (rc = ensure(c, c->ex.err, 4)) ||
-        (rc = ensure(c, sf.p_act, (size_t)H * cs)) || (rc = ensure(c, sf.p_edge, (size_t)H * cs)) ||
-        (rc = ensure(c, sf.p_chi, (size_t)H * cs)))
-        return rc;
+    const size_t HC = (size_t)H * cs, HK = (size_t)H * ks;
+    if ((rc = ensure(c, c->sf.l_list, HK * kCQ)) || (rc = ensure(c, c->ex.err, 4)) || (rc = pose_scratch(c, HC))) return rc;
     hipStream_t s = main_stream(c);
-    Pack pk;
+    Staged st;
     // H rows of `stride` elements, row h holding cnt(h) of them (the rest zero)
     auto rows = [&](auto ptr_of, auto cnt_of, size_t stride, size_t elem) {
-        const size_t o = pk.total;
+        const size_t o = st.pk.total;
         for (int h = 0; h < H; h++) {
             const size_t nb = (size_t)cnt_of(h) * elem;
-            pk.add(nb ? ptr_of(h) : nullptr, nb);
-            pk.fill(0, stride * elem - ((nb + 15) & ~(size_t)15));
+            st.add(nb ? ptr_of(h) : nullptr, nb);
+            st.fill(0, stride * elem - ((nb + 15) & ~(size_t)15));
         }
         return o;
     };
@@ -1645,9 +1646,8 @@ int coeb_reloc_refine(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe* 
         memcpy(T0 + 16 * h, hyp[h].Tcw, 64);
     }
     cnt0[4 * H] = H;                                // first_good: none
-    const size_t o_k = pk.add(cur->keys_un, (size_t)n * sizeof(coeb_keypoint)), o_d = pk.add(cur->descriptors, (size_t)n * 32);
-    const size_t o_ur = pk.add(cur->u_right, (size_t)n * 4), o_is = pk.add(c->tab.inv_sigma2, sizeof(float) * COEB_MAXL);
-    const size_t o_kn = pk.add(kfn, (size_t)H * 4);
+    const CurOff o_c = pack_cur(st, cur);
+    const size_t o_is = st.add(c->tab.inv_sigma2, sizeof(float) * COEB_MAXL), o_kn = st.add(kfn, (size_t)H * 4);
     const size_t o_mi = rows([&](int h) { return (const void*)hyp[h].match; }, all_n, cs, 4);
     const size_t o_in = rows([&](int h) { return (const void*)hyp[h].inlier; }, all_n, cs, 1);
     const size_t o_v = rows([&](int h) { return (const void*)hyp[h].kf.valid; }, kf_n, ks, 1);
@@ -1657,47 +1657,40 @@ int coeb_reloc_refine(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe* 
     const size_t o_mn = rows([&](int h) { return (const void*)hyp[h].kf.min_distance; }, kf_n, ks, 4);
     const size_t o_a = rows([&](int h) { return (const void*)hyp[h].kf.angle; }, kf_n, ks, 4);
     // results with an initial value: {stage, ngood, nadditional1, nadditional2} per hypothesis, first_good, the poses
-    const size_t o_cnt = pk.add(cnt0, ((size_t)4 * H + 4) * 4), o_T = pk.add(T0, (size_t)H * 64);
-    // results the kernels write (not uploaded), then scratch
-    size_t at = pk.total;
-    auto take = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 15) & ~(size_t)15; return o; };
-    const size_t HC = (size_t)H * cs, HK = (size_t)H * ks;
-    const size_t o_held = take(HC * 4), o_oo = take(HC);
-    const size_t back_end = at;
-    const size_t o_has = take(HC), o_px = take(HC * 12), o_out = take(HC), o_ao = take(HC);
-    const size_t o_kh = take(HC * sizeof(coeb_keypoint)), o_uh = take(HC * 4);
-    const size_t o_f = take(HK), o_vs = take(HK), o_sm = take(HC * 4), o_snm = take((size_t)H * 4);
-    const size_t o_act = take((size_t)2 * H), o_pn = take((size_t)3 * H * 4), o_pr = take((size_t)3 * H * 4);
-    const size_t o_path = take((size_t)2 * H * 4);
-    const size_t o_err = at;
-    if ((rc = pinned(c, o_err + 16)) || (rc = ensure(c, c->ex.stage, at)) || (rc = stage_in(c, pk, &dbase, s))) return rc;
+    const size_t o_cnt = st.add(cnt0, ((size_t)4 * H + 4) * 4), o_T = st.add(T0, (size_t)H * 64);
+    // results the kernels write (the held indices, the packed outlier flags), then scratch
+    const size_t o_held = st.take(HC * 4), o_oo = st.take(HC);
+    const size_t back_end = st.end();
+    const size_t o_has = st.take(HC), o_px = st.take(HC * 12), o_out = st.take(HC), o_ao = st.take(HC);
+    const size_t o_kh = st.take(HC * sizeof(coeb_keypoint)), o_uh = st.take(HC * 4);
+    const size_t o_f = st.take(HK), o_vs = st.take(HK), o_sm = st.take(HC * 4), o_snm = st.take((size_t)H * 4);
+    const size_t o_act = st.take((size_t)2 * H), o_pn = st.take((size_t)3 * H * 4), o_pr = st.take((size_t)3 * H * 4);
+    const size_t o_path = st.take((size_t)2 * H * 4);
+    if ((rc = st.stage(c, s, true))) return rc;
     RrBufs r;
     r.nhyp = H; r.cur_n = n; r.cs = cs; r.ks = ks;
     r.min_good = min_good; r.low_good = low_good; r.enough_good = enough_good;
-    r.kps = dbase + o_k; r.ur = (const float*)(dbase + o_ur);
-    r.match_in = (const int*)(dbase + o_mi); r.inlier = dbase + o_in;
-    r.kf_n = (const int*)(dbase + o_kn); r.kf_valid = dbase + o_v; r.kf_xw = (const float*)(dbase + o_x);
-    r.held = (int*)(dbase + o_held); r.has = dbase + o_has; r.xw = (float*)(dbase + o_px); r.outl = dbase + o_out;
-    r.at_opt = dbase + o_ao; r.kps_h = dbase + o_kh; r.ur_h = (float*)(dbase + o_uh);
-    r.found = dbase + o_f; r.valid_s = dbase + o_vs; r.smatch = (const int*)(dbase + o_sm); r.snm = (const int*)(dbase + o_snm);
-    r.active = dbase + o_act; r.pose_n = (int*)(dbase + o_pn); r.pose_res = (const int*)(dbase + o_pr);
-    r.cnt = (int*)(dbase + o_cnt); r.first_good = r.cnt + 4 * H; r.outl_out = dbase + o_oo;
+    r.kps = st.dev<void>(o_c.k); r.ur = st.dev<float>(o_c.ur);
+    r.match_in = st.dev<int>(o_mi); r.inlier = st.dev<uint8_t>(o_in);
+    r.kf_n = st.dev<int>(o_kn); r.kf_valid = st.dev<uint8_t>(o_v); r.kf_xw = st.dev<float>(o_x);
+    r.held = st.dev<int>(o_held); r.has = st.dev<uint8_t>(o_has); r.xw = st.dev<float>(o_px); r.outl = st.dev<uint8_t>(o_out);
+    r.at_opt = st.dev<uint8_t>(o_ao); r.kps_h = st.dev<void>(o_kh); r.ur_h = st.dev<float>(o_uh);
+    r.found = st.dev<uint8_t>(o_f); r.valid_s = st.dev<uint8_t>(o_vs); r.smatch = st.dev<int>(o_sm); r.snm = st.dev<int>(o_snm);
+    r.active = st.dev<uint8_t>(o_act); r.pose_n = st.dev<int>(o_pn); r.pose_res = st.dev<int>(o_pr);
+    r.cnt = st.dev<int>(o_cnt); r.first_good = r.cnt + 4 * H; r.outl_out = st.dev<uint8_t>(o_oo);
     const MatchCam mc = make_cam(c, cam);
     auto pose = [&](int k) {                        // the k-th PoseOptimization: F = nhyp, gated by pose_n[k][h] = 0
-        PoseBufs p;
-        p.n = r.pose_n + k * H; p.has_mp = r.has; p.xw = r.xw; p.kps = r.kps_h; p.ur = r.ur_h;
-        p.inv_sigma2 = (const float*)(dbase + o_is); p.Tcw = (float*)(dbase + o_T); p.outlier = r.outl;
-        p.result = (int*)(dbase + o_pr) + k * H; p.edges = sf.p_edge.p; p.active = sf.p_act.p; p.chi2 = sf.p_chi.p;
-        p.stride = cs; p.timing = nullptr;
+        const PoseBufs p = pose_bufs(c, r.pose_n + k * H, r.has, r.xw, r.kps_h, r.ur_h, st.dev<float>(o_is), st.dev<float>(o_T),
+                                     r.outl, st.dev<int>(o_pr) + k * H, cs);
         return launch_pose(p, H, cam->fx, cam->fy, cam->cx, cam->cy, cam->bf, s, &c->hook);
     };
     auto search = [&](int k, float th, int orb_dist) {
         KfBufs b;
-        b.cur_kps = dbase + o_k; b.cur_desc = dbase + o_d; b.cur_has = r.has; b.cur_n = n;
-        b.valid = r.valid_s; b.xw = r.kf_xw; b.desc = dbase + o_qd; b.maxd = (const float*)(dbase + o_mx);
-        b.mind = (const float*)(dbase + o_mn); b.angle = (const float*)(dbase + o_a); b.kf_n = kmax;
-        b.Tcw = (const float*)(dbase + o_T); b.match = (int*)(dbase + o_sm); b.nmatch = (int*)(dbase + o_snm);
-        b.lists = sf.l_list.p; b.err = c->ex.err.p; b.path = (int*)(dbase + o_path);
+        b.cur_kps = r.kps; b.cur_desc = st.dev<uint8_t>(o_c.d); b.cur_has = r.has; b.cur_n = n;
+        b.valid = r.valid_s; b.xw = r.kf_xw; b.desc = st.dev<uint8_t>(o_qd); b.maxd = st.dev<float>(o_mx);
+        b.mind = st.dev<float>(o_mn); b.angle = st.dev<float>(o_a); b.kf_n = kmax;
+        b.Tcw = st.dev<float>(o_T); b.match = st.dev<int>(o_sm); b.nmatch = st.dev<int>(o_snm);
+        b.lists = c->sf.l_list.p; b.err = c->ex.err.p; b.path = st.dev<int>(o_path);
         b.kf_n_arr = r.kf_n; b.active = r.active + k * H; b.cur_stride = cs; b.kf_stride = ks; b.npairs = H;
         return launch_match_kf(mc, b, th, orb_dist, check_orientation ? 1 : 0, s, &c->hook);
     };
@@ -1705,17 +1698,14 @@ int coeb_reloc_refine(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe* 
         launch_rr_merge(r, 1, s, &c->hook) || pose(1) || launch_rr_after2(r, s, &c->hook) || search(1, th2, orb_dist2) ||
         launch_rr_merge(r, 2, s, &c->hook) || pose(2) || launch_rr_tail(r, s, &c->hook))
         return hip_err(c, hipGetLastError(), "coeb_reloc_refine launch");
-    HIP_TRY(c, hipMemcpyAsync(c->pin + o_cnt, dbase + o_cnt, back_end - o_cnt, hipMemcpyDeviceToHost, s));
-    if ((rc = err_word_async(c, c->pin + o_err))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if ((rc = err_word_seen(c, c->pin + o_err))) return rc;
-    const int32_t* hc = reinterpret_cast<const int32_t*>(c->pin + o_cnt);
+    if ((rc = st.finish(c, s, o_cnt, back_end, true))) return rc;
+    const int32_t* hc = st.host<int32_t>(o_cnt);
     for (int h = 0; h < H; h++) {
         stage[h] = hc[4 * h]; ngood[h] = hc[4 * h + 1]; nadditional1[h] = hc[4 * h + 2]; nadditional2[h] = hc[4 * h + 3];
-        memcpy(hyp[h].Tcw, c->pin + o_T + (size_t)h * 64, 64);
-        memcpy(match_out + (size_t)h * n, c->pin + o_held + (size_t)h * cs * 4, (size_t)n * 4);
+        memcpy(hyp[h].Tcw, st.pin + o_T + (size_t)h * 64, 64);
+        memcpy(match_out + (size_t)h * n, st.pin + o_held + (size_t)h * cs * 4, (size_t)n * 4);
         if (outlier_out) {                          // written where the keypoint held a point at the last optimisation run
-            const uint8_t* fl = c->pin + o_oo + (size_t)h * cs;
+            const uint8_t* fl = st.pin + o_oo + (size_t)h * cs;
             for (int i = 0; i < n; i++)
                 if (fl[i] != 2) outlier_out[(size_t)h * n + i] = fl[i];
         }

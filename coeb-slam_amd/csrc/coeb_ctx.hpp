@@ -277,6 +277,35 @@ int pinned(coeb_ctx* c, size_t bytes);          // the page-locked buffer holds 
 // pack -> pinned -> one H2D copy into the "stage" device buffer; *dbase = its device address
 int stage_in(coeb_ctx* c, const Pack& pk, uint8_t** dbase, hipStream_t s);
 
+// The staged region of one single-frame tracking call, at the same offsets of the "stage" device
+// buffer and of the page-locked buffer: the packed inputs (uploaded in one copy; results that have
+// an initial value are uploaded with them), then what take() hands out behind them at 16-byte
+// rounded offsets -- first the results the kernels write, which finish() copies back in one piece
+// together with the uploaded results in front of them, then scratch -- and, for a call that reads
+// the device error word, the word's 16-byte slot of the page-locked buffer at the region's end.
+struct Staged {
+    Pack pk;
+    size_t at = 0;                  // the region's end once take() has been called
+    uint8_t* dbase = nullptr;       // stage(): the region on the device
+    uint8_t* pin = nullptr;         //          and its page-locked copy
+    size_t add(const void* p, size_t n) { return pk.add(p, n); }
+    size_t fill(int byte, size_t n) { return pk.fill(byte, n); }
+    size_t end() const { return std::max(at, pk.total); }
+    size_t take(size_t bytes)
+    {
+        const size_t o = end();
+        at = (o + bytes + 15) & ~(size_t)15;
+        return o;
+    }
+    template <class T> T* dev(size_t off) const { return reinterpret_cast<T*>(dbase + off); }
+    template <class T> const T* host(size_t off) const { return reinterpret_cast<const T*>(pin + off); }
+    // both buffers sized for the region (with_err: and the error-word slot), the inputs enqueued on s
+    int stage(coeb_ctx* c, hipStream_t s, bool with_err);
+    // behind the kernels: one D2H copy of [from, to), the error word when asked, the call's one
+    // synchronisation, and the verdict on the word
+    int finish(coeb_ctx* c, hipStream_t s, size_t from, size_t to, bool with_err);
+};
+
 // coeb_bow.hip, called by coeb_capi.hip (coeb_track_reference_keyframe): Frame::ComputeBoW's transform and
 // SearchByBoW on device arrays.  launch_transform: descriptor i of frame f at d_desc + (f * stride + i) * 32,
 // d_counts ? d_counts[f] : n_fixed of them; d_word / d_node [F][stride].

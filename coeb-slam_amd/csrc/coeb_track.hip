@@ -545,69 +545,42 @@ int launch_rr_after2(const RrBufs& r, hipStream_t s, ProfileHook* prof) { COEB_R
 int launch_rr_tail(const RrBufs& r, hipStream_t s, ProfileHook* prof) { COEB_RR_LAUNCH(k_rr_tail, r); }
 #undef COEB_RR_LAUNCH
 
-int launch_mm_tail(const TrkBufs& t, hipStream_t s, ProfileHook* prof)
+// One kT-thread workgroup per kT of `count` elements; nothing to do (0) when there are none.  `name` is
+// the kernel's key in coeb_profile_read.
+template <class K, class... A>
+int launch_1d(const char* name, K kernel, int count, size_t lds, hipStream_t s, ProfileHook* prof, const A&... args)
 {
-    if (t.cur_n <= 0) return 0;                     // nothing can match: nmatches and nmap stay 0
-    prof_begin(prof, "k_mm_tail", s);
-    hipLaunchKernelGGL(k_mm_tail, dim3((t.cur_n + kT - 1) / kT), dim3(kT), 0, s, t);
+    if (count <= 0) return 0;
+    prof_begin(prof, name, s);
+    hipLaunchKernelGGL(kernel, dim3((count + kT - 1) / kT), dim3(kT), lds, s, args...);
     prof_end(prof, s);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+// without keypoints the counts these kernels accumulate (nmatches, nmap, pose_n, ninl) stay 0, as uploaded;
+// without local-map points so does n_to_match
+int launch_mm_tail(const TrkBufs& t, hipStream_t s, ProfileHook* prof) { return launch_1d("k_mm_tail", k_mm_tail, t.cur_n, 0, s, prof, t); }
+int launch_frustum(const MatchCam& cam, const LmBufs& t, hipStream_t s, ProfileHook* prof)
+{
+    return launch_1d("k_frustum", k_frustum, t.mp_n, 0, s, prof, cam, t);
+}
+int launch_lm_pose_prep(const LmBufs& t, hipStream_t s, ProfileHook* prof)
+{
+    return launch_1d("k_lm_pose_prep", k_lm_pose_prep, t.cur_n, 0, s, prof, t);
+}
+int launch_lm_tail(const LmBufs& t, hipStream_t s, ProfileHook* prof) { return launch_1d("k_lm_tail", k_lm_tail, t.cur_n, 0, s, prof, t); }
+int launch_trk_pose_prep(const TrkBufs& t, hipStream_t s, ProfileHook* prof)
+{
+    return launch_1d("k_trk_pose_prep", k_trk_pose_prep, t.cur_n, 0, s, prof, t);
+}
+int launch_trk_tail(const TrkBufs& t, hipStream_t s, ProfileHook* prof) { return launch_1d("k_trk_tail", k_trk_tail, t.cur_n, 0, s, prof, t); }
 
 int launch_vo_points(const VoBufs& v, hipStream_t s, ProfileHook* prof)
 {
     if (v.n <= 0) return 0;
     if (v.n > kVoMaxLast) return -2;
     lds_limit_max((const void*)k_vo_points);        // kVoMaxLast depths are the default limit exactly
-    prof_begin(prof, "k_vo_points", s);
-    hipLaunchKernelGGL(k_vo_points, dim3((v.n + kT - 1) / kT), dim3(kT), (size_t)((v.n + 3) & ~3) * sizeof(float), s, v);
-    prof_end(prof, s);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_frustum(const MatchCam& cam, const LmBufs& t, hipStream_t s, ProfileHook* prof)
-{
-    if (t.mp_n <= 0) return 0;                      // n_to_match stays 0
-    prof_begin(prof, "k_frustum", s);
-    hipLaunchKernelGGL(k_frustum, dim3((t.mp_n + kT - 1) / kT), dim3(kT), 0, s, cam, t);
-    prof_end(prof, s);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_lm_pose_prep(const LmBufs& t, hipStream_t s, ProfileHook* prof)
-{
-    if (t.cur_n <= 0) return 0;
-    prof_begin(prof, "k_lm_pose_prep", s);
-    hipLaunchKernelGGL(k_lm_pose_prep, dim3((t.cur_n + kT - 1) / kT), dim3(kT), 0, s, t);
-    prof_end(prof, s);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_lm_tail(const LmBufs& t, hipStream_t s, ProfileHook* prof)
-{
-    if (t.cur_n <= 0) return 0;                     // ninl stays 0
-    prof_begin(prof, "k_lm_tail", s);
-    hipLaunchKernelGGL(k_lm_tail, dim3((t.cur_n + kT - 1) / kT), dim3(kT), 0, s, t);
-    prof_end(prof, s);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_trk_pose_prep(const TrkBufs& t, hipStream_t s, ProfileHook* prof)
-{
-    if (t.cur_n <= 0) return 0;                     // pose_n stays 0
-    prof_begin(prof, "k_trk_pose_prep", s);
-    hipLaunchKernelGGL(k_trk_pose_prep, dim3((t.cur_n + kT - 1) / kT), dim3(kT), 0, s, t);
-    prof_end(prof, s);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_trk_tail(const TrkBufs& t, hipStream_t s, ProfileHook* prof)
-{
-    if (t.cur_n <= 0) return 0;                     // nmatches and nmap stay 0
-    prof_begin(prof, "k_trk_tail", s);
-    hipLaunchKernelGGL(k_trk_tail, dim3((t.cur_n + kT - 1) / kT), dim3(kT), 0, s, t);
-    prof_end(prof, s);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launch_1d("k_vo_points", k_vo_points, v.n, (size_t)((v.n + 3) & ~3) * sizeof(float), s, prof, v);
 }
 
 int launch_tlm_snapshot(const TlmBufs& t, int F, hipStream_t s, ProfileHook* prof)
