@@ -1,7 +1,8 @@
 /*
  * Frame_coeb.h -- MI355X body for Frame::ProcessMovingObject(const cv::Mat &imgray,
  * std::vector<std::vector<float>> &box) (include/Frame.h, src/Frame.cc:311-393), and
- * coeb::FrameRGBD, the RGB-D constructor's tail (src/Frame.cc:214-223; at the end of this file).
+ * coeb::FrameRGBD, the RGB-D constructor's tail (src/Frame.cc:214-223), and coeb::FrameRGBDStream, the whole
+ * constructor on a stream of frames (:157-223), at the end of this file.
  *
  * Included from the reference's src/Frame.cc; the member function body becomes
  *
@@ -98,6 +99,42 @@ inline void FrameRGBD(FrameT& F, ExtractorT* extractor, const cv::Mat& imGray, c
     extractor->ExtractRGBD(imGray, imDepth, F.mK, F.mDistCoef, F.mbf, box, T_M, blur_flag, F.mvKeys, F.mDescriptors,
                            F.mvKeysUn, F.mvuRight, F.mvDepth);
     F.N = (int)F.mvKeys.size();
+}
+
+/* The whole RGB-D constructor on a stream of frames: src/Frame.cc:157-223
+ *
+ *     if(imGrayPre.data) { ProcessMovingObject(imGray,box); ... blur_flag per box ... } else { flags 0 }
+ *     imGrayPre = imGray.clone();
+ *     ExtractORB(0,imGray,img,imDepth,box,T_M,mask_result,blur_flag);
+ *     N = mvKeys.size(); if(mvKeys.empty()) return;
+ *     UndistortKeyPoints(); ComputeStereoFromRGBD(imDepth);
+ *
+ * collapses to
+ *
+ *     coeb::FrameRGBDStream(*this, mpORBextractorLeft, imGray, imDepth, box, T_M, blur_flag);
+ *     if(mvKeys.empty()) return;
+ *
+ * one device call (ORBextractor::ExtractRGBDStream -> coeb_rgbd_stream_frame).  T_M and blur_flag are
+ * filled here.  The previous frame lives on the device, in a stream kept with the extractor's pooled
+ * context, so the file-scope imGrayPre is no longer read or written.  The first frame of a thread,
+ * the first after coeb::FrameStreamReset (called from Tracking::Reset), the first after a change of
+ * frame size and the first handed to ANOTHER extractor than the frame before (Tracking's adaptive
+ * nFeatures switch) are first frames: T_M empty, every flag 0 (:205-209).
+ */
+template <class FrameT, class ExtractorT>
+inline void FrameRGBDStream(FrameT& F, ExtractorT* extractor, const cv::Mat& imGray, const cv::Mat& imDepth,
+                            std::vector<std::vector<float>>& box, std::vector<cv::Point2f>& T_M, std::vector<int>& blur_flag)
+{
+    extractor->ExtractRGBDStream(imGray, imDepth, F.mK, F.mDistCoef, F.mbf, box, T_M, blur_flag, F.mvKeys, F.mDescriptors,
+                                 F.mvKeysUn, F.mvuRight, F.mvDepth);
+    F.N = (int)F.mvKeys.size();
+}
+
+/* Tracking::Reset (Tracking.cc, on the tracking thread): `coeb::FrameStreamReset(mpORBextractorLeft);` */
+template <class ExtractorT>
+inline void FrameStreamReset(ExtractorT*)
+{
+    ExtractorT::ResetFrameStreams();
 }
 
 }  // namespace coeb

@@ -80,6 +80,7 @@ ABI_SYMBOLS = [
     "coeb_kfdb_size", "coeb_kfdb_query", "coeb_match_bow_kfdb",
     "coeb_search_local_points", "coeb_track_local_map", "coeb_track_reference_keyframe",
     "coeb_track_motion_model", "coeb_reloc_refine",
+    "coeb_rgbd_stream_create", "coeb_rgbd_stream_destroy", "coeb_rgbd_stream_reset", "coeb_rgbd_stream_frame",
 ]
 # COEB_ABI_VERSION of the include/coeb_front.h these argtypes are written against; lib() refuses
 # a library that reports another (tests/test_capi_symbols.py keeps the two equal)
@@ -170,6 +171,17 @@ class BowFrameC(C.Structure):
 class KfdbKeyFrameC(C.Structure):
     _fields_ = [("n", C.c_int32), ("descriptor", C.c_void_p), ("node_id", C.c_void_p), ("angle", C.c_void_p),
                 ("bow_word", C.c_void_p), ("bow_value", C.c_void_p), ("nw", C.c_int32)]
+
+
+class RgbdStreamOutC(C.Structure):
+    _fields_ = [("tm_xy", C.c_void_p), ("tm_cap", C.c_int), ("n_tm", C.c_int), ("blur_flag", C.c_void_p),
+                ("gray", C.c_void_p), ("gray_stride", C.c_size_t), ("kp", C.c_void_p), ("kp_un", C.c_void_p),
+                ("desc", C.c_void_p), ("u_right", C.c_void_p), ("depth", C.c_void_p), ("cap", C.c_int), ("n", C.c_int),
+                ("first", C.c_int)]
+
+
+STREAM_NO_SHADOW = 1    # COEB_STREAM_NO_SHADOW
+STREAM_TM_CAP = 1024    # T_M points a stream frame can return
 
 
 class CoebError(RuntimeError):
@@ -340,6 +352,13 @@ def lib():
             getattr(L, nm).argtypes = [C.c_void_p, C.c_void_p]
         L.coeb_debug_read.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t,
                                       C.POINTER(C.c_size_t)]
+        L.coeb_rgbd_stream_create.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.c_void_p)]
+        L.coeb_rgbd_stream_destroy.restype = None
+        L.coeb_rgbd_stream_destroy.argtypes = [C.c_void_p]
+        L.coeb_rgbd_stream_reset.argtypes = [C.c_void_p]
+        L.coeb_rgbd_stream_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.POINTER(Camera), C.c_void_p,
+                                             C.c_void_p, C.c_int, C.POINTER(RgbdStreamOutC)]
         _lib = L
     return _lib
 
@@ -874,6 +893,72 @@ class HostBuffer:
             self.free()
         except Exception:
             pass
+
+
+class RGBDStream:
+    """The RGB-D Frame constructor (Frame.cc:157-223) on a stream of frames: one coeb_rgbd_stream.
+    frame() takes the image as GrabImageRGBD receives it -- (H, W) gray, (H, W, 3) or (H, W, 4)
+    u8, strided rows allowed -- and returns dict(tm, n_tm, blur, gray, kps, kps_un, desc, u_right,
+    depth, first): ProcessMovingObject against the previous frame, the blur flag of every box, the
+    extraction with both, UndistortKeyPoints and ComputeStereoFromRGBD in one call.  n_tm = -1: the
+    fundamental matrix was empty (tm is then empty, the frame extracted without T_M).  shadow=False
+    runs the previous-frame-only work inside the next call (COEB_STREAM_NO_SHADOW).  close() before
+    the context is closed."""
+
+    def __init__(self, ctx, shadow=True):
+        self.ctx = ctx
+        h = C.c_void_p()
+        ctx.check(lib().coeb_rgbd_stream_create(ctx.h, 0 if shadow else STREAM_NO_SHADOW, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            lib().coeb_rgbd_stream_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        self.ctx.check(lib().coeb_rgbd_stream_reset(self.h))
+
+    def frame(self, img, depth, cam, dist=None, boxes=None, depth_scale=1.0, rgb_order=True, want_gray=True):
+        img = np.asarray(img)
+        if img.dtype != np.uint8 or img.ndim not in (2, 3) or img.strides[1] != (1 if img.ndim == 2 else img.shape[2]) or \
+                (img.ndim == 3 and img.strides[2] != 1):
+            img = np.ascontiguousarray(img, np.uint8)
+        h, w = img.shape[:2]
+        ch = 1 if img.ndim == 2 else img.shape[2]
+        depth = np.asarray(depth)
+        if depth.shape != (h, w) or depth.dtype not in (np.uint16, np.float32):
+            raise ValueError("depth must be (H, W) uint16 or float32")
+        if depth.strides[1] != depth.itemsize:
+            depth = np.ascontiguousarray(depth)
+        dtype = DEPTH_F32 if depth.dtype == np.float32 else DEPTH_U16
+        d = None
+        if dist is not None:
+            d = np.zeros(5, np.float32)
+            d[:len(dist)] = np.asarray(dist, np.float32)
+        boxes = None if boxes is None else np.ascontiguousarray(boxes, np.float32)
+        nb = 0 if boxes is None else len(boxes)
+        cap = self.ctx.max_keypoints(w, h)
+        kps, kun = np.empty(cap, KEYPOINT_DTYPE), np.empty(cap, KEYPOINT_DTYPE)
+        desc = np.empty((cap, 32), np.uint8)
+        ur, dep = np.empty(cap, np.float32), np.empty(cap, np.float32)
+        tm = np.empty((STREAM_TM_CAP, 2), np.float32)
+        blur = np.empty(max(nb, 1), np.int32)
+        gray = np.empty((h, w), np.uint8) if want_gray else None
+        o = RgbdStreamOutC(_p(tm), STREAM_TM_CAP, 0, _p(blur), _p(gray), w, _p(kps), _p(kun), _p(desc), _p(ur), _p(dep),
+                           cap, 0, 0)
+        self.ctx.check(lib().coeb_rgbd_stream_frame(self.h, _p(img), img.strides[0], ch, 1 if rgb_order else 0, w, h,
+                                                    _p(depth), depth.strides[0], dtype, C.c_float(depth_scale),
+                                                    C.byref(cam), _p(d), _p(boxes) if nb else None, nb, C.byref(o)))
+        n = o.n
+        return dict(tm=tm[:max(o.n_tm, 0)], n_tm=o.n_tm, blur=blur[:nb], gray=gray, kps=kps[:n], kps_un=kun[:n],
+                    desc=(desc[:n] if n else None), u_right=ur[:n], depth=dep[:n], first=bool(o.first))
 
 
 def UndistortKeyPoints(ctx, keys, camera, dist):

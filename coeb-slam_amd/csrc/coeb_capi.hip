@@ -16,6 +16,7 @@
 
 #include "coeb_ctx.hpp"
 #include "coeb_single_frame_host.hpp"
+#include "coeb_rgbd_stream_host.hpp"
 
 static const int8_t kPattern[1024] = {
 #include "../../data/orb_bit_pattern_31.inc"
@@ -993,6 +994,55 @@ int coeb_extract(coeb_ctx* c, const uint8_t* gray, int W, int H, size_t stride, 
     return COEB_OK;
 }
 
+namespace {
+// Where k_frame_tail's results and the depth rows it gathers from lie in the page-locked buffer
+// (FrameRgbdLayout and RgbdStreamLayout both have these regions).
+struct TailRegions { size_t o_n, o_k, o_d, o_kun, o_ur, o_dep, o_depth; };
+
+// k_frame_tail behind the extraction b left on stream s, for coeb_frame_rgbd and coeb_rgbd_stream_frame;
+// *guess = the records it packs (frame_rgbd_guess)
+int launch_frame_tail(coeb_ctx* c, hipStream_t s, const ExtractBufs& b, const TailRegions& R, int kcap, int cap, bool want_kun,
+                      int W, int H, int depth_type, float depth_scale, const coeb_camera* cam, const float dist[5], int* guess)
+{
+    FrameTail a;
+    memset(&a, 0, sizeof(a));
+    a.counts = b.counts; a.kps = static_cast<const uint32_t*>(b.kps); a.desc = reinterpret_cast<const uint4*>(b.desc);
+    a.guess = *guess = frame_rgbd_guess(kcap, cap);
+    a.out_n = reinterpret_cast<int*>(c->pin_dev + R.o_n);
+    a.out_k = reinterpret_cast<uint32_t*>(c->pin_dev + R.o_k);
+    a.out_d = reinterpret_cast<uint4*>(c->pin_dev + R.o_d);
+    a.out_kun = want_kun ? reinterpret_cast<uint32_t*>(c->pin_dev + R.o_kun) : nullptr;
+    a.out_ur = reinterpret_cast<float*>(c->pin_dev + R.o_ur);
+    a.out_dep = reinterpret_cast<float*>(c->pin_dev + R.o_dep);
+    a.depth = c->pin_dev + R.o_depth;
+    a.W = W; a.H = H;
+    a.depth_u16 = depth_type == COEB_DEPTH_U16;
+    a.depth_copy = frame_rgbd_depth_copy(depth_type, depth_scale);
+    a.depth_scale = depth_scale;
+    a.bf = cam->bf;
+    a.undistort = dist && dist[0] != 0.0f;                  // Frame.cc:581-585
+    for (int q = 0; q < 12; q++) a.dist.k[q] = (a.undistort && q < 5) ? (double)dist[q] : 0.0;
+    a.dist.fx = cam->fx; a.dist.fy = cam->fy; a.dist.cx = cam->cx; a.dist.cy = cam->cy;
+    prof_begin(&c->hook, "k_frame_tail", s);
+    hipLaunchKernelGGL(k_frame_tail, dim3(16), dim3(256), 0, s, a);
+    prof_end(&c->hook, s);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+// the first m records of every output, from the page-locked buffer to the caller's arrays
+void frame_tail_copy_out(const coeb_ctx* c, const TailRegions& R, int m, coeb_keypoint* kp, coeb_keypoint* kp_un, uint8_t* desc,
+                         float* u_right, float* depth)
+{
+    if (m <= 0) return;
+    memcpy(kp, c->pin + R.o_k, (size_t)m * sizeof(coeb_keypoint));
+    memcpy(desc, c->pin + R.o_d, (size_t)m * 32);
+    if (kp_un) memcpy(kp_un, c->pin + R.o_kun, (size_t)m * sizeof(coeb_keypoint));
+    memcpy(u_right, c->pin + R.o_ur, (size_t)m * 4);
+    memcpy(depth, c->pin + R.o_dep, (size_t)m * 4);
+}
+}  // namespace
+
 int coeb_frame_rgbd(coeb_ctx* c, const uint8_t* gray, int W, int H, size_t stride, const void* depth, size_t depth_stride,
                     int depth_type, float depth_scale, const coeb_camera* cam, const float dist[5], const coeb_box* boxes,
                     int nbox, const float* tm_xy, int ntm, const int32_t* blur_flag, int nblur, coeb_keypoint* kp_out,
@@ -1020,42 +1070,263 @@ int coeb_frame_rgbd(coeb_ctx* c, const uint8_t* gray, int W, int H, size_t strid
     // half the bytes, and only the gathered values are ever converted)
     single_frame_stage_rows(c->pin + L.o_depth, depth, H, L.depth_row, depth_stride);
     // 3. the tail kernel behind the extraction
-    FrameTail a;
-    memset(&a, 0, sizeof(a));
-    a.counts = b.counts; a.kps = static_cast<const uint32_t*>(b.kps); a.desc = reinterpret_cast<const uint4*>(b.desc);
-    a.guess = frame_rgbd_guess(kcap, cap);
-    a.out_n = reinterpret_cast<int*>(c->pin_dev + L.o_n);
-    a.out_k = reinterpret_cast<uint32_t*>(c->pin_dev + L.o_k);
-    a.out_d = reinterpret_cast<uint4*>(c->pin_dev + L.o_d);
-    a.out_kun = kp_un_out ? reinterpret_cast<uint32_t*>(c->pin_dev + L.o_kun) : nullptr;
-    a.out_ur = reinterpret_cast<float*>(c->pin_dev + L.o_ur);
-    a.out_dep = reinterpret_cast<float*>(c->pin_dev + L.o_dep);
-    a.depth = c->pin_dev + L.o_depth;
-    a.W = W; a.H = H;
-    a.depth_u16 = depth_type == COEB_DEPTH_U16;
-    a.depth_copy = frame_rgbd_depth_copy(depth_type, depth_scale);
-    a.depth_scale = depth_scale;
-    a.bf = cam->bf;
-    a.undistort = dist && dist[0] != 0.0f;                  // Frame.cc:581-585
-    for (int q = 0; q < 12; q++) a.dist.k[q] = (a.undistort && q < 5) ? (double)dist[q] : 0.0;
-    a.dist.fx = cam->fx; a.dist.fy = cam->fy; a.dist.cx = cam->cx; a.dist.cy = cam->cy;
-    prof_begin(&c->hook, "k_frame_tail", s);
-    hipLaunchKernelGGL(k_frame_tail, dim3(16), dim3(256), 0, s, a);
-    prof_end(&c->hook, s);
-    HIP_TRY(c, hipGetLastError());
+    const TailRegions R{L.o_n, L.o_k, L.o_d, L.o_kun, L.o_ur, L.o_dep, L.o_depth};
+    int guess = 0;
+    if ((rc = launch_frame_tail(c, s, b, R, kcap, cap, kp_un_out != nullptr, W, H, depth_type, depth_scale, cam, dist, &guess)))
+        return rc;
     // 4. the error word, and the call's one synchronisation
     int n = 0;
     if ((rc = finish_single_frame(c, L, s, &n))) return rc;
     *n_out = n;
-    const int m = std::min(n, a.guess);                    // guess = min(kcap, cap) and n <= kcap
-    if (m > 0) {
-        memcpy(kp_out, c->pin + L.o_k, (size_t)m * sizeof(coeb_keypoint));
-        memcpy(desc_out, c->pin + L.o_d, (size_t)m * 32);
-        if (kp_un_out) memcpy(kp_un_out, c->pin + L.o_kun, (size_t)m * sizeof(coeb_keypoint));
-        memcpy(u_right_out, c->pin + L.o_ur, (size_t)m * 4);
-        memcpy(depth_out, c->pin + L.o_dep, (size_t)m * 4);
-    }
+    // guess = min(kcap, cap) and n <= kcap
+    frame_tail_copy_out(c, R, std::min(n, guess), kp_out, kp_un_out, desc_out, u_right_out, depth_out);
     if (n > cap) return set_err(c, COEB_ERANGE, "keypoint output capacity too small");
+    return COEB_OK;
+}
+
+// ---- the RGB-D Frame constructor on a stream of frames (Frame.cc:157-223) ----
+// The object owns one device allocation (coeb_rgbd_stream_host.hpp): two slots that take the frames
+// by parity, then the scratch of the corner work and of the LK / fundamental-matrix step; a HIP
+// stream for the previous-frame-only work and the two events that order it against the context
+// stream.  Nothing of it lies in the context's flow scratch, so other calls on the context and
+// other streams leave it alone; what a call shares with them (the page-locked buffer, the stage
+// buffer, the extraction's buffers) is free again when the call returns, after its one
+// synchronisation.
+struct coeb_rgbd_stream {
+    coeb_ctx* c = nullptr;
+    unsigned flags = 0;
+    hipStream_t shadow = nullptr;
+    hipEvent_t ev_pyr = nullptr, ev_shadow = nullptr;
+    bool shadow_recorded = false;      // ev_shadow marks the end of the corner work enqueued last
+    uint8_t* mem = nullptr;
+    int w = 0, h = 0;                  // the frame size mem is laid out for
+    RgbdStreamSlot slot{};
+    size_t o_corner = 0, o_track = 0;
+    int prev_w = 0, prev_h = 0;        // the predecessor's size (0: the next frame is a first frame)
+    bool corners_due = false;          // no-shadow form: the predecessor's corner work has yet to run
+    uint64_t seq = 0;                  // frames taken so far
+};
+
+namespace {
+
+StreamFlowFrame stream_frame(const coeb_rgbd_stream* st, int slot)
+{
+    const RgbdStreamSlot& S = st->slot;
+    uint8_t* base = st->mem + (size_t)slot * S.bytes;
+    StreamFlowFrame f;
+    memset(&f, 0, sizeof(f));
+    f.gray = base + S.s_gray;
+    for (int l = 1; l < S.L; l++) f.lvl[l] = base + S.s_lvl[l];
+    for (int l = 0; l < S.L; l++) f.der[l] = base + S.s_der[l];
+    f.pts = reinterpret_cast<float*>(base + S.s_pts);
+    f.npts = reinterpret_cast<int*>(base + S.s_npts);
+    return f;
+}
+
+// the stream's memory laid out for W x H frames (a size change follows a reset: nothing is kept)
+int stream_size(coeb_rgbd_stream* st, int W, int H)
+{
+    coeb_ctx* c = st->c;
+    if (st->mem && st->w == W && st->h == H) return 0;
+    // the slot is laid out for exactly the levels the flow kernels will walk
+    if (stream_flow_levels(W, H) > kStreamLkLevels || stream_flow_levels(W, H) != rgbd_stream_slot(W, H).L)
+        return set_err(c, COEB_EINVAL, "coeb_rgbd_stream_frame: image too large");
+    if (st->mem) {
+        HIP_TRY(c, hipStreamSynchronize(st->shadow));
+        int rc = quiesce(c);
+        if (rc) return rc;
+        if (c->batch_gray >= st->mem && c->batch_gray < st->mem + st->o_track) c->batch_gray = nullptr, c->batch_frames = 0;
+        (void)hipFree(st->mem);
+        st->mem = nullptr;
+    }
+    const RgbdStreamSlot S = rgbd_stream_slot(W, H);
+    const size_t o_corner = 2 * S.bytes, o_track = o_corner + stream_flow_corner_scratch(W, H);
+    const size_t total = o_track + stream_flow_track_scratch();
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&st->mem), total);
+    if (e != hipSuccess) {
+        st->mem = nullptr;
+        return set_err(c, COEB_ENOMEM, std::string("hipMalloc rgbd stream: ") + hipGetErrorString(e));
+    }
+    st->slot = S; st->o_corner = o_corner; st->o_track = o_track; st->w = W; st->h = H;
+    st->shadow_recorded = false;
+    return stream_flow_init(c, st->mem + o_corner);
+}
+
+}  // namespace
+
+int coeb_rgbd_stream_create(coeb_ctx* c, unsigned flags, coeb_rgbd_stream** out)
+{
+    if (!c || !out || (flags & ~(unsigned)COEB_STREAM_NO_SHADOW))
+        return set_err(c, COEB_EINVAL, "coeb_rgbd_stream_create: invalid arguments");
+    *out = nullptr;
+    (void)hipSetDevice(c->device);
+    coeb_rgbd_stream* st = new coeb_rgbd_stream();
+    st->c = c;
+    st->flags = flags;
+    // the corner work yields to whatever the caller enqueues on the context stream meanwhile
+    int lo = 0, hi = 0;
+    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
+    if (hipStreamCreateWithPriority(&st->shadow, hipStreamNonBlocking, lo) != hipSuccess ||
+        hipEventCreateWithFlags(&st->ev_pyr, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&st->ev_shadow, hipEventDisableTiming) != hipSuccess) {
+        const int rc = hip_err(c, hipGetLastError(), "coeb_rgbd_stream_create");
+        coeb_rgbd_stream_destroy(st);
+        return rc ? rc : COEB_EDEVICE;
+    }
+    *out = st;
+    return COEB_OK;
+}
+
+void coeb_rgbd_stream_destroy(coeb_rgbd_stream* st)
+{
+    if (!st) return;
+    coeb_ctx* c = st->c;
+    (void)hipSetDevice(c->device);
+    if (st->shadow) (void)hipStreamSynchronize(st->shadow);
+    if (st->mem) {
+        (void)quiesce(c);
+        if (c->batch_gray >= st->mem && c->batch_gray < st->mem + st->o_track) c->batch_gray = nullptr, c->batch_frames = 0;
+        (void)hipFree(st->mem);
+    }
+    if (st->ev_pyr) (void)hipEventDestroy(st->ev_pyr);
+    if (st->ev_shadow) (void)hipEventDestroy(st->ev_shadow);
+    if (st->shadow) (void)hipStreamDestroy(st->shadow);
+    delete st;
+}
+
+int coeb_rgbd_stream_reset(coeb_rgbd_stream* st)
+{
+    if (!st) return set_err(nullptr, COEB_EINVAL, "coeb_rgbd_stream_reset: null stream");
+    st->prev_w = st->prev_h = 0;
+    st->corners_due = false;
+    return COEB_OK;
+}
+
+int coeb_rgbd_stream_frame(coeb_rgbd_stream* st, const uint8_t* img, size_t img_stride, int channels, int rgb_order, int W,
+                           int H, const void* depth, size_t depth_stride, int depth_type, float depth_scale,
+                           const coeb_camera* cam, const float dist[5], const coeb_box* boxes, int nbox,
+                           coeb_rgbd_stream_out* out)
+{
+    if (!st) return set_err(nullptr, COEB_EINVAL, "coeb_rgbd_stream_frame: null stream");
+    coeb_ctx* c = st->c;
+    const char* why = "";
+    int rc = rgbd_stream_check(img, img_stride, channels, W, H, depth, depth_stride, depth_type, cam, boxes, nbox, out,
+                               st->prev_w, st->prev_h, &why);
+    if (rc == 1) {                                          // _image.empty() -> return (:1096-1097)
+        out->n = 0; out->n_tm = 0; out->first = st->prev_w == 0;
+        return COEB_OK;
+    }
+    if (rc) return set_err(c, rc, std::string("coeb_rgbd_stream_frame: ") + why);
+    (void)hipSetDevice(c->device);
+    if ((rc = ensure_plan(c, W, H))) return rc;
+    const int kcap = c->plan.kcap;
+    const RgbdStreamLayout L = rgbd_stream_layout(W, H, channels, kcap, depth_type);
+    // everything that may allocate, before anything is enqueued: the page-locked buffer must not
+    // move afterwards, and ensure() drains the context when a buffer grows
+    ExtractBufs b;
+    if ((rc = pinned(c, L.total)) || (rc = stream_size(st, W, H)) || (rc = extract_bufs(c, 1, b)) ||
+        (channels > 1 && (rc = ensure(c, c->ex.stage, L.up_bytes))))
+        return rc;
+    hipStream_t s = main_stream(c);
+    const bool first = st->prev_w == 0;
+    const bool shadow = !(st->flags & COEB_STREAM_NO_SHADOW);
+    const int cur_slot = rgbd_stream_slot_of(st->seq), prev_slot = cur_slot ^ 1;
+    const RgbdStreamSlot& S = st->slot;
+    uint8_t* cur_base = st->mem + (size_t)cur_slot * S.bytes;
+    const StreamFlowFrame cur = stream_frame(st, cur_slot), prev = stream_frame(st, prev_slot);
+    RgbdStreamRes* res = reinterpret_cast<RgbdStreamRes*>(cur_base + S.s_res);
+    // 0. the corner work enqueued last has both slots to itself until it ends (after a reset it is
+    // the old sequence's: it still writes the slot this frame may take)
+    if (st->shadow_recorded) HIP_TRY(c, hipStreamWaitEvent(s, st->ev_shadow, 0));
+    st->shadow_recorded = false;
+    // 1. the one upload: head + image rows.  A 1-channel frame lands on its slot's head and gray
+    // level 0; a colour frame in the stage buffer, from where k_rgbd makes the gray level.
+    RgbdStreamHdr* hdr = reinterpret_cast<RgbdStreamHdr*>(c->pin + L.o_hdr);
+    memset(hdr, 0, sizeof(*hdr));
+    hdr->box_off[1] = nbox;
+    if (nbox) memcpy(hdr->box, boxes, (size_t)nbox * sizeof(coeb_box));
+    single_frame_stage_rows(c->pin + L.o_img, img, H, L.img_row, img_stride);
+    uint8_t* up = channels == 1 ? cur_base + S.s_hdr : c->ex.stage.p;
+    HIP_TRY(c, hipMemcpyAsync(up, c->pin, L.up_bytes, hipMemcpyHostToDevice, s));
+    const RgbdStreamHdr* dhdr = reinterpret_cast<const RgbdStreamHdr*>(up);
+    if (channels > 1 && launch_rgbd_gray(c, up + L.o_img, (int)L.img_row, channels, rgb_order, W, H, cur.gray, s))
+        return hip_err(c, hipGetLastError(), "k_rgbd");
+    // without a shadow stream the predecessor's corners, subpixel refinement and Scharr planes are
+    // made here, in front of the LK step that reads them
+    if (!first && st->corners_due && (rc = stream_flow_corners(c, prev, W, H, st->mem + st->o_corner, s))) return rc;
+    st->corners_due = false;
+    // 2. this frame's LK pyramid; behind it, on the stream's own HIP stream, the work the NEXT call
+    // needs of this frame alone
+    if ((rc = stream_flow_pyramid(c, cur, W, H, s))) return rc;
+    if (shadow) {
+        HIP_TRY(c, hipEventRecord(st->ev_pyr, s));
+        HIP_TRY(c, hipStreamWaitEvent(st->shadow, st->ev_pyr, 0));
+        if ((rc = stream_flow_corners(c, cur, W, H, st->mem + st->o_corner, st->shadow))) return rc;
+        HIP_TRY(c, hipEventRecord(st->ev_shadow, st->shadow));
+        st->shadow_recorded = true;
+    }
+    // 3.-5. k_lk against the predecessor, k_fm and the blur flags leave T_M, its count and the flags
+    // in the slot's result block, where the extraction reads them
+    if (!first) {
+        if ((rc = stream_flow_track(c, prev, cur, W, H, st->mem + st->o_track, res->tm, &res->ntm, kStreamTmCap, s))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(&res->ncorners, prev.npts, 4, hipMemcpyDeviceToDevice, s));
+        if (launch_blur_flags(c, cur.gray, W, H, reinterpret_cast<const float*>(dhdr->box), nbox, res->flag, s))
+            return hip_err(c, hipGetLastError(), "k_blur_flags");
+        b.tmd = res->tm; b.ntmd = &res->ntm; b.tmd_cap = kStreamTmCap;
+    }
+    // 6. the extraction (a first frame: no T_M, every flag 0, Frame.cc:205-209)
+    if (nbox) {
+        b.boxes = reinterpret_cast<const float*>(dhdr->box);
+        b.box_off = dhdr->box_off;
+        b.blurf = first ? nullptr : res->flag;
+    }
+    b.gray = cur.gray;
+    if (launch_extract(c->plan, c->pl.plan.p, b, 1, s, &c->hook, nullptr)) return hip_err(c, hipGetLastError(), "launch_extract");
+    c->batch_frames = 1;
+    c->batch_gray = cur.gray;
+    // while the device works, the host packs the depth rows the tail kernel gathers from
+    single_frame_stage_rows(c->pin + L.o_depth, depth, H, L.depth_row, depth_stride);
+    // 7. the tail kernel, as coeb_frame_rgbd launches it
+    const TailRegions R{L.o_n, L.o_k, L.o_d, L.o_kun, L.o_ur, L.o_dep, L.o_depth};
+    int guess = 0;
+    if ((rc = launch_frame_tail(c, s, b, R, kcap, out->cap, out->kp_un != nullptr, W, H, depth_type, depth_scale, cam, dist,
+                                &guess)))
+        return rc;
+    // 8. one copy back -- the gray level the kernels made, when asked for, and the result block
+    // behind it -- then the error word and the call's one synchronisation
+    const bool gray_back = out->gray && channels > 1;
+    if (gray_back || !first) {
+        const size_t from = gray_back ? 0 : L.o_res - L.o_gray;
+        HIP_TRY(c, hipMemcpyAsync(c->pin + L.o_gray + from, cur_base + S.s_gray + from,
+                                  (L.o_res - L.o_gray) - from + (first ? 0 : sizeof(RgbdStreamRes)), hipMemcpyDeviceToHost, s));
+    }
+    int n = 0;
+    SingleFrameLayout LN{};
+    LN.o_n = L.o_n;
+    rc = finish_single_frame(c, LN, s, &n);
+    // the frame is the next call's predecessor whatever is reported below
+    st->prev_w = W; st->prev_h = H;
+    st->corners_due = !shadow;
+    st->seq++;
+    if (rc) return rc;
+    const RgbdStreamRes* hres = reinterpret_cast<const RgbdStreamRes*>(c->pin + L.o_res);
+    if (!first && hres->ncorners < 0)
+        return set_err(c, COEB_ERANGE, "coeb_rgbd_stream_frame: the previous frame has more local maxima than the exact selection covers");
+    out->first = first;
+    out->n_tm = first ? 0 : hres->ntm;
+    const int nt = first ? 0 : rgbd_stream_tm_count(hres->ntm, out->tm_cap);
+    if (nt > 0) memcpy(out->tm_xy, hres->tm, (size_t)nt * 8);
+    for (int i = 0; i < nbox; i++) out->blur_flag[i] = first ? 0 : hres->flag[i];
+    if (out->gray) {
+        if (channels == 1) {
+            for (int y = 0; y < H; y++) memcpy(out->gray + (size_t)y * out->gray_stride, img + (size_t)y * img_stride, (size_t)W);
+        } else {
+            for (int y = 0; y < H; y++) memcpy(out->gray + (size_t)y * out->gray_stride, c->pin + L.o_gray + (size_t)y * W, (size_t)W);
+        }
+    }
+    out->n = n;
+    frame_tail_copy_out(c, R, std::min(n, guess), out->kp, out->kp_un, out->desc, out->u_right, out->depth);
+    if (n > out->cap) return set_err(c, COEB_ERANGE, "keypoint output capacity too small");
     return COEB_OK;
 }
 

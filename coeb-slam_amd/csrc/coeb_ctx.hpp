@@ -324,3 +324,28 @@ int pmo_batch(coeb_ctx* c, const uint8_t* d_gray, int F, int w, int h, float* tm
 int flow_counts(coeb_ctx* c, int* out, int cap, int* npairs);
 int blur_flags_batch(coeb_ctx* c, const uint8_t* d_gray, int W, int H, const float* d_boxes, const int* d_box_off, int F,
                      int* d_box_frame, int nbox, int* d_out, hipStream_t s);
+
+// coeb_flow.hip / coeb_frame.hip, called by coeb_rgbd_stream_frame (coeb_capi.hip): Frame::ProcessMovingObject
+// in the pieces a frame stream launches, on memory the stream owns (never the context's flow scratch).
+// What the chain keeps of one w x h frame (a slot of the stream, coeb_rgbd_stream_host.hpp):
+struct StreamFlowFrame {
+    uint8_t* gray;                      // level 0, pitch w
+    uint8_t* lvl[8];                    // LK levels 1.. (pitch = level width)
+    void* der[8];                       // Scharr planes of levels 0..
+    float* pts; int* npts;              // refined corners, their count (-1: more candidates than the selection covers)
+};
+size_t stream_flow_corner_scratch(int w, int h);     // bytes stream_flow_corners needs
+size_t stream_flow_track_scratch();                  // bytes stream_flow_track needs
+int stream_flow_levels(int w, int h);                // LK pyramid levels the kernels build for a w x h frame
+int stream_flow_init(coeb_ctx* c, uint8_t* corner_scratch);                         // cornerSubPix's weights (synchronous)
+int stream_flow_pyramid(coeb_ctx* c, const StreamFlowFrame& f, int w, int h, hipStream_t s);      // k_pyr_down per level
+// goodFeaturesToTrack, cornerSubPix and the Scharr derivatives of f: all the chain does on imGrayPre alone
+int stream_flow_corners(coeb_ctx* c, const StreamFlowFrame& f, int w, int h, uint8_t* scratch, hipStream_t s);
+// k_lk from prev's corners into cur, then k_fm: T_M into tm (tm_cap points), |T_M| or -1 into *ntm
+int stream_flow_track(coeb_ctx* c, const StreamFlowFrame& prev, const StreamFlowFrame& cur, int w, int h, uint8_t* scratch,
+                      float* tm, int* ntm, int tm_cap, hipStream_t s);
+// GrabImageRGBD's cvtColor of one staged frame (k_rgbd), and the blur flags of its boxes (k_blur_flags)
+int launch_rgbd_gray(coeb_ctx* c, const uint8_t* d_img, int row_bytes, int channels, int rgb_order, int W, int H,
+                     uint8_t* d_gray, hipStream_t s);
+int launch_blur_flags(coeb_ctx* c, const uint8_t* d_gray, int W, int H, const float* d_boxes, int nbox, int* d_out,
+                      hipStream_t s);

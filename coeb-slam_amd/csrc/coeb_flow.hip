@@ -36,6 +36,7 @@
 #include <cstring>
 
 #include "coeb_ctx.hpp"
+#include "coeb_rgbd_stream_host.hpp"
 
 namespace {
 
@@ -1924,6 +1925,55 @@ int launch_subpix(const FlowDev* d, const uint8_t* img, int w, int h, int stride
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// calcOpticalFlowPyrLK in three steps on explicit LkPyr pointers: the pyrDown levels, the Scharr
+// derivatives of every previous-frame level, the LK iterations.  launch_lk chains them for a pair
+// (or a batch of pairs) whose buffers lie in the flow scratch; a frame stream (stream_flow_*)
+// launches each on the buffers it keeps per frame.
+
+// level sizes of a w x h frame (level 0 = the input, pitch stride); -2: more levels than LkPyr holds
+int lk_geometry(LkPyr& pyr, int w, int h, int stride, int win, int max_level)
+{
+    memset(&pyr, 0, sizeof(pyr));
+    const int L = lk_levels(w, h, win, max_level);
+    if (L > kLkMaxLevels) return -2;
+    pyr.L = L;
+    pyr.w[0] = w; pyr.h[0] = h; pyr.pitch[0] = stride;
+    for (int l = 1; l < L; l++) {
+        pyr.w[l] = (pyr.w[l - 1] + 1) / 2; pyr.h[l] = (pyr.h[l - 1] + 1) / 2; pyr.pitch[l] = pyr.w[l];
+    }
+    return 0;
+}
+
+// levels 1.. of pyr.P (nfr == 1; nz pyramids `iz` / `pz` bytes apart) or of pyr.P and pyr.N
+// (nfr == 2; nz = 2 * pairs), one launch per level
+void launch_pyr_down(const FlowDev* d, const LkPyr& pyr, int nfr, int nz, hipStream_t s, int64_t iz)
+{
+    for (int l = 1; l < pyr.L; l++) {
+        PyrDownArgs a;
+        a.src[0] = pyr.P[l - 1]; a.src[1] = pyr.N[l - 1];
+        a.dst[0] = const_cast<uint8_t*>(pyr.P[l]); a.dst[1] = const_cast<uint8_t*>(pyr.N[l]);
+        a.sw = pyr.w[l - 1]; a.sh = pyr.h[l - 1]; a.spitch = pyr.pitch[l - 1]; a.dw = pyr.w[l]; a.dh = pyr.h[l];
+        a.src_img = l == 1;
+        a.nfr = nfr;
+        FLOW_LAUNCH(d, "k_pyr_down", s, k_pyr_down, dim3((a.dw + 4 * kPdCols - 1) / (4 * kPdCols), (a.dh + kPdRows - 1) / kPdRows,
+                                                         nz), dim3(256), 0, s, a,
+                           iz, d->pz);
+    }
+}
+
+void launch_sharr(const FlowDev* d, const LkPyr& pyr, hipStream_t s, int64_t iz)
+{
+    const int sh_items = ((pyr.w[0] + kShCols - 1) / kShCols) * ((pyr.h[0] + kShRows - 1) / kShRows);   // level 0 is the largest
+    FLOW_LAUNCH(d, "k_sharr", s, k_sharr, dim3((sh_items + 3) / 4, pyr.L, d->npairs), dim3(256), 0, s, pyr, iz, d->pz);
+}
+
+void launch_lk_iter(const FlowDev* d, const LkPyr& pyr, int win, int max_count, double eps, hipStream_t s, int64_t iz)
+{
+    launch_flow_index(d, s);            // the host LK entry point sets npts without cornerSubPix
+    FLOW_LAUNCH(d, "k_lk", s, k_lk, dim3(flow_grid(d, 4)), dim3(256), 0, s, pyr, d->pts, d->offs, d->npairs, d->nxt,
+                d->status, win, max_count, eps * eps, iz, d->pz);
+}
+
 // calcOpticalFlowPyrLK: the pyramids of both frames (pyrDown levels and the Scharr derivatives of
 // every level), then the LK iterations on them
 int launch_lk(const FlowDev* d, const uint8_t* prev, const uint8_t* cur, int w, int h, int stride, int win,
@@ -1931,11 +1981,8 @@ int launch_lk(const FlowDev* d, const uint8_t* prev, const uint8_t* cur, int w, 
 {
     LkPyr pyr;
     const int P = d->npairs;
-    memset(&pyr, 0, sizeof(pyr));
-    const int L = lk_levels(w, h, win, max_level);
-    if (L > kLkMaxLevels) return -2;
-    pyr.L = L;
-    pyr.P[0] = prev; pyr.N[0] = cur; pyr.w[0] = w; pyr.h[0] = h; pyr.pitch[0] = stride;
+    if (lk_geometry(pyr, w, h, stride, win, max_level)) return -2;
+    pyr.P[0] = prev; pyr.N[0] = cur;
     uint8_t* q = d->pyr;
     short2* dq = d->der;
     pyr.D[0] = dq;
@@ -1943,27 +1990,15 @@ int launch_lk(const FlowDev* d, const uint8_t* prev, const uint8_t* cur, int w, 
     // consecutive frames of a batch (pair z = frames z, z + 1): one pyramid per frame, in pair
     // block z, and pair z's next-frame pyramid is pair z + 1's previous-frame one
     const bool chained = P > 1 && iz != 0 && cur == prev + iz;
-    for (int l = 1; l < L; l++) {
-        pyr.w[l] = (pyr.w[l - 1] + 1) / 2; pyr.h[l] = (pyr.h[l - 1] + 1) / 2; pyr.pitch[l] = pyr.w[l];
+    for (int l = 1; l < pyr.L; l++) {
         const size_t sz = (size_t)pyr.w[l] * pyr.h[l];
         pyr.P[l] = q; q += align256(sz);
         pyr.N[l] = chained ? pyr.P[l] + d->pz : q; q += align256(sz);
         pyr.D[l] = dq; dq += sz;
-        PyrDownArgs a;
-        a.src[0] = pyr.P[l - 1]; a.src[1] = pyr.N[l - 1];
-        a.dst[0] = const_cast<uint8_t*>(pyr.P[l]); a.dst[1] = const_cast<uint8_t*>(pyr.N[l]);
-        a.sw = pyr.w[l - 1]; a.sh = pyr.h[l - 1]; a.spitch = pyr.pitch[l - 1]; a.dw = pyr.w[l]; a.dh = pyr.h[l];
-        a.src_img = l == 1;
-        a.nfr = chained ? 1 : 2;
-        FLOW_LAUNCH(d, "k_pyr_down", s, k_pyr_down, dim3((a.dw + 4 * kPdCols - 1) / (4 * kPdCols), (a.dh + kPdRows - 1) / kPdRows,
-                                                         chained ? P + 1 : 2 * P), dim3(256), 0, s, a,
-                           iz, d->pz);
     }
-    const int sh_items = ((w + kShCols - 1) / kShCols) * ((h + kShRows - 1) / kShRows);   // level 0 is the largest
-    FLOW_LAUNCH(d, "k_sharr", s, k_sharr, dim3((sh_items + 3) / 4, L, P), dim3(256), 0, s, pyr, iz, d->pz);
-    launch_flow_index(d, s);            // the host LK entry point sets npts without cornerSubPix
-    FLOW_LAUNCH(d, "k_lk", s, k_lk, dim3(flow_grid(d, 4)), dim3(256), 0, s, pyr, d->pts, d->offs, P, d->nxt,
-                d->status, win, max_count, eps * eps, iz, d->pz);
+    launch_pyr_down(d, pyr, chained ? 1 : 2, chained ? P + 1 : 2 * P, s, iz);
+    launch_sharr(d, pyr, s, iz);
+    launch_lk_iter(d, pyr, win, max_count, eps, s, iz);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -2245,5 +2280,123 @@ extern "C" int coeb_moving_object_points_device(coeb_ctx* c, const uint8_t* d_pr
         FL_TRY(c, hipStreamSynchronize(fc.s));
     }
     *n_tm = nt;
+    return COEB_OK;
+}
+
+// ---- the chain in the pieces a frame stream launches (coeb_rgbd_stream_frame, coeb_capi.hip) ----
+// Every buffer is the stream's own: a FlowDev is laid over the scratch the caller passes and over
+// the frames' slots, one pair, so the kernels and their arguments are those of
+// coeb_moving_object_points_device.
+namespace {
+
+constexpr int64_t kStreamPz = 256;      // pair stride of a one-pair view (only pair 0 is addressed)
+constexpr size_t kStreamMexpOff = 0;    // cornerSubPix's weights lead the corner scratch: their place holds for every frame size
+
+// the slot layout of coeb_rgbd_stream_host.hpp is written for these kernels' limits
+static_assert(kStreamTmCap == kMaxPts, "a slot's corner / T_M arrays hold kMaxPts points");
+static_assert(kStreamLkLevels == kLkMaxLevels, "a slot holds kLkMaxLevels pyramid levels");
+static_assert(sizeof(StreamFlowFrame::lvl) / sizeof(uint8_t*) == kLkMaxLevels &&
+              sizeof(StreamFlowFrame::der) / sizeof(void*) == kLkMaxLevels, "StreamFlowFrame holds kLkMaxLevels levels");
+static_assert(sizeof(LkPyr::P) / sizeof(const uint8_t*) == kLkMaxLevels, "LkPyr holds kLkMaxLevels levels");
+
+struct CornerScratch { size_t R, rmax, nkeys, keys, mexp, offs, order, ocnt, total; };
+CornerScratch corner_scratch(int w, int h)
+{
+    CornerScratch c;
+    size_t o = 0;
+    auto take = [&](size_t n) { const size_t r = o; o += align256(n); return r; };
+    c.mexp = take(kSubpixMaskBytes);        // = kStreamMexpOff
+    c.R = take((size_t)w * h * 4); c.rmax = take(4); c.nkeys = take(4); c.keys = take((size_t)gf_key_cap(w, h) * 8);
+    c.offs = take(8); c.order = take(sizeof(int) * (size_t)kMaxPts); c.ocnt = take(12);
+    c.total = o;
+    return c;
+}
+
+struct TrackScratch { size_t nxt, status, state, F, nf, offs, total; };
+TrackScratch track_scratch()
+{
+    TrackScratch t;
+    size_t o = 0;
+    auto take = [&](size_t n) { const size_t r = o; o += align256(n); return r; };
+    t.nxt = take((size_t)kMaxPts * 8); t.status = take(kMaxPts); t.state = take(kMaxPts); t.F = take(72); t.nf = take(4);
+    t.offs = take(8);
+    t.total = o;
+    return t;
+}
+
+FlowDev stream_view(coeb_ctx* c)
+{
+    FlowDev d;
+    memset(&d, 0, sizeof(d));
+    d.npairs = 1;
+    d.pz = kStreamPz;
+    d.prof = &c->hook;
+    return d;
+}
+
+int stream_pyr(LkPyr& pyr, const StreamFlowFrame& f, int w, int h)
+{
+    if (lk_geometry(pyr, w, h, w, kStreamLkWin, kStreamLkMaxLevel)) return -2;
+    pyr.P[0] = f.gray;
+    for (int l = 1; l < pyr.L; l++) pyr.P[l] = f.lvl[l];
+    for (int l = 0; l < pyr.L; l++) pyr.D[l] = static_cast<const short2*>(f.der[l]);
+    return 0;
+}
+
+}  // namespace
+
+size_t stream_flow_corner_scratch(int w, int h) { return corner_scratch(w, h).total; }
+size_t stream_flow_track_scratch() { return track_scratch().total; }
+int stream_flow_levels(int w, int h) { return lk_levels(w, h, kStreamLkWin, kStreamLkMaxLevel); }
+
+int stream_flow_init(coeb_ctx* c, uint8_t* scratch)
+{
+    float mask[21];
+    subpix_mask(10, mask);
+    FL_TRY(c, hipMemcpy(scratch + kStreamMexpOff, mask, kSubpixMaskBytes, hipMemcpyHostToDevice));
+    return COEB_OK;
+}
+
+int stream_flow_pyramid(coeb_ctx* c, const StreamFlowFrame& f, int w, int h, hipStream_t s)
+{
+    const FlowDev d = stream_view(c);
+    LkPyr pyr;
+    if (stream_pyr(pyr, f, w, h)) return set_err(c, COEB_EINVAL, "coeb_rgbd_stream_frame: image too large");
+    launch_pyr_down(&d, pyr, 1, 1, s, 0);
+    return hipGetLastError() == hipSuccess ? COEB_OK : set_err(c, COEB_EDEVICE, "coeb_rgbd_stream_frame: pyramid launch failed");
+}
+
+int stream_flow_corners(coeb_ctx* c, const StreamFlowFrame& f, int w, int h, uint8_t* scratch, hipStream_t s)
+{
+    const CornerScratch cs = corner_scratch(w, h);
+    FlowDev d = stream_view(c);
+    d.R = (float*)(scratch + cs.R); d.rmax = (uint32_t*)(scratch + cs.rmax); d.nkeys = (int*)(scratch + cs.nkeys);
+    d.keys = (uint64_t*)(scratch + cs.keys); d.offs = (int*)(scratch + cs.offs); d.order = (int*)(scratch + cs.order);
+    d.ocnt = (int*)(scratch + cs.ocnt);
+    d.mexp = (float*)(scratch + kStreamMexpOff);
+    d.pts = f.pts; d.npts = f.npts;
+    LkPyr pyr;
+    if (stream_pyr(pyr, f, w, h)) return set_err(c, COEB_EINVAL, "coeb_rgbd_stream_frame: image too large");
+    if (launch_gf(&d, f.gray, w, h, w, 1000, 0.01, 8.0, 0.04, s) || launch_subpix(&d, f.gray, w, h, w, 20, 0.03, s))
+        return set_err(c, COEB_EDEVICE, "coeb_rgbd_stream_frame: corner launch failed");
+    launch_sharr(&d, pyr, s, 0);
+    return hipGetLastError() == hipSuccess ? COEB_OK : set_err(c, COEB_EDEVICE, "coeb_rgbd_stream_frame: Scharr launch failed");
+}
+
+int stream_flow_track(coeb_ctx* c, const StreamFlowFrame& prev, const StreamFlowFrame& cur, int w, int h, uint8_t* scratch,
+                      float* tm, int* ntm, int tm_cap, hipStream_t s)
+{
+    const TrackScratch ts = track_scratch();
+    FlowDev d = stream_view(c);
+    d.nxt = (float*)(scratch + ts.nxt); d.status = scratch + ts.status; d.state = scratch + ts.state;
+    d.F = (double*)(scratch + ts.F); d.nf = (int*)(scratch + ts.nf); d.offs = (int*)(scratch + ts.offs);
+    d.pts = prev.pts; d.npts = prev.npts;
+    LkPyr pyr;
+    if (stream_pyr(pyr, prev, w, h)) return set_err(c, COEB_EINVAL, "coeb_rgbd_stream_frame: image too large");
+    pyr.N[0] = cur.gray;
+    for (int l = 1; l < pyr.L; l++) pyr.N[l] = cur.lvl[l];
+    launch_lk_iter(&d, pyr, 22, 20, 0.01, s, 0);
+    if (launch_fm(&d, prev.gray, cur.gray, w, h, w, 5, 2120.0, s, tm_cap, 0, tm, ntm))
+        return set_err(c, COEB_EDEVICE, "coeb_rgbd_stream_frame: T_M launch failed");
     return COEB_OK;
 }

@@ -253,6 +253,30 @@ int blur_flags_batch(coeb_ctx* c, const uint8_t* d_gray, int W, int H, const flo
     return hipGetLastError() == hipSuccess ? COEB_OK : COEB_EDEVICE;
 }
 
+// One staged frame for coeb_rgbd_stream_frame, device arrays throughout, enqueued on s: the
+// cvtColor of coeb_rgbd_preprocess (rows row_bytes apart) into a packed gray frame ...
+int launch_rgbd_gray(coeb_ctx* c, const uint8_t* d_img, int row_bytes, int channels, int rgb_order, int W, int H,
+                     uint8_t* d_gray, hipStream_t s)
+{
+    prof_begin(&c->hook, "k_rgbd", s);
+    hipLaunchKernelGGL(k_rgbd, dim3((W + 63) / 64, (H + 3) / 4), dim3(256), 0, s, d_img, row_bytes, channels, rgb_order,
+                       (const uint8_t*)nullptr, 0, 0, 0.f, 0, W, H, d_gray, (float*)nullptr);
+    prof_end(&c->hook, s);
+    return hipGetLastError() == hipSuccess ? COEB_OK : COEB_EDEVICE;
+}
+
+// ... and the blur flag of each of its boxes, as coeb_blur_flags launches it
+int launch_blur_flags(coeb_ctx* c, const uint8_t* d_gray, int W, int H, const float* d_boxes, int nbox, int* d_out,
+                      hipStream_t s)
+{
+    if (nbox <= 0) return COEB_OK;
+    prof_begin(&c->hook, "k_blur_flags", s);
+    hipLaunchKernelGGL(k_blur_flags, dim3(nbox), dim3(256), 0, s, d_gray, W, H, W, d_boxes, d_out, (double*)nullptr,
+                       (const int*)nullptr, (int64_t)0);
+    prof_end(&c->hook, s);
+    return hipGetLastError() == hipSuccess ? COEB_OK : COEB_EDEVICE;
+}
+
 extern "C" int coeb_blur_flags(coeb_ctx* c, const uint8_t* gray, int W, int H, size_t stride, const coeb_box* boxes,
                                int nbox, int32_t* flags_out)
 {

@@ -22,6 +22,9 @@
  *   coeb_frame_rgbd                 <- the RGB-D Frame constructor's tail  src/Frame.cc:214-223:
  *                                      ExtractORB, N = mvKeys.size(), UndistortKeyPoints (:579-609)
  *                                      and ComputeStereoFromRGBD (:820-842) on one host frame
+ *   coeb_rgbd_stream_frame          <- the whole RGB-D Frame constructor  src/Frame.cc:157-223 on a stream
+ *                                      of host frames: ProcessMovingObject against the previous frame
+ *                                      (kept on the device), the blur flags, then coeb_frame_rgbd's steps
  *   coeb_match_lastframe            <- ORBmatcher::SearchByProjection(Frame&, const Frame&,
  *                                      const float th, const bool bMono)
  *                                      include/ORBmatcher.h:52, src/ORBmatcher.cc:1329-1471
@@ -838,6 +841,52 @@ int coeb_moving_object_points(coeb_ctx* ctx, const uint8_t* prev, const uint8_t*
 int coeb_moving_object_points_device(coeb_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_cur, int width,
                                      int height, size_t stride, float* tm_xy, int tm_cap, int* n_tm,
                                      coeb_flow_debug* dbg);
+
+/* ---- The RGB-D Frame constructor on a stream of frames (src/Frame.cc:157-223), one call per frame ----
+ * A coeb_rgbd_stream keeps what the constructor needs of the previous frame on the device (gray
+ * level 0, its LK pyramid, Scharr derivatives and refined corners), in memory of its own: other
+ * calls on the context between two frames, and other streams on the same context, do not touch it.
+ * Call f computes what coeb_moving_object_points(frame f-1, frame f) -> coeb_blur_flags(frame f) ->
+ * coeb_frame_rgbd(frame f, boxes, that T_M, those flags) compute, bit for bit, with one upload (the
+ * boxes and the image rows; the depth rows are not uploaded: as in coeb_frame_rgbd they stay in
+ * page-locked host memory, where the tail kernel reads the values under the keypoints), one pyramid
+ * and one synchronisation: T_M and the flags never leave the device on their way to the extraction.  img / channels / rgb_order as coeb_rgbd_preprocess (1-channel rows are mImGray itself);
+ * depth / cam / dist / cap as coeb_frame_rgbd; at most COEB_MAX_BOXES boxes; width and height >= 32.
+ * A frame without predecessor (the first, or the first after coeb_rgbd_stream_reset) is a first
+ * frame (:205-209): first = 1, n_tm = 0, every flag 0, extraction without T_M.  n_tm = -1:
+ * findFundamentalMat returned an empty matrix; the frame is then extracted without T_M, as
+ * coeb_frame_batch_device does.  At most min(n_tm, tm_cap) points are written to tm_xy.
+ * Errors: COEB_EINVAL (nothing written, the stream unchanged) for a bad argument or a size that
+ * differs from the previous frame's without a reset; COEB_ERANGE with n > cap as coeb_frame_rgbd;
+ * COEB_ERANGE with nothing written when the PREVIOUS frame had more corner candidates than the
+ * exact selection covers (as coeb_moving_object_points on that pair) -- the stream then carries on
+ * with the current frame as the next predecessor.  An empty image returns COEB_OK with n = 0 and
+ * leaves the stream as it was.
+ * The previous-frame-only work (goodFeaturesToTrack, cornerSubPix, the Scharr derivatives) of frame
+ * f runs behind call f on a HIP stream the object owns, and call f + 1 waits for it on the device;
+ * with COEB_STREAM_NO_SHADOW it runs at the start of call f + 1 on the context stream instead.
+ * Destroy the stream before its context. */
+typedef struct coeb_rgbd_stream coeb_rgbd_stream;
+#define COEB_STREAM_NO_SHADOW 1   /* previous-frame-only work runs inside the next call instead of behind this one */
+int coeb_rgbd_stream_create(coeb_ctx* ctx, unsigned flags, coeb_rgbd_stream** out);
+void coeb_rgbd_stream_destroy(coeb_rgbd_stream* st);      /* before coeb_destroy(ctx); joins the shadow work */
+int coeb_rgbd_stream_reset(coeb_rgbd_stream* st);         /* the next frame has no imGrayPre (sequence start, tracking reset) */
+
+typedef struct {
+    float* tm_xy; int tm_cap; int n_tm;        /* T_M in the reference's order; n_tm = -1: F empty; 0 on a first frame */
+    int32_t* blur_flag;                        /* nbox flags (Frame.cc:171-202); all 0 on a first frame (:205-209) */
+    uint8_t* gray; size_t gray_stride;         /* optional: mImGray as GrabImageRGBD makes it */
+    coeb_keypoint *kp, *kp_un; uint8_t* desc; float *u_right, *depth; int cap; int n;   /* as coeb_frame_rgbd */
+    int first;                                 /* 1 when the frame had no predecessor */
+} coeb_rgbd_stream_out;
+
+int coeb_rgbd_stream_frame(coeb_rgbd_stream* st,
+                           const uint8_t* img, size_t img_stride, int channels, int rgb_order,
+                           int width, int height,
+                           const void* depth, size_t depth_stride, int depth_type, float depth_scale,
+                           const coeb_camera* cam, const float dist[5],
+                           const coeb_box* boxes, int nbox,
+                           coeb_rgbd_stream_out* out);
 
 int coeb_descriptor_distance(const uint8_t* a, const uint8_t* b);
 
