@@ -77,7 +77,8 @@ ABI_SYMBOLS = [
     "coeb_bow_set_vocabulary", "coeb_bow_transform", "coeb_bow_batch_device", "coeb_batch_bow_results",
     "coeb_match_bow",
     "coeb_bow_vector", "coeb_kfdb_create", "coeb_kfdb_destroy", "coeb_kfdb_add", "coeb_kfdb_erase", "coeb_kfdb_clear",
-    "coeb_kfdb_size", "coeb_kfdb_query", "coeb_match_bow_kfdb",
+    "coeb_kfdb_size", "coeb_kfdb_query", "coeb_match_bow_kfdb", "coeb_kfdb_set_geometry",
+    "coeb_kfdb_search_triangulation",
     "coeb_search_local_points", "coeb_track_local_map", "coeb_track_reference_keyframe",
     "coeb_track_motion_model", "coeb_reloc_refine",
     "coeb_rgbd_stream_create", "coeb_rgbd_stream_destroy", "coeb_rgbd_stream_reset", "coeb_rgbd_stream_frame",
@@ -321,6 +322,10 @@ def lib():
                                       C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.coeb_match_bow_kfdb.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(BowFrameC),
                                           C.c_float, C.c_int, C.c_void_p, C.c_void_p]
+        L.coeb_kfdb_set_geometry.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.coeb_kfdb_search_triangulation.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                     C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                     C.c_void_p, C.c_void_p]
         L.coeb_profile_enable.argtypes = [C.c_void_p, C.c_int]
         L.coeb_profile_reset.argtypes = [C.c_void_p]
         L.coeb_profile_read.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
@@ -1454,6 +1459,45 @@ class KeyFrameDatabase:
         self.ctx.check(lib().coeb_match_bow_kfdb(self.h, _p(slots) if nc else None, nc, vp, C.byref(fc), nnratio,
                                                  int(checkOri), _p(out) if out.size else None, _p(nm)))
         return out, nm[:nc]
+
+    def set_geometry(self, slot, keys_un, u_right):
+        """What SearchForTriangulation reads of the keyframe in `slot` beyond add()'s arrays: mvKeysUn
+        (pt, octave) and mvuRight, one entry per feature.  erase, clear and the reuse of a slot drop it."""
+        keys_un = np.ascontiguousarray(keys_un, KEYPOINT_DTYPE)
+        u_right = np.ascontiguousarray(u_right, np.float32)
+        n = self._n.get(int(slot))
+        if n is not None and (len(keys_un) != n or len(u_right) != n):
+            raise ValueError("the keyframe of slot %d has %d features" % (slot, n))
+        self.ctx.check(lib().coeb_kfdb_set_geometry(self.h, int(slot), _p(keys_un) if len(keys_un) else None,
+                                                    _p(u_right) if len(u_right) else None))
+
+    def search_for_triangulation(self, slot1, has_mp1, slots2, has_mp2, F12, epipole, only_stereo, check_orientation):
+        """ORBmatcher(_, check_orientation).SearchForTriangulation(KF[slot1], KF[slots2[j]], F12[j], .., only_stereo)
+        for every neighbour j in one call (LocalMapping::CreateNewMapPoints).  has_mp1 / has_mp2[j]:
+        GetMapPoint(i) != NULL per feature; F12 [nnb, 3, 3] and epipole [nnb, 2] = (ex, ey) are the caller's.
+        -> (match [nnb, n1] int32: vMatches12, nmatches [nnb])."""
+        slots2 = np.ascontiguousarray(slots2, np.int32)
+        nnb = len(slots2)
+        if len(has_mp2) != nnb:
+            raise ValueError("one has_mp2 mask per neighbour")
+        has_mp1 = np.ascontiguousarray(has_mp1, np.uint8)
+        has_mp2 = [np.ascontiguousarray(m, np.uint8) for m in has_mp2]
+        n1 = self._n.get(int(slot1), len(has_mp1))
+        if len(has_mp1) != n1:
+            raise ValueError("has_mp1 has %d entries, the keyframe %d" % (len(has_mp1), n1))
+        for s, m in zip(slots2, has_mp2):
+            if int(s) in self._n and len(m) != self._n[int(s)]:
+                raise ValueError("has_mp2 of slot %d has %d entries, the keyframe %d" % (s, len(m), self._n[int(s)]))
+        F12 = np.ascontiguousarray(F12, np.float32).reshape(nnb, 9)
+        epipole = np.ascontiguousarray(epipole, np.float32).reshape(nnb, 2)
+        mp = (C.c_void_p * max(nnb, 1))(*[m.ctypes.data if len(m) else None for m in has_mp2])
+        out = np.full((nnb, n1), -1, np.int32)
+        nm = np.zeros(max(nnb, 1), np.int32)
+        self.ctx.check(lib().coeb_kfdb_search_triangulation(
+            self.h, int(slot1), _p(has_mp1) if n1 else None, _p(slots2) if nnb else None, nnb, mp,
+            _p(F12) if nnb else None, _p(epipole) if nnb else None, int(bool(only_stereo)), int(bool(check_orientation)),
+            _p(out) if out.size else None, _p(nm)))
+        return out, nm[:nnb]
 
 
 class ORBmatcher:

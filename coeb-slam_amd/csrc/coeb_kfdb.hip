@@ -3,6 +3,8 @@
 //   DetectRelocalizationCandidates up to lScoreAndMatch  src/KeyFrameDatabase.cc:199-253
 //                                                        (k_kfdb_common, k_kfdb_score)
 //   SearchByBoW against every candidate                  src/Tracking.cc:1449-1470 (k_match_bow_db)
+//   SearchForTriangulation against every neighbour       src/ORBmatcher.cc:657-824, 140-157 (k_tri_match,
+//                                                        k_tri_rot)
 // What a keyframe contributes never changes after KeyFrame::ComputeBoW, so it is uploaded once
 // (descriptors, angles, BowVector) and its feature-vector CSR is built once.  There is no inverted
 // file: mnRelocWords of a keyframe is |words(F) & words(KF)|, counted per keyframe.  The scoring
@@ -41,6 +43,10 @@ struct coeb_kfdb {
     std::vector<uint8_t> used;
     std::vector<int> n, nd;         // features and feature-vector nodes per slot
     std::vector<int64_t> seq;       // insertion sequence number per slot
+    // coeb_kfdb_set_geometry: KfdbGeo[mf] per slot, allocated by the first call (null before)
+    uint8_t* geo = nullptr;
+    size_t geo_stride = 0;
+    std::vector<uint8_t> has_geo;   // the slot's keyframe has its geometry
 };
 
 namespace {
@@ -203,6 +209,170 @@ __global__ __launch_bounds__(kCsrThreads) void k_bow_rot_db(DbMatch a)
                    s_ind, &s_cnt);
 }
 
+// ============================== k_tri_match ==============================
+// ORBmatcher::SearchForTriangulation (:686-776) over (node of keyframe 1, neighbour).  Nothing is
+// claimed (:762 is commented out), so a feature idx1 is decided alone: its match is the accepted
+// candidate of its node's list in keyframe 2 with the smallest distance, the last in list order
+// among equals (dist > bestDist skips, so an equal later one replaces).  bestDist only moves on
+// acceptance: a nearer candidate that fails a geometric test shadows nothing.
+// A workgroup takes one node; its waves take the node's keyframe-1 features in turn and the lanes
+// of a wave the list positions p, p + 64, .. of keyframe 2.  What depends on the candidate alone
+// (descriptor, point, the map-point / stereo skip, the epipole test, the chi-square bound) is
+// loaded once per lane for the first trip and kept in registers across the wave's features;
+// further trips reload theirs.  The winner is one min over (dist << 16 | 0xFFFF - p).  No LDS.
+// The float forms are those of the reference binary: a, b = fma(x1, F0k, y1 * F1k)
+// + F2k; c = fma(y1, F12, x1 * F02) + F22; den = fma(a, a, b * b); num = fma(b, y2, a * x2) + c;
+// the epipole distance fma(dx, dx, dy * dy).  The bound is the double product 3.84 * sigma2.
+constexpr int kTriThreads = 256;
+constexpr int kTriWaves = kTriThreads / 64;
+static_assert(kBowMax <= 0xFFFF, "a list position fits the key's low half");
+
+struct TriArgs {
+    KfdbView v;
+    const uint8_t* geo;         // the geometry slab
+    size_t geo_stride;
+    int slot1;
+    const uint8_t* has1;        // [n1]
+    const int* tab;             // [nnb][2]: slot2, offset of the neighbour's has_mp2 in masks
+    const uint8_t* masks;
+    const float* F;             // [nnb][9]
+    const float* epi;           // [nnb][2]
+    const float* scale;         // [COEB_MAXL] mvScaleFactors
+    const float* sigma2;        // [COEB_MAXL] mvLevelSigma2
+    int only_stereo, check_ori;
+    int cs;                     // max(n1, 1): the row stride of match and bin
+    int* match; int* bin; int* hist; int* nm;
+};
+
+struct TriCand {
+    uint32_t d[8];
+    float x, y;
+    double bound;               // 3.84 * mvLevelSigma2[octave]
+    bool ok;                    // in the list, without a MapPoint, stereo under only_stereo
+    bool stereo;
+    bool near_epipole;          // distex^2 + distey^2 < 100 * mvScaleFactors[octave]
+};
+
+__device__ __forceinline__ TriCand tri_cand(const TriArgs& a, const uint8_t* desc2, const KfdbGeo* geo2, const uint8_t* has2,
+                                            const int* list2, int p, int len, float ex, float ey)
+{
+    TriCand c;
+#pragma unroll
+    for (int k = 0; k < 8; k++) c.d[k] = 0;
+    c.x = c.y = 0.f; c.bound = 0.0; c.ok = c.stereo = c.near_epipole = false;
+    if (p >= len) return c;
+    const int i2 = list2[p];
+    const KfdbGeo g = geo2[i2];
+    c.stereo = g.u_right >= 0;
+    c.ok = !has2[i2] && (!a.only_stereo || c.stereo);
+    if (!c.ok) return c;
+    const uint4* d = reinterpret_cast<const uint4*>(desc2 + (int64_t)i2 * 32);
+    const uint4 d0 = d[0], d1 = d[1];
+    c.d[0] = d0.x; c.d[1] = d0.y; c.d[2] = d0.z; c.d[3] = d0.w;
+    c.d[4] = d1.x; c.d[5] = d1.y; c.d[6] = d1.z; c.d[7] = d1.w;
+    c.x = g.x; c.y = g.y;
+    const float distex = ex - g.x, distey = ey - g.y;
+    c.near_epipole = fmaf(distex, distex, distey * distey) < 100.0f * a.scale[g.octave];
+    c.bound = 3.84 * (double)a.sigma2[g.octave];
+    return c;
+}
+
+struct TriLine { float a, b, c, den; bool stereo1; };
+
+// the candidate at list position p against one feature of keyframe 1: the smaller of key and its own
+__device__ __forceinline__ uint32_t tri_eval(const TriCand& c, int p, const uint32_t* q, const TriLine& l, uint32_t key)
+{
+    if (!c.ok) return key;
+    const uint32_t dist = (uint32_t)hamming32(q, c.d);
+    if (dist > (uint32_t)TH_LOW) return key;
+    if (!l.stereo1 && !c.stereo && c.near_epipole) return key;
+    if (l.den == 0) return key;
+    const float num = fmaf(l.b, c.y, l.a * c.x) + l.c;
+    const float dsqr = num * num / l.den;
+    if (!((double)dsqr < c.bound)) return key;
+    return min(key, (dist << 16) | (uint32_t)(0xFFFF - p));
+}
+
+__global__ __launch_bounds__(kTriThreads) void k_tri_match(TriArgs a)
+{
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int w = blockIdx.x, j = blockIdx.y;
+    const int slot2 = a.tab[2 * j];
+    const int n1 = a.v.meta[a.slot1 * 4], n2 = a.v.meta[slot2 * 4];
+    const int cap1 = max(n1, 1), cap2 = max(n2, 1);
+    const int* csr1 = a.v.csr(a.slot1);
+    const int* csr2 = a.v.csr(slot2);
+    if (w >= csr1[0]) return;                      // workgroup-uniform from here on
+    const int* node1 = csr1 + 4;
+    const int* off1 = node1 + cap1;
+    const int* idx1 = off1 + cap1 + 1;
+    const int* node2 = csr2 + 4;
+    const int* off2 = node2 + cap2;
+    const int* idx2 = off2 + cap2 + 1;
+    const int node = node1[w];
+    int lo = 0, hi = csr2[0];
+    while (lo < hi) {                              // lower bound of node among keyframe 2's nodes
+        const int mid = (lo + hi) >> 1;
+        if (node2[mid] < node) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo >= csr2[0] || node2[lo] != node) return;
+    const int len = off2[lo + 1] - off2[lo];
+    const int* list2 = idx2 + off2[lo];
+    const int k0 = off1[w], k1 = off1[w + 1];
+    const uint8_t* desc1 = a.v.desc(a.slot1);
+    const uint8_t* desc2 = a.v.desc(slot2);
+    const KfdbGeo* geo1 = reinterpret_cast<const KfdbGeo*>(a.geo + a.slot1 * a.geo_stride);
+    const KfdbGeo* geo2 = reinterpret_cast<const KfdbGeo*>(a.geo + slot2 * a.geo_stride);
+    const uint8_t* has2 = a.masks + a.tab[2 * j + 1];
+    const float* F = a.F + j * 9;
+    const float ex = a.epi[2 * j], ey = a.epi[2 * j + 1];
+    const TriCand first = tri_cand(a, desc2, geo2, has2, list2, lane, len, ex, ey);
+    for (int kq = k0 + wv; kq < k1; kq += kTriWaves) {
+        const int i1 = __builtin_amdgcn_readfirstlane(idx1[kq]);
+        if (a.has1[i1]) continue;                  // wave-uniform
+        const KfdbGeo g1 = geo1[i1];
+        TriLine l;
+        l.stereo1 = g1.u_right >= 0;
+        if (a.only_stereo && !l.stereo1) continue;
+        uint32_t q[8];
+        {
+            const uint4* d = reinterpret_cast<const uint4*>(desc1 + (int64_t)i1 * 32);
+            const uint4 d0 = d[0], d1 = d[1];
+            q[0] = d0.x; q[1] = d0.y; q[2] = d0.z; q[3] = d0.w;
+            q[4] = d1.x; q[5] = d1.y; q[6] = d1.z; q[7] = d1.w;
+        }
+        l.a = fmaf(g1.x, F[0], g1.y * F[3]) + F[6];
+        l.b = fmaf(g1.x, F[1], g1.y * F[4]) + F[7];
+        l.c = fmaf(g1.y, F[5], g1.x * F[2]) + F[8];
+        l.den = fmaf(l.a, l.a, l.b * l.b);
+        uint32_t key = tri_eval(first, lane, q, l, 0xFFFFFFFFu);
+        for (int base = 64; base < len; base += 64)
+            key = tri_eval(tri_cand(a, desc2, geo2, has2, list2, base + lane, len, ex, ey), base + lane, q, l, key);
+#pragma unroll
+        for (int x = 1; x < 64; x <<= 1) key = min(key, (uint32_t)__shfl_xor((int)key, x));
+        if (lane == 0 && key != 0xFFFFFFFFu) {
+            const int i2 = list2[0xFFFF - (int)(key & 0xFFFFu)];
+            a.match[(size_t)j * a.cs + i1] = i2;
+            if (a.check_ori) {
+                int b = rot_bin(a.v.angle(a.slot1)[i1], a.v.angle(slot2)[i2]);
+                if (b < 0 || b >= HISTO_LENGTH) b = HISTO_LENGTH;                // the reference asserts; dropped below
+                else atomicAdd(&a.hist[j * 32 + b], 1);
+                a.bin[(size_t)j * a.cs + i1] = b;
+            }
+        }
+    }
+}
+
+// the three-maxima pass and the match count of every neighbour, one workgroup each
+__global__ __launch_bounds__(kCsrThreads) void k_tri_rot(TriArgs a, int n1)
+{
+    __shared__ int s_ind[3], s_cnt;
+    const int y = blockIdx.x;
+    bow_rot_filter(a.match + (size_t)y * a.cs, a.bin + (size_t)y * a.cs, a.hist + y * 32, n1, a.check_ori, a.nm + y, s_ind,
+                   &s_cnt);
+}
+
 size_t slot_stride(int mf) { return ((size_t)mf * 48 + (size_t)csr_ints(mf) * 4 + 255) & ~(size_t)255; }
 
 int db_err(coeb_kfdb* db, const char* what)
@@ -221,25 +391,30 @@ int grow(coeb_kfdb* db, int want)
     uint8_t* slab = nullptr;
     int* meta = nullptr;
     int* q = nullptr;
+    uint8_t* geo = nullptr;
     hipError_t e = hipMalloc(&slab, (size_t)ncap * db->v.stride);
     if (e == hipSuccess) e = hipMalloc(&meta, (size_t)ncap * 16);
     if (e == hipSuccess) e = hipMalloc(&q, (4 + 3 * (size_t)ncap) * 4);
+    if (e == hipSuccess && db->geo) e = hipMalloc(&geo, (size_t)ncap * db->geo_stride);
     if (e != hipSuccess) {
         if (slab) (void)hipFree(slab);
         if (meta) (void)hipFree(meta);
+        if (q) (void)hipFree(q);
         return set_err(c, COEB_ENOMEM, std::string("hipMalloc kfdb: ") + hipGetErrorString(e));
     }
     HIP_TRY(c, hipMemsetAsync(meta, 0, (size_t)ncap * 16, s));
     if (db->nslots) {
         HIP_TRY(c, hipMemcpyAsync(slab, db->v.slab, (size_t)db->nslots * db->v.stride, hipMemcpyDeviceToDevice, s));
         HIP_TRY(c, hipMemcpyAsync(meta, db->v.meta, (size_t)db->nslots * 16, hipMemcpyDeviceToDevice, s));
+        if (geo) HIP_TRY(c, hipMemcpyAsync(geo, db->geo, (size_t)db->nslots * db->geo_stride, hipMemcpyDeviceToDevice, s));
     }
     HIP_TRY(c, hipStreamSynchronize(s));
     if (db->v.slab) (void)hipFree(db->v.slab);
     if (db->v.meta) (void)hipFree(db->v.meta);
     if (db->q) (void)hipFree(db->q);
-    db->v.slab = slab; db->v.meta = meta; db->q = q; db->cap = ncap;
-    db->used.resize(ncap, 0); db->n.resize(ncap, 0); db->nd.resize(ncap, 0); db->seq.resize(ncap, 0);
+    if (db->geo) (void)hipFree(db->geo);
+    db->v.slab = slab; db->v.meta = meta; db->q = q; db->geo = geo; db->cap = ncap;
+    db->used.resize(ncap, 0); db->has_geo.resize(ncap, 0); db->n.resize(ncap, 0); db->nd.resize(ncap, 0); db->seq.resize(ncap, 0);
     return 0;
 }
 
@@ -248,7 +423,8 @@ void release_device(coeb_kfdb* db)
     if (db->v.slab) (void)hipFree(db->v.slab);
     if (db->v.meta) (void)hipFree(db->v.meta);
     if (db->q) (void)hipFree(db->q);
-    db->v.slab = nullptr; db->v.meta = nullptr; db->q = nullptr;
+    if (db->geo) (void)hipFree(db->geo);
+    db->v.slab = nullptr; db->v.meta = nullptr; db->q = nullptr; db->geo = nullptr;
     db->cap = db->nslots = db->nkf = 0;
 }
 
@@ -333,6 +509,7 @@ int coeb_kfdb_add(coeb_kfdb* db, const coeb_kfdb_keyframe* kf, int* slot_out)
     HIP_TRY(c, hipMemcpyAsync(c->pin, db->v.csr(slot), 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     db->used[slot] = 1;
+    db->has_geo[slot] = 0;
     db->n[slot] = n;
     db->nd[slot] = reinterpret_cast<const int32_t*>(c->pin)[0];
     db->seq[slot] = db->next_seq++;
@@ -350,6 +527,7 @@ int coeb_kfdb_erase(coeb_kfdb* db, int slot)
     (void)hipSetDevice(c->device);
     HIP_TRY(c, hipMemsetAsync(db->v.meta + slot * 4, 0, 16, main_stream(c)));
     db->used[slot] = 0;
+    db->has_geo[slot] = 0;
     db->n[slot] = db->nd[slot] = 0;
     db->nkf--;
     return COEB_OK;
@@ -362,6 +540,7 @@ int coeb_kfdb_clear(coeb_kfdb* db)
     (void)hipSetDevice(c->device);
     HIP_TRY(c, hipMemsetAsync(db->v.meta, 0, (size_t)db->cap * 16, main_stream(c)));
     std::fill(db->used.begin(), db->used.end(), 0);
+    std::fill(db->has_geo.begin(), db->has_geo.end(), 0);
     std::fill(db->n.begin(), db->n.end(), 0);
     std::fill(db->nd.begin(), db->nd.end(), 0);
     db->nslots = db->nkf = 0;
@@ -492,6 +671,93 @@ int coeb_match_bow_kfdb(coeb_kfdb* db, const int32_t* slots, int ncand, const ui
     HIP_TRY(c, hipStreamSynchronize(s));
     for (int j = 0; j < ncand && n; j++) memcpy(match_out + (size_t)j * n, hout + (size_t)j * cs, (size_t)n * 4);
     memcpy(nmatches, hout + (size_t)ncand * cs, (size_t)ncand * 4);
+    return COEB_OK;
+}
+
+int coeb_kfdb_set_geometry(coeb_kfdb* db, int slot, const coeb_keypoint* keys_un, const float* u_right)
+{
+    if (!db || !db->c) return db_err(db, "coeb_kfdb_set_geometry: invalid arguments");
+    if (slot < 0 || slot >= db->nslots || !db->used[slot]) return db_err(db, "coeb_kfdb_set_geometry: no keyframe in that slot");
+    coeb_ctx* c = db->c;
+    const int n = db->n[slot];
+    if (n && (!keys_un || !u_right)) return db_err(db, "coeb_kfdb_set_geometry: missing keyframe arrays");
+    (void)hipSetDevice(c->device);
+    int rc;
+    if ((rc = pinned(c, (size_t)n * sizeof(KfdbGeo)))) return rc;
+    if (!kfdb_pack_geometry(keys_un, u_right, n, c->tab.nlevels, reinterpret_cast<KfdbGeo*>(c->pin)))
+        return db_err(db, "coeb_kfdb_set_geometry: keypoint octave outside the pyramid");
+    if (!db->geo) {
+        const size_t stride = ((size_t)db->v.mf * sizeof(KfdbGeo) + 255) & ~(size_t)255;
+        const hipError_t e = hipMalloc(&db->geo, (size_t)db->cap * stride);
+        if (e != hipSuccess) {
+            db->geo = nullptr;
+            return set_err(c, COEB_ENOMEM, std::string("hipMalloc kfdb geometry: ") + hipGetErrorString(e));
+        }
+        db->geo_stride = stride;
+    }
+    if (n) {
+        hipStream_t s = main_stream(c);
+        HIP_TRY(c, hipMemcpyAsync(db->geo + slot * db->geo_stride, c->pin, (size_t)n * sizeof(KfdbGeo), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipStreamSynchronize(s));       // the page-locked buffer is the next call's
+    }
+    db->has_geo[slot] = 1;
+    return COEB_OK;
+}
+
+// Uploaded: both masks, the slot table, F12, the epipoles, the level tables, the zeroed histograms and
+// the match rows as -1.  Copied back: the match rows and the counts.
+int coeb_kfdb_search_triangulation(coeb_kfdb* db, int slot1, const uint8_t* has_mp1, const int32_t* slots2, int nnb,
+                                   const uint8_t* const* has_mp2, const float* F12, const float* epipole,
+                                   int only_stereo, int check_orientation, int32_t* match_out, int32_t* nmatches)
+{
+    const std::string w("coeb_kfdb_search_triangulation: ");
+    if (!db || !db->c) return db_err(db, (w + "invalid arguments").c_str());
+    coeb_ctx* c = db->c;
+    const char* why = kfdb_tri_check(db->used.data(), db->has_geo.data(), db->n.data(), db->nslots, slot1, has_mp1, slots2,
+                                     nnb, has_mp2, F12, epipole, match_out, nmatches);
+    if (why) return db_err(db, (w + why).c_str());
+    if (nnb == 0) return COEB_OK;
+    const int n1 = db->n[slot1];
+    if (n1 == 0) {
+        memset(nmatches, 0, (size_t)nnb * 4);
+        return COEB_OK;
+    }
+    (void)hipSetDevice(c->device);
+    hipStream_t s = main_stream(c);
+    std::vector<uint8_t> masks;
+    std::vector<int32_t> tab;
+    kfdb_tri_pack(db->n.data(), slots2, nnb, has_mp2, masks, tab);
+    const size_t rows = (size_t)nnb * n1;
+    Staged st;
+    const size_t o_h1 = st.add(has_mp1, (size_t)n1), o_mk = st.add(masks.data(), masks.size());
+    const size_t o_tab = st.add(tab.data(), tab.size() * 4), o_F = st.add(F12, (size_t)nnb * 36);
+    const size_t o_e = st.add(epipole, (size_t)nnb * 8);
+    const size_t o_sc = st.add(c->tab.scale, sizeof(float) * COEB_MAXL), o_sg = st.add(c->tab.sigma2, sizeof(float) * COEB_MAXL);
+    const size_t o_hist = st.fill(0, (size_t)nnb * 32 * 4);
+    // results: the match rows with their initial value, the counts; then scratch
+    const size_t o_m = st.fill(0xFF, rows * 4), o_nm = st.take((size_t)nnb * 4);
+    const size_t back_end = st.end();
+    const size_t o_bin = st.take(rows * 4);
+    int rc;
+    if ((rc = st.stage(c, s, false))) return rc;
+    TriArgs a;
+    a.v = db->v; a.geo = db->geo; a.geo_stride = db->geo_stride; a.slot1 = slot1;
+    a.has1 = st.dev<uint8_t>(o_h1); a.tab = st.dev<int>(o_tab); a.masks = st.dev<uint8_t>(o_mk);
+    a.F = st.dev<float>(o_F); a.epi = st.dev<float>(o_e); a.scale = st.dev<float>(o_sc); a.sigma2 = st.dev<float>(o_sg);
+    a.only_stereo = only_stereo ? 1 : 0; a.check_ori = check_orientation ? 1 : 0; a.cs = n1;
+    a.match = st.dev<int>(o_m); a.bin = st.dev<int>(o_bin); a.hist = st.dev<int>(o_hist); a.nm = st.dev<int>(o_nm);
+    if (db->nd[slot1]) {
+        prof_begin(&c->hook, "k_tri_match", s);
+        hipLaunchKernelGGL(k_tri_match, dim3(db->nd[slot1], nnb), dim3(kTriThreads), 0, s, a);
+        prof_end(&c->hook, s);
+    }
+    prof_begin(&c->hook, "k_tri_rot", s);
+    hipLaunchKernelGGL(k_tri_rot, dim3(nnb), dim3(kCsrThreads), 0, s, a, n1);
+    prof_end(&c->hook, s);
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = st.finish(c, s, o_m, back_end, false))) return rc;
+    memcpy(match_out, st.host<int32_t>(o_m), rows * 4);
+    memcpy(nmatches, st.host<int32_t>(o_nm), (size_t)nnb * 4);
     return COEB_OK;
 }
 

@@ -66,3 +66,50 @@ extern "C" int coeb_bow_vector(const int32_t* word, const double* weight, const 
     }
     return COEB_OK;
 }
+
+// ---- SearchForTriangulation over stored keyframes: packing and argument rules ----
+bool kfdb_pack_geometry(const coeb_keypoint* keys_un, const float* u_right, int n, int nlevels, KfdbGeo* out)
+{
+    for (int i = 0; i < n; i++) {
+        const int oct = keys_un[i].octave;
+        if (oct < 0 || oct >= nlevels) return false;
+        out[i] = KfdbGeo{keys_un[i].x, keys_un[i].y, u_right[i], oct};
+    }
+    return true;
+}
+
+const char* kfdb_tri_check(const uint8_t* used, const uint8_t* geo, const int* n, int nslots, int slot1,
+                           const uint8_t* has_mp1, const int32_t* slots2, int nnb, const uint8_t* const* has_mp2,
+                           const float* F12, const float* epipole, const int32_t* match_out, const int32_t* nmatches)
+{
+    if (nnb < 0 || nnb > COEB_TRI_MAX_NEIGHBOURS) return "the neighbour count lies outside 0..32";
+    if (slot1 < 0 || slot1 >= nslots || !used[slot1]) return "no keyframe in slot1";
+    if (!geo[slot1]) return "slot1 has no geometry (coeb_kfdb_set_geometry)";
+    if (nnb == 0) return nullptr;
+    if (!slots2 || !has_mp2 || !F12 || !epipole || !nmatches) return "missing arrays";
+    if (n[slot1] && (!has_mp1 || !match_out)) return "missing has_mp1 or match_out";
+    for (int j = 0; j < nnb; j++) {
+        const int s = slots2[j];
+        if (s < 0 || s >= nslots || !used[s]) return "no keyframe in a neighbour's slot";
+        if (!geo[s]) return "a neighbour's slot has no geometry (coeb_kfdb_set_geometry)";
+        if (n[s] && !has_mp2[j]) return "missing has_mp2 mask";
+    }
+    return nullptr;
+}
+
+void kfdb_tri_pack(const int* n, const int32_t* slots2, int nnb, const uint8_t* const* has_mp2,
+                   std::vector<uint8_t>& masks, std::vector<int32_t>& tab)
+{
+    tab.assign((size_t)nnb * 2, 0);
+    size_t total = 0;
+    for (int j = 0; j < nnb; j++) {
+        tab[2 * j] = slots2[j];
+        tab[2 * j + 1] = (int32_t)total;
+        total += ((size_t)n[slots2[j]] + 15) & ~(size_t)15;
+    }
+    masks.assign(total, 0);
+    for (int j = 0; j < nnb; j++) {
+        const int nj = n[slots2[j]];
+        if (nj) std::copy(has_mp2[j], has_mp2[j] + nj, masks.begin() + tab[2 * j + 1]);
+    }
+}

@@ -4,6 +4,10 @@
 #pragma once
 #include <stdint.h>
 
+#include <vector>
+
+#include "../../include/coeb_front.h"
+
 // int minCommonWords = maxCommonWords * 0.8f  (:235): a float multiply, truncated
 int kfdb_min_common(int max_common);
 
@@ -14,3 +18,22 @@ int kfdb_sharing_order(const int32_t* common, const int32_t* first_word, const i
 
 // bow_word strictly ascending and non-negative
 bool kfdb_words_ascending(const int32_t* word, int nw);
+
+// ---- LocalMapping::CreateNewMapPoints' SearchForTriangulation over stored keyframes ----
+// What coeb_kfdb_set_geometry keeps of one feature: mvKeysUn[i].pt, mvuRight[i], mvKeysUn[i].octave.
+struct KfdbGeo { float x, y, u_right; int32_t octave; };
+static_assert(sizeof(KfdbGeo) == 16, "the geometry slab holds 16 bytes per feature");
+
+// out[0 .. n) from the keyframe's arrays; false, with out unspecified, when an octave lies outside 0 .. nlevels - 1
+bool kfdb_pack_geometry(const coeb_keypoint* keys_un, const float* u_right, int n, int nlevels, KfdbGeo* out);
+
+// The rules of coeb_kfdb_search_triangulation's arguments that need no device.  used / geo / n describe
+// the slots [0, nslots).  nullptr: the call may go on; else the text of its COEB_EINVAL.
+const char* kfdb_tri_check(const uint8_t* used, const uint8_t* geo, const int* n, int nslots, int slot1,
+                           const uint8_t* has_mp1, const int32_t* slots2, int nnb, const uint8_t* const* has_mp2,
+                           const float* F12, const float* epipole, const int32_t* match_out, const int32_t* nmatches);
+
+// The neighbours' masks one after the other at 16-byte rounded offsets of `masks`, and the table the
+// kernel reads: tab[2 j] = slots2[j], tab[2 j + 1] = the offset of has_mp2[j] in masks.
+void kfdb_tri_pack(const int* n, const int32_t* slots2, int nnb, const uint8_t* const* has_mp2,
+                   std::vector<uint8_t>& masks, std::vector<int32_t>& tab);

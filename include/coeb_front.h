@@ -103,7 +103,11 @@
  *                                      covisibility tail :258-308 stays on the host, in the adapters)
  *   coeb_match_bow_kfdb             <- the SearchByBoW loop of Tracking::Relocalization
  *                                      src/Tracking.cc:1449-1470
- *   coeb_tum_read_list             <- associate.py read_file_list  associate.py:49-69
+ *   coeb_kfdb_search_triangulation  <- the SearchForTriangulation loop of
+ *                                      LocalMapping::CreateNewMapPoints  src/LocalMapping.cc:255-270,
+ *                                      src/ORBmatcher.cc:657-824 (coeb_kfdb_set_geometry: the
+ *                                      KeyFrame's mvKeysUn / mvuRight it reads)
+ *   coeb_tum_read_list            <- associate.py read_file_list  associate.py:49-69
  *   coeb_tum_associate              <- associate.py associate  associate.py:71-102 (host only)
  *
  * Conventions: 0 on success, negative COEB_E* code on failure (the reference has no error
@@ -710,6 +714,31 @@ int coeb_kfdb_query(coeb_kfdb* db, const int32_t* word, const double* value, int
 int coeb_match_bow_kfdb(coeb_kfdb* db, const int32_t* slots, int ncand, const uint8_t* const* valid,
                         const coeb_bow_frame* cur, float nnratio, int check_orientation, int32_t* match_out,
                         int32_t* nmatches);
+
+/* ---- ORBmatcher::SearchForTriangulation against many keyframes (src/ORBmatcher.cc:657-824, the
+ * loop of LocalMapping::CreateNewMapPoints, src/LocalMapping.cc:255-270) ----
+ * coeb_kfdb_set_geometry uploads what the search reads of a stored keyframe beyond coeb_kfdb_add's
+ * arrays: mvKeysUn[i].pt, mvKeysUn[i].octave and mvuRight[i] of the slot's n features (const
+ * members of KeyFrame).  They live in a slab of their own (16 bytes per feature, allocated by the
+ * first call, growing with the slots); erase, clear and the reuse of a slot drop them, a second call
+ * replaces them.  COEB_EINVAL for an empty or out-of-range slot, a NULL array with n > 0 or an
+ * octave outside the context's pyramid. */
+int coeb_kfdb_set_geometry(coeb_kfdb* db, int slot, const coeb_keypoint* keys_un, const float* u_right);
+#define COEB_TRI_MAX_NEIGHBOURS 32
+/* SearchForTriangulation(pKF1 = slot1, pKF2 = slots2[j], F12[j], vMatchedPairs, only_stereo) of an
+ * ORBmatcher(_, check_orientation) for j < nnb (nnb <= 32; a slot may repeat and may be slot1), in
+ * one upload, one download and one synchronisation.  has_mp1[i] = pKF1->GetMapPoint(i) != NULL,
+ * has_mp2[j][i] likewise for neighbour j (may be NULL where that keyframe has no features).
+ * F12 [nnb][9] row-major and epipole [nnb][2] = {ex, ey} (:664-670) are the caller's: nothing is
+ * derived from poses here.  match_out[j][n1] = vMatches12 (the feature of keyframe 2 or -1; the pair
+ * list of :816-821 is its ascending read), nmatches[j] = the return value.  mvScaleFactors and
+ * mvLevelSigma2 are the context's.  The line and epipole tests are written with the fused
+ * multiply-adds the reference binary shows; parity against the binary is UNPINNED.
+ * COEB_EINVAL, with nothing written, for a slot that is empty, out of range or without geometry,
+ * nnb outside 0..32 or a missing pointer; nnb == 0 or a keyframe without features: COEB_OK, counts 0. */
+int coeb_kfdb_search_triangulation(coeb_kfdb* db, int slot1, const uint8_t* has_mp1, const int32_t* slots2, int nnb,
+                                   const uint8_t* const* has_mp2, const float* F12, const float* epipole,
+                                   int only_stereo, int check_orientation, int32_t* match_out, int32_t* nmatches);
 
 /* The Frame fields Optimizer::PoseOptimization reads (Optimizer.cc:276-357). */
 typedef struct {
