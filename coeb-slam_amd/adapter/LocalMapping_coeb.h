@@ -23,10 +23,29 @@
  * the caller's ComputeF12) and fills one vMatchedPairs per neighbour.  A neighbour that is not in
  * the store gets no pairs.  The triangulation stays the caller's.  The line and epipole tests use
  * the fused forms seen in the reference binary; parity against it is UNPINNED.
+ *
+ * The two loops of LocalMapping::SearchInNeighbors (src/LocalMapping.cc:455-535):
+ *   coeb::FuseSearch   the snapshot of a point list (under MapPoint::mGlobalMutex) and one
+ *                      coeb_kfdb_fuse_search over any number of (keyframe, skip) jobs on it;
+ *   coeb::Fuse         ORBmatcher::Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:826-976): one job, then
+ *                      the reference's loop replayed on the host with the search results;
+ *   coeb::FuseTargets  Fuse(vpTargetKFs[j], vpMapPointMatches) for j in order: one call for all targets,
+ *                      the replay target by target, and a further call whenever a Replace changed the
+ *                      descriptor of a listed point before a later target looks at it.
+ * The search (bestIdx, bestDist) reads only the point's position, normal, distances and descriptor, the
+ * keyframe's constant features and pose, and the camera; the skips (!pMP, isBad(), IsInKeyFrame) and the
+ * action (GetMapPoint(bestIdx), Observations(), Replace / AddObservation) are evaluated by the replay at
+ * the moment the reference evaluates them.  MapPoint::Replace ends in ComputeDistinctiveDescriptors on the
+ * survivor, so a survivor's descriptor can change.  Within one Fuse call that cannot matter: a survivor
+ * is an earlier point of the list or a point of the keyframe, and IsInKeyFrame skips it.  Across targets
+ * it can, which FuseTargets detects by comparing GetDescriptor() of the survivor with the uploaded bytes.
+ * A keyframe that was never added to the store fuses nothing (as s3l's neighbour without pairs); a
+ * keyframe that is in the store always takes the device path.
  */
 #ifndef COEB_ADAPTER_LOCALMAPPING_H
 #define COEB_ADAPTER_LOCALMAPPING_H
 
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <stdexcept>
@@ -191,6 +210,252 @@ inline int SearchForTriangulationNeighbors(KeyFrameStore<KeyFrameT>& store, KeyF
         }
     }
     return total;
+}
+
+// The point list of a fuse call as the device reads it; descriptor keeps the uploaded bytes.
+struct FusePointSnapshot {
+    std::vector<uint8_t> valid, descriptor;
+    std::vector<float> pos, normal, maxd, mind;
+    coeb_fuse_points c() const
+    {
+        return coeb_fuse_points{(int32_t)valid.size(), valid.data(), pos.data(), normal.data(), maxd.data(), mind.data(),
+                                descriptor.data()};
+    }
+};
+
+template <class MapPointT>
+inline void fuse_snapshot_point(FusePointSnapshot& s, size_t i, MapPointT* pMP)
+{
+    s.valid[i] = pMP && !pMP->isBad();
+    s.maxd[i] = s.mind[i] = 1.f;
+    if (!s.valid[i]) return;
+    const cv::Mat p = pMP->GetWorldPos(), nrm = pMP->GetNormal(), d = pMP->GetDescriptor();
+    for (int k = 0; k < 3; ++k) {
+        s.pos[3 * i + k] = p.template at<float>(k);
+        s.normal[3 * i + k] = nrm.template at<float>(k);
+    }
+    s.maxd[i] = pMP->GetMaxDistance();
+    s.mind[i] = pMP->GetMinDistance();
+    if (d.empty()) s.valid[i] = 0;                   // no descriptor yet: nothing to compare (the reference would read an empty Mat)
+    else std::memcpy(&s.descriptor[32 * i], d.template ptr<uint8_t>(0), 32);
+}
+
+template <class MapPointT>
+inline FusePointSnapshot fuse_snapshot(const std::vector<MapPointT*>& vpMapPoints)
+{
+    const size_t n = vpMapPoints.size();
+    FusePointSnapshot s;
+    s.valid.assign(n, 0); s.descriptor.assign(n * 32, 0);
+    s.pos.assign(n * 3, 0.f); s.normal.assign(n * 3, 0.f); s.maxd.assign(n, 1.f); s.mind.assign(n, 1.f);
+    std::unique_lock<std::mutex> lock(MapPointT::mGlobalMutex);
+    for (size_t i = 0; i < n; ++i) fuse_snapshot_point(s, i, vpMapPoints[i]);
+    return s;
+}
+
+template <class KeyFrameT>
+inline coeb_camera fuse_camera(KeyFrameT* pKF)
+{
+    return coeb_camera{pKF->fx, pKF->fy, pKF->cx, pKF->cy, pKF->mbf, (float)pKF->mnMinX, (float)pKF->mnMaxX,
+                       (float)pKF->mnMinY, (float)pKF->mnMaxY};
+}
+
+// One coeb_kfdb_fuse_search: points[first[j] .. first[j] + count[j]) against vpKFs[j], all under cam, for up to
+// COEB_FUSE_MAX_JOBS keyframes that are in the store (the caller has checked).  skip[j][i] = IsInKeyFrame at
+// the time of the call.  bestIdx[j] / bestDist[j] hold count[j] entries.
+template <class KeyFrameT, class MapPointT>
+inline void FuseSearch(KeyFrameStore<KeyFrameT>& store, const coeb_camera& cam, const FusePointSnapshot& snap,
+                       const std::vector<MapPointT*>& vpMapPoints, const std::vector<KeyFrameT*>& vpKFs,
+                       const std::vector<int>& first, const std::vector<int>& count, float th,
+                       std::vector<std::vector<int32_t> >& bestIdx, std::vector<std::vector<int32_t> >& bestDist)
+{
+    const size_t nj = vpKFs.size();
+    std::vector<coeb_fuse_job> jobs(nj);
+    std::vector<std::vector<uint8_t> > skip(nj);
+    size_t total = 0;
+    std::unique_lock<std::mutex> lock(store.mutex());
+    for (size_t j = 0; j < nj; ++j) {
+        KeyFrameT* pKF = vpKFs[j];
+        coeb_fuse_job& b = jobs[j];
+        b.slot = store.slot(pKF);
+        if (b.slot < 0) throw std::runtime_error("FuseSearch: a keyframe is not in the store");
+        const cv::Mat R = pKF->GetRotation(), t = pKF->GetTranslation(), O = pKF->GetCameraCenter();
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) b.Rcw[3 * r + c] = R.template at<float>(r, c);
+            b.tcw[r] = t.template at<float>(r);
+            b.Ow[r] = O.template at<float>(r);
+        }
+        b.first = first[j]; b.count = count[j];
+        skip[j].resize((size_t)count[j]);
+        for (int i = 0; i < count[j]; ++i) {
+            MapPointT* pMP = vpMapPoints[(size_t)first[j] + i];
+            skip[j][i] = snap.valid[(size_t)first[j] + i] && pMP->IsInKeyFrame(pKF);
+        }
+        b.skip = count[j] ? skip[j].data() : nullptr;
+        total += (size_t)count[j];
+    }
+    std::vector<int32_t> bi(total + 1), bd(total + 1);
+    const coeb_fuse_points pts = snap.c();
+    if (coeb_kfdb_fuse_search(store.handle(), &cam, &pts, jobs.data(), (int)nj, th, bi.data(), bd.data()) != COEB_OK)
+        throw std::runtime_error(coeb_last_error(store.ctx()));
+    bestIdx.assign(nj, std::vector<int32_t>());
+    bestDist.assign(nj, std::vector<int32_t>());
+    size_t at = 0;
+    for (size_t j = 0; j < nj; ++j) {
+        bestIdx[j].assign(bi.begin() + at, bi.begin() + at + count[j]);
+        bestDist[j].assign(bd.begin() + at, bd.begin() + at + count[j]);
+        at += (size_t)count[j];
+    }
+}
+
+// The tail of ORBmatcher::Fuse's loop body (:953-971) for one point with a match; *survivor = the point a
+// Replace kept (its descriptor was recomputed), else NULL.
+template <class KeyFrameT, class MapPointT>
+inline void fuse_act(KeyFrameT* pKF, MapPointT* pMP, int bestIdx, MapPointT** survivor)
+{
+    *survivor = nullptr;
+    MapPointT* pMPinKF = pKF->GetMapPoint(bestIdx);
+    if (pMPinKF) {
+        if (!pMPinKF->isBad()) {
+            if (pMPinKF->Observations() > pMP->Observations()) {
+                pMP->Replace(pMPinKF);
+                *survivor = pMPinKF;
+            } else {
+                pMPinKF->Replace(pMP);
+                *survivor = pMP;
+            }
+        }
+    } else {
+        pMP->AddObservation(pKF, bestIdx);
+        pKF->AddMapPoint(pMP, bestIdx);
+    }
+}
+
+// ORBmatcher::Fuse(pKF, vpMapPoints, th): one device call, then the reference's loop with its own skips.
+template <class KeyFrameT, class MapPointT>
+inline int Fuse(KeyFrameStore<KeyFrameT>& store, KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, float th = 3.0f)
+{
+    {
+        std::unique_lock<std::mutex> lock(store.mutex());
+        if (store.slot(pKF) < 0) return 0;               // never added: nothing fused
+    }
+    const int n = (int)vpMapPoints.size();
+    if (!n) return 0;
+    const FusePointSnapshot snap = fuse_snapshot(vpMapPoints);
+    std::vector<std::vector<int32_t> > bi, bd;
+    FuseSearch(store, fuse_camera(pKF), snap, vpMapPoints, std::vector<KeyFrameT*>(1, pKF), std::vector<int>(1, 0),
+               std::vector<int>(1, n), th, bi, bd);
+    int nFused = 0;
+    for (int i = 0; i < n; ++i) {
+        MapPointT* pMP = vpMapPoints[i];
+        if (!pMP) continue;
+        if (pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;
+        if (!snap.valid[i] || bi[0][i] < 0) continue;
+        MapPointT* survivor;
+        fuse_act(pKF, pMP, bi[0][i], &survivor);
+        nFused++;
+    }
+    return nFused;
+}
+
+// for (pKFi : vpTargetKFs) matcher.Fuse(pKFi, vpMapPointMatches) (LocalMapping.cc:497-503) in one device call per
+// COEB_FUSE_MAX_JOBS targets, plus one call whenever a listed point's descriptor changed before a later target
+// reads it.  vnFused (may be NULL) receives nFused per target.  Returns the number of device calls.
+template <class KeyFrameT, class MapPointT>
+inline int FuseTargets(KeyFrameStore<KeyFrameT>& store, KeyFrameT* pKFcur, const std::vector<KeyFrameT*>& vpTargetKFs,
+                       const std::vector<MapPointT*>& vpMapPointMatches, float th = 3.0f, std::vector<int>* vnFused = nullptr,
+                       bool bRequery = true)
+{
+    const int n = (int)vpMapPointMatches.size(), T = (int)vpTargetKFs.size();
+    if (vnFused) vnFused->assign((size_t)T, 0);
+    if (!n || !T) return 0;
+    std::vector<uint8_t> stored((size_t)T);
+    {
+        std::unique_lock<std::mutex> lock(store.mutex());
+        for (int j = 0; j < T; ++j) stored[j] = store.slot(vpTargetKFs[j]) >= 0;
+    }
+    const coeb_camera cam = fuse_camera(pKFcur);
+    FusePointSnapshot snap = fuse_snapshot(vpMapPointMatches);
+    std::map<MapPointT*, int> index;                     // pointer -> first index in the list
+    for (int i = n - 1; i >= 0; --i)
+        if (vpMapPointMatches[i]) index[vpMapPointMatches[i]] = i;
+    std::vector<std::vector<int32_t> > bi((size_t)T), bd((size_t)T);
+    std::vector<uint8_t> stale((size_t)n, 0);
+    int nstale = 0, ncalls = 0, have = 0;                // results of targets [0, have) are in bi
+    for (int j = 0; j < T; ++j) {
+        if (!stored[j]) continue;                        // never added: nothing fused
+        KeyFrameT* pKF = vpTargetKFs[j];
+        if (j >= have) {                                 // the next first call: targets j .. over the whole list
+            std::vector<KeyFrameT*> kfs;
+            std::vector<int> which;
+            for (int k = j; k < T && (int)kfs.size() < COEB_FUSE_MAX_JOBS; ++k)
+                if (stored[k]) { kfs.push_back(vpTargetKFs[k]); which.push_back(k); }
+            if (nstale) {                                // every point afresh: the marks are cleared
+                snap = fuse_snapshot(vpMapPointMatches);
+                std::fill(stale.begin(), stale.end(), 0);
+                nstale = 0;
+            }
+            std::vector<std::vector<int32_t> > ri, rd;
+            FuseSearch(store, cam, snap, vpMapPointMatches, kfs, std::vector<int>(kfs.size(), 0),
+                       std::vector<int>(kfs.size(), n), th, ri, rd);
+            ncalls++;
+            for (size_t q = 0; q < which.size(); ++q) { bi[which[q]].swap(ri[q]); bd[which[q]].swap(rd[q]); }
+            have = which.back() + 1;
+        }
+        int nFused = 0;
+        for (int i = 0; i < n; ++i) {
+            MapPointT* pMP = vpMapPointMatches[i];
+            if (!pMP) continue;
+            if (pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;
+            if (stale[i] && bRequery) {
+                // the stale points, with their descriptors of now, against the targets j .. have - 1
+                std::vector<int> idx;
+                for (int k = 0; k < n; ++k)
+                    if (stale[k]) idx.push_back(k);
+                std::vector<MapPointT*> pts(idx.size());
+                for (size_t q = 0; q < idx.size(); ++q) pts[q] = vpMapPointMatches[idx[q]];
+                const FusePointSnapshot fresh = fuse_snapshot(pts);
+                std::vector<KeyFrameT*> kfs;
+                std::vector<int> which;
+                for (int k = j; k < have; ++k)
+                    if (stored[k]) { kfs.push_back(vpTargetKFs[k]); which.push_back(k); }
+                std::vector<std::vector<int32_t> > ri, rd;
+                FuseSearch(store, cam, fresh, pts, kfs, std::vector<int>(kfs.size(), 0),
+                           std::vector<int>(kfs.size(), (int)idx.size()), th, ri, rd);
+                ncalls++;
+                for (size_t w = 0; w < which.size(); ++w)
+                    for (size_t q = 0; q < idx.size(); ++q) {
+                        bi[which[w]][idx[q]] = ri[w][q];
+                        bd[which[w]][idx[q]] = rd[w][q];
+                    }
+                for (size_t q = 0; q < idx.size(); ++q) {
+                    const int k = idx[q];
+                    snap.valid[k] = fresh.valid[q];
+                    std::memcpy(&snap.descriptor[32 * k], &fresh.descriptor[32 * q], 32);
+                    stale[k] = 0;
+                }
+                nstale = 0;
+            }
+            if (!snap.valid[i] || bi[j][i] < 0) continue;
+            MapPointT* survivor;
+            fuse_act(pKF, pMP, bi[j][i], &survivor);
+            nFused++;
+            if (survivor) {
+                typename std::map<MapPointT*, int>::const_iterator it = index.find(survivor);
+                if (it != index.end()) {
+                    const cv::Mat d = survivor->GetDescriptor();
+                    for (int k = it->second; k < n; ++k) {           // every index the survivor is listed at
+                        if (vpMapPointMatches[k] != survivor || stale[k]) continue;
+                        if (d.empty() || std::memcmp(&snap.descriptor[32 * k], d.template ptr<uint8_t>(0), 32)) {
+                            stale[k] = 1;
+                            nstale++;
+                        }
+                    }
+                }
+            }
+        }
+        if (vnFused) (*vnFused)[j] = nFused;
+    }
+    return ncalls;
 }
 
 }  // namespace coeb

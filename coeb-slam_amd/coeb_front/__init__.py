@@ -78,7 +78,7 @@ ABI_SYMBOLS = [
     "coeb_match_bow",
     "coeb_bow_vector", "coeb_kfdb_create", "coeb_kfdb_destroy", "coeb_kfdb_add", "coeb_kfdb_erase", "coeb_kfdb_clear",
     "coeb_kfdb_size", "coeb_kfdb_query", "coeb_match_bow_kfdb", "coeb_kfdb_set_geometry",
-    "coeb_kfdb_search_triangulation",
+    "coeb_kfdb_search_triangulation", "coeb_kfdb_fuse_search",
     "coeb_search_local_points", "coeb_track_local_map", "coeb_track_reference_keyframe",
     "coeb_track_motion_model", "coeb_reloc_refine",
     "coeb_rgbd_stream_create", "coeb_rgbd_stream_destroy", "coeb_rgbd_stream_reset", "coeb_rgbd_stream_frame",
@@ -172,6 +172,19 @@ class BowFrameC(C.Structure):
 class KfdbKeyFrameC(C.Structure):
     _fields_ = [("n", C.c_int32), ("descriptor", C.c_void_p), ("node_id", C.c_void_p), ("angle", C.c_void_p),
                 ("bow_word", C.c_void_p), ("bow_value", C.c_void_p), ("nw", C.c_int32)]
+
+
+class FusePointsC(C.Structure):
+    _fields_ = [("n", C.c_int32), ("valid", C.c_void_p), ("world_pos", C.c_void_p), ("normal", C.c_void_p),
+                ("max_distance", C.c_void_p), ("min_distance", C.c_void_p), ("descriptor", C.c_void_p)]
+
+
+class FuseJobC(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3),
+                ("first", C.c_int32), ("count", C.c_int32), ("skip", C.c_void_p)]
+
+
+FUSE_MAX_JOBS = 128     # COEB_FUSE_MAX_JOBS
 
 
 class RgbdStreamOutC(C.Structure):
@@ -326,6 +339,8 @@ def lib():
         L.coeb_kfdb_search_triangulation.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                                      C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                                      C.c_void_p, C.c_void_p]
+        L.coeb_kfdb_fuse_search.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(FusePointsC), C.POINTER(FuseJobC),
+                                            C.c_int, C.c_float, C.c_void_p, C.c_void_p]
         L.coeb_profile_enable.argtypes = [C.c_void_p, C.c_int]
         L.coeb_profile_reset.argtypes = [C.c_void_p]
         L.coeb_profile_read.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
@@ -1498,6 +1513,53 @@ class KeyFrameDatabase:
             _p(F12) if nnb else None, _p(epipole) if nnb else None, int(bool(only_stereo)), int(bool(check_orientation)),
             _p(out) if out.size else None, _p(nm)))
         return out, nm[:nnb]
+
+    def fuse_search(self, cam, points, jobs, th=3.0):
+        """The search of ORBmatcher::Fuse(KF[slot], vpMapPoints[first : first + count], th) for every job in one
+        call (LocalMapping::SearchInNeighbors).  points: dict(valid [n] = pMP && !isBad(), world_pos [n, 3],
+        normal [n, 3], max_distance [n] = mfMaxDistance, min_distance [n], descriptor [n, 32]).  jobs: dicts
+        (slot, Rcw [3, 3], tcw [3], Ow [3], first = 0, count = to the list's end, skip = None or [count] =
+        IsInKeyFrame).  -> (best_idx, best_dist): one int32 array per job; best_idx is bestIdx where bestDist <=
+        TH_LOW else -1, best_dist is bestDist (256: no candidate accepted, or the point was skipped or rejected)."""
+        valid = np.ascontiguousarray(points["valid"], np.uint8)
+        n = len(valid)
+        pos = np.ascontiguousarray(points["world_pos"], np.float32).reshape(n, 3)
+        nrm = np.ascontiguousarray(points["normal"], np.float32).reshape(n, 3)
+        mx = np.ascontiguousarray(points["max_distance"], np.float32)
+        mn = np.ascontiguousarray(points["min_distance"], np.float32)
+        desc = np.ascontiguousarray(points["descriptor"], np.uint8).reshape(n, 32)
+        if len(mx) != n or len(mn) != n:
+            raise ValueError("point arrays differ in length")
+        pc = FusePointsC(n, *[C.c_void_p(a.ctypes.data) if n else None for a in (valid, pos, nrm, mx, mn, desc)])
+        nj = len(jobs)
+        jc = (FuseJobC * max(nj, 1))()
+        keep, counts = [], []
+        for k, j in enumerate(jobs):
+            first = int(j.get("first", 0))
+            count = int(j["count"]) if j.get("count") is not None else n - first
+            jc[k].slot, jc[k].first, jc[k].count = int(j["slot"]), first, count
+            jc[k].Rcw[:] = np.asarray(j["Rcw"], np.float32).reshape(9).tolist()
+            jc[k].tcw[:] = np.asarray(j["tcw"], np.float32).reshape(3).tolist()
+            jc[k].Ow[:] = np.asarray(j["Ow"], np.float32).reshape(3).tolist()
+            if j.get("skip") is not None:
+                sk = np.ascontiguousarray(j["skip"], np.uint8)
+                if len(sk) != count:
+                    raise ValueError("skip of job %d has %d entries, its range %d" % (k, len(sk), count))
+                keep.append(sk)
+                jc[k].skip = sk.ctypes.data if count > 0 else None
+            counts.append(count)
+        total = sum(c for c in counts if c > 0)
+        bi = np.full(max(total, 1), -1, np.int32)
+        bd = np.full(max(total, 1), 256, np.int32)
+        c = cam if isinstance(cam, Camera) else Camera(*[float(x) for x in cam])
+        self.ctx.check(lib().coeb_kfdb_fuse_search(self.h, C.byref(c), C.byref(pc), jc if nj else None, nj, float(th),
+                                                   _p(bi) if total else None, _p(bd) if total else None))
+        out_i, out_d, o = [], [], 0
+        for cnt in counts:
+            out_i.append(bi[o:o + cnt].copy())
+            out_d.append(bd[o:o + cnt].copy())
+            o += cnt
+        return out_i, out_d
 
 
 class ORBmatcher:

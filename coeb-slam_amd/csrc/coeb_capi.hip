@@ -686,6 +686,23 @@ MatchBufs last_pair_bufs(coeb_ctx* c, const Staged& st, const LastPair& p, int c
 
 }  // namespace
 
+// declared in coeb_ctx.hpp: coeb_kfdb.hip calls it too
+MatchCam make_cam(const coeb_ctx* c, const coeb_camera* cam)
+{
+    MatchCam m;
+    memset(&m, 0, sizeof(m));
+    m.fx = cam->fx; m.fy = cam->fy; m.cx = cam->cx; m.cy = cam->cy; m.bf = cam->bf;
+    m.mb = cam->bf / cam->fx;                                       // Frame.cc:246
+    m.min_x = cam->min_x; m.max_x = cam->max_x; m.min_y = cam->min_y; m.max_y = cam->max_y;
+    m.grid_inv_w = (float)COEB_GRID_COLS / (cam->max_x - cam->min_x);   // Frame.cc:233-234
+    m.grid_inv_h = (float)COEB_GRID_ROWS / (cam->max_y - cam->min_y);
+    for (int l = 0; l < c->tab.nlevels; l++) m.scale[l] = c->tab.scale[l];
+    m.nlevels = c->tab.nlevels;
+    // mfLogScaleFactor = log(mfScaleFactor): std::log(float), canonical correctly rounded (DESIGN.md s2.1)
+    m.log_sf = (float)std::log((double)(float)c->tab.scale_factor);
+    return m;
+}
+
 extern "C" {
 
 int coeb_abi_version(void) { return COEB_ABI_VERSION; }
@@ -1328,22 +1345,6 @@ int coeb_rgbd_stream_frame(coeb_rgbd_stream* st, const uint8_t* img, size_t img_
     frame_tail_copy_out(c, R, std::min(n, guess), out->kp, out->kp_un, out->desc, out->u_right, out->depth);
     if (n > out->cap) return set_err(c, COEB_ERANGE, "keypoint output capacity too small");
     return COEB_OK;
-}
-
-static MatchCam make_cam(const coeb_ctx* c, const coeb_camera* cam)
-{
-    MatchCam m;
-    memset(&m, 0, sizeof(m));
-    m.fx = cam->fx; m.fy = cam->fy; m.cx = cam->cx; m.cy = cam->cy; m.bf = cam->bf;
-    m.mb = cam->bf / cam->fx;                                       // Frame.cc:246
-    m.min_x = cam->min_x; m.max_x = cam->max_x; m.min_y = cam->min_y; m.max_y = cam->max_y;
-    m.grid_inv_w = (float)COEB_GRID_COLS / (cam->max_x - cam->min_x);   // Frame.cc:233-234
-    m.grid_inv_h = (float)COEB_GRID_ROWS / (cam->max_y - cam->min_y);
-    for (int l = 0; l < c->tab.nlevels; l++) m.scale[l] = c->tab.scale[l];
-    m.nlevels = c->tab.nlevels;
-    // mfLogScaleFactor = log(mfScaleFactor): std::log(float), canonical correctly rounded (DESIGN.md s2.1)
-    m.log_sf = (float)std::log((double)(float)c->tab.scale_factor);
-    return m;
 }
 
 int coeb_match_lastframe(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe* cur, const coeb_lastframe* last,

@@ -233,6 +233,8 @@ void join_pose(coeb_ctx* c);                    // the context stream waits for 
 int quiesce(coeb_ctx* c);                       // nothing enqueued by the context is running afterwards
 const SideStream* side_stream(coeb_ctx* c);     // launch_extract's side stream, or null when disabled
 void kfdb_release_all(coeb_ctx* c);             // coeb_kfdb.hip: coeb_destroy frees the databases' device memory
+// coeb_capi.hip: the camera, the context's scale factors and mfLogScaleFactor as the matchers read them
+MatchCam make_cam(const coeb_ctx* c, const coeb_camera* cam);
 
 // a holds at least max(count * sizeof(T), 256) bytes afterwards; it only grows
 template <class T>

@@ -5,6 +5,8 @@
 //   SearchByBoW against every candidate                  src/Tracking.cc:1449-1470 (k_match_bow_db)
 //   SearchForTriangulation against every neighbour       src/ORBmatcher.cc:657-824, 140-157 (k_tri_match,
 //                                                        k_tri_rot)
+//   the search of ORBmatcher::Fuse for many (keyframe,   src/ORBmatcher.cc:826-951, src/KeyFrame.cc:569-608
+//   point list) pairs                                    (k_fuse_grid, k_fuse)
 // What a keyframe contributes never changes after KeyFrame::ComputeBoW, so it is uploaded once
 // (descriptors, angles, BowVector) and its feature-vector CSR is built once.  There is no inverted
 // file: mnRelocWords of a keyframe is |words(F) & words(KF)|, counted per keyframe.  The scoring
@@ -17,6 +19,7 @@
 
 #include "coeb_bow_dev.hpp"
 #include "coeb_kfdb_host.hpp"
+#include "coeb_track_dev.hpp"
 
 // One slot of the slab, by byte offset (mf = max_features): value[mf] f64, word[mf] i32,
 // angle[mf] f32, descriptor[mf][32], the CSR (csr_ints(mf) ints, laid out for the keyframe's own n).
@@ -47,6 +50,11 @@ struct coeb_kfdb {
     uint8_t* geo = nullptr;
     size_t geo_stride = 0;
     std::vector<uint8_t> has_geo;   // the slot's keyframe has its geometry
+    // coeb_kfdb_fuse_search: the keyframe's 64 x 48 feature grid as a CSR, fuse_grid_ints(mf) ints per
+    // slot, allocated by the first call (null before); grid_rec: the bounds each was built with
+    uint8_t* grid = nullptr;
+    size_t grid_stride = 0;
+    std::vector<KfdbGridRec> grid_rec;
 };
 
 namespace {
@@ -373,6 +381,236 @@ __global__ __launch_bounds__(kCsrThreads) void k_tri_rot(TriArgs a, int n1)
                    &s_cnt);
 }
 
+// ============================== k_fuse_grid ==============================
+// Frame::AssignFeaturesToGrid (Frame.cc:396-411; a KeyFrame copies the Frame's grid) of one stored
+// keyframe per workgroup, as a CSR in cell order (ix outer, iy inner, index order inside a cell):
+// cell[c] = the start of cell c = ix * 48 + iy in sorted[], cell[3072] = the listed features.  A feature
+// whose PosInGrid (round) falls outside the grid is listed nowhere.  The counting sort is that of
+// stage_grid (coeb_match.hip): counts by LDS atomics, a block scan, a scatter through per-cell cursors
+// and an insertion sort of every (short) cell range, since the scatter's order inside a cell is any.
+constexpr int kGridThreads = 256;
+constexpr int kGridCpt = COEB_GRID_CELLS / kGridThreads;
+static_assert(COEB_GRID_CELLS == kGridCpt * kGridThreads, "whole cells per thread");
+inline size_t fuse_grid_ints(int mf) { return (size_t)COEB_GRID_CELLS + 1 + (size_t)mf; }
+
+struct FuseGridArgs {
+    KfdbView v;
+    const uint8_t* geo; size_t geo_stride;
+    uint8_t* grid; size_t grid_stride;
+    const int* slots;           // [gridDim.x]
+    float min_x, min_y, inv_w, inv_h;
+};
+
+__global__ __launch_bounds__(kGridThreads) void k_fuse_grid(FuseGridArgs a)
+{
+    __shared__ int s_start[COEB_GRID_CELLS + 1];
+    __shared__ int s_cur[COEB_GRID_CELLS];
+    __shared__ int s_sort[kBowMax + 1];
+    __shared__ int s_wsum[kGridThreads / 64];
+    const int tid = threadIdx.x, slot = a.slots[blockIdx.x];
+    const int n = min(a.v.meta[slot * 4], a.v.mf);
+    const KfdbGeo* geo = reinterpret_cast<const KfdbGeo*>(a.geo + slot * a.geo_stride);
+    int* cell = reinterpret_cast<int*>(a.grid + slot * a.grid_stride);
+    int* sorted = cell + COEB_GRID_CELLS + 1;
+    const auto cell_of = [&](int i) {
+        const KfdbGeo g = geo[i];
+        const int px = (int)roundf((g.x - a.min_x) * a.inv_w);          // PosInGrid (Frame.cc:560-571)
+        const int py = (int)roundf((g.y - a.min_y) * a.inv_h);
+        return (px >= 0 && px < COEB_GRID_COLS && py >= 0 && py < COEB_GRID_ROWS) ? px * COEB_GRID_ROWS + py : -1;
+    };
+    for (int c = tid; c <= COEB_GRID_CELLS; c += kGridThreads) s_start[c] = 0;
+    __syncthreads();
+    for (int i = tid; i < n; i += kGridThreads) {
+        const int c = cell_of(i);
+        if (c >= 0) atomicAdd(&s_start[c + 1], 1);
+    }
+    __syncthreads();
+    {                                          // s_start[c + 1] = the end of cell c
+        const int lane = tid & 63, wv = tid >> 6, c0 = 1 + kGridCpt * tid;
+        int cnt[kGridCpt];
+        int v = 0;
+#pragma unroll
+        for (int k = 0; k < kGridCpt; k++) { cnt[k] = s_start[c0 + k]; v += cnt[k]; }
+        for (int o = 1; o < 64; o <<= 1) {
+            const int y = __shfl_up(v, o, 64);
+            if (lane >= o) v += y;
+        }
+        if (lane == 63) s_wsum[wv] = v;
+        __syncthreads();
+        int end = v;
+        for (int w = 0; w < wv; w++) end += s_wsum[w];
+#pragma unroll
+        for (int k = kGridCpt - 1; k >= 0; k--) { s_start[c0 + k] = end; end -= cnt[k]; }
+    }
+    __syncthreads();
+    for (int c = tid; c < COEB_GRID_CELLS; c += kGridThreads) s_cur[c] = s_start[c];
+    __syncthreads();
+    for (int i = tid; i < n; i += kGridThreads) {
+        const int c = cell_of(i);
+        if (c >= 0) s_sort[atomicAdd(&s_cur[c], 1)] = i;
+    }
+    __syncthreads();
+    for (int c = tid; c < COEB_GRID_CELLS; c += kGridThreads) {
+        const int b = s_start[c], e = s_start[c + 1];
+        for (int x = b + 1; x < e; x++) {
+            const int key = s_sort[x];
+            int y = x - 1;
+            while (y >= b && s_sort[y] > key) { s_sort[y + 1] = s_sort[y]; y--; }
+            s_sort[y + 1] = key;
+        }
+    }
+    __syncthreads();
+    for (int c = tid; c <= COEB_GRID_CELLS; c += kGridThreads) cell[c] = s_start[c];
+    const int ng = s_start[COEB_GRID_CELLS];
+    for (int e = tid; e < ng; e += kGridThreads) sorted[e] = s_sort[e];
+}
+
+// ================================= k_fuse =================================
+// The search of ORBmatcher::Fuse (:843-950) over (point tile, job): kFuseLanes lanes per point, every
+// lane with the point's projection (:853-891) in registers.  A window spans about 2 * th * scale / 10 px
+// + 1 grid columns of a few features each, so the lanes of a point take the window's columns ix0 + lane,
+// ix0 + lane + kFuseLanes, .. and walk each column's CSR range [cell[ix][iy0], cell[ix][iy1 + 1]) alone.
+// The CSR position of a candidate grows along GetFeaturesInArea's enumeration (ix outer, iy inner, index
+// order in a cell), so the min over (dist << 16 | position) is the smallest distance and the first of
+// equals in that order: the reference's strict dist < bestDist.  A candidate that fails the window, the
+// level or the chi-square test is skipped before its distance is taken.  No LDS.
+// The four lanes of a point repeat its projection (one double sqrt, one double log); k_fuse takes 13 us per
+// launch for 10 and for 30 targets of 1000 features, the floor of a short launch, so a
+// broadcast from one lane was not tried.
+// Float forms: Rcw * P + tcw as cv::Mat's small gemm (float products summed left to
+// right, tcw added in double); invz = 1 / z in float, x = X * invz, u = fma(fx, x, cx), ur = fma(-bf,
+// invz, u); cv::norm and Mat::dot in double, the dot compared in double with 0.5 * dist3D; PredictScale's
+// (float)log((double)ratio) / mfLogScaleFactor; e2 = fma(ex, ex, ey * ey), then fma(er, er, .); the float
+// product e2 * invSigma2 widened for the comparison with 7.8 / 5.99.
+constexpr int kFuseThreads = 256;
+constexpr int kFuseLanes = 4;
+constexpr int kFusePts = kFuseThreads / kFuseLanes;
+static_assert(kBowMax <= 0xFFFF, "a CSR position fits the key's low half");
+
+struct FuseArgs {
+    KfdbView v;
+    const uint8_t* geo; size_t geo_stride;
+    const uint8_t* grid; size_t grid_stride;
+    const KfdbFuseJob* jobs;
+    const uint8_t* skip;
+    const uint8_t* valid; const float* pos; const float* nrm; const float* maxd; const float* mind; const uint8_t* desc;
+    const float* inv_sigma2;    // [COEB_MAXL] mvInvLevelSigma2
+    MatchCam cam;
+    float th;
+    int* best_idx; int* best_dist;
+};
+
+__global__ __launch_bounds__(kFuseThreads) void k_fuse(FuseArgs a)
+{
+    const KfdbFuseJob* jb = a.jobs + blockIdx.y;
+    const int count = jb->count;
+    if ((int)blockIdx.x * kFusePts >= count) return;               // workgroup-uniform
+    const int pi = blockIdx.x * kFusePts + threadIdx.x / kFuseLanes, gl = threadIdx.x & (kFuseLanes - 1);
+    const bool live = pi < count;
+    const int i = jb->first + pi, slot = jb->slot;
+    const MatchCam& cam = a.cam;
+    const int* cell = reinterpret_cast<const int*>(a.grid + slot * a.grid_stride);
+    const int* sorted = cell + COEB_GRID_CELLS + 1;
+    uint32_t key = 0xFFFFFFFFu;
+    bool go = live && a.valid[i] && !(jb->skip_off >= 0 && a.skip[jb->skip_off + pi]);
+    float u = 0.f, v = 0.f, ur = 0.f, radius = 0.f;
+    int lvl = 0;
+    if (go) {
+        const float* P = a.pos + (int64_t)i * 3;
+        float Pc[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {                               // Rcw*p3Dw + tcw (:854)
+            float t = jb->Rcw[k * 3 + 0] * P[0] + jb->Rcw[k * 3 + 1] * P[1];
+            t = t + jb->Rcw[k * 3 + 2] * P[2];
+            Pc[k] = (float)((double)t + (double)jb->tcw[k]);
+        }
+        go = !(Pc[2] < 0.0f);                                       // :857
+        if (go) {
+            const float invz = 1.0f / Pc[2];
+            const float x = Pc[0] * invz, y = Pc[1] * invz;
+            u = __builtin_fmaf(cam.fx, x, cam.cx);
+            v = __builtin_fmaf(cam.fy, y, cam.cy);
+            go = u >= cam.min_x && u < cam.max_x && v >= cam.min_y && v < cam.max_y;   // IsInImage (:868)
+            ur = __builtin_fmaf(-cam.bf, invz, u);
+        }
+        if (go) {
+            const float PO[3] = {P[0] - jb->Ow[0], P[1] - jb->Ow[1], P[2] - jb->Ow[2]};
+            const float dist3D = (float)norm3(PO);
+            const float maxd = a.maxd[i], mind = a.mind[i];
+            go = !(dist3D < 0.8f * mind || dist3D > 1.2f * maxd);   // :879
+            if (go) {
+                const float* Pn = a.nrm + (int64_t)i * 3;
+                double dot = 0.0;
+                dot += (double)PO[0] * (double)Pn[0];
+                dot += (double)PO[1] * (double)Pn[1];
+                dot += (double)PO[2] * (double)Pn[2];
+                go = !(dot < 0.5 * (double)dist3D);                 // :885
+                if (go) {
+                    const float ratio = maxd / dist3D;              // PredictScale (MapPoint.cc:385-400)
+                    const int s = (int)ceilf((float)log((double)ratio) / cam.log_sf);
+                    lvl = s < 0 ? 0 : (s >= cam.nlevels ? cam.nlevels - 1 : s);
+                    radius = a.th * cam.scale[lvl];
+                }
+            }
+        }
+    }
+    if (go) {
+        // KeyFrame::GetFeaturesInArea (KeyFrame.cc:569-608); its four early returns leave the key as it is
+        const int x0 = max(0, (int)floorf(((u - cam.min_x) - radius) * cam.grid_inv_w));
+        const int x1 = min(COEB_GRID_COLS - 1, (int)ceilf(((u - cam.min_x) + radius) * cam.grid_inv_w));
+        const int y0 = max(0, (int)floorf(((v - cam.min_y) - radius) * cam.grid_inv_h));
+        const int y1 = min(COEB_GRID_ROWS - 1, (int)ceilf(((v - cam.min_y) + radius) * cam.grid_inv_h));
+        if (x0 < COEB_GRID_COLS && x1 >= 0 && y0 < COEB_GRID_ROWS && y1 >= 0) {
+            const KfdbGeo* geo = reinterpret_cast<const KfdbGeo*>(a.geo + slot * a.geo_stride);
+            const uint8_t* kdesc = a.v.desc(slot);
+            uint32_t q[8];
+            {
+                const uint4* d = reinterpret_cast<const uint4*>(a.desc + (int64_t)i * 32);
+                const uint4 d0 = d[0], d1 = d[1];
+                q[0] = d0.x; q[1] = d0.y; q[2] = d0.z; q[3] = d0.w;
+                q[4] = d1.x; q[5] = d1.y; q[6] = d1.z; q[7] = d1.w;
+            }
+            for (int ix = x0 + gl; ix <= x1; ix += kFuseLanes) {
+                const int c0 = cell[ix * COEB_GRID_ROWS + y0], c1 = cell[ix * COEB_GRID_ROWS + y1 + 1];
+                for (int e = c0; e < c1; e++) {
+                    const int idx = sorted[e];
+                    const KfdbGeo g = geo[idx];
+                    const float distx = g.x - u, disty = g.y - v;
+                    if (!(fabsf(distx) < radius && fabsf(disty) < radius)) continue;
+                    if (g.octave < lvl - 1 || g.octave > lvl) continue;             // :912
+                    const float ex = u - g.x, ey = v - g.y;
+                    float e2 = __builtin_fmaf(ex, ex, ey * ey);
+                    if (g.u_right >= 0) {
+                        const float er = ur - g.u_right;
+                        e2 = __builtin_fmaf(er, er, e2);
+                        if ((double)(e2 * a.inv_sigma2[g.octave]) > 7.8) continue;
+                    } else if ((double)(e2 * a.inv_sigma2[g.octave]) > 5.99) {
+                        continue;
+                    }
+                    uint32_t c[8];
+                    const uint4* d = reinterpret_cast<const uint4*>(kdesc + (int64_t)idx * 32);
+                    const uint4 d0 = d[0], d1 = d[1];
+                    c[0] = d0.x; c[1] = d0.y; c[2] = d0.z; c[3] = d0.w;
+                    c[4] = d1.x; c[5] = d1.y; c[6] = d1.z; c[7] = d1.w;
+                    key = min(key, ((uint32_t)hamming32(q, c) << 16) | (uint32_t)e);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int x = 1; x < kFuseLanes; x <<= 1) key = min(key, (uint32_t)__shfl_xor((int)key, x));
+    if (live && gl == 0) {
+        int bd = 256, bi = -1;
+        if (key != 0xFFFFFFFFu && (key >> 16) < 256u) {             // dist < bestDist from 256 (:902, :945)
+            bd = (int)(key >> 16);
+            bi = sorted[key & 0xFFFFu];
+        }
+        const int o = jb->out_off + pi;
+        a.best_dist[o] = bd;
+        a.best_idx[o] = bd <= TH_LOW ? bi : -1;
+    }
+}
+
 size_t slot_stride(int mf) { return ((size_t)mf * 48 + (size_t)csr_ints(mf) * 4 + 255) & ~(size_t)255; }
 
 int db_err(coeb_kfdb* db, const char* what)
@@ -392,14 +630,17 @@ int grow(coeb_kfdb* db, int want)
     int* meta = nullptr;
     int* q = nullptr;
     uint8_t* geo = nullptr;
+    uint8_t* gridp = nullptr;
     hipError_t e = hipMalloc(&slab, (size_t)ncap * db->v.stride);
     if (e == hipSuccess) e = hipMalloc(&meta, (size_t)ncap * 16);
     if (e == hipSuccess) e = hipMalloc(&q, (4 + 3 * (size_t)ncap) * 4);
     if (e == hipSuccess && db->geo) e = hipMalloc(&geo, (size_t)ncap * db->geo_stride);
+    if (e == hipSuccess && db->grid) e = hipMalloc(&gridp, (size_t)ncap * db->grid_stride);
     if (e != hipSuccess) {
         if (slab) (void)hipFree(slab);
         if (meta) (void)hipFree(meta);
         if (q) (void)hipFree(q);
+        if (geo) (void)hipFree(geo);
         return set_err(c, COEB_ENOMEM, std::string("hipMalloc kfdb: ") + hipGetErrorString(e));
     }
     HIP_TRY(c, hipMemsetAsync(meta, 0, (size_t)ncap * 16, s));
@@ -407,13 +648,16 @@ int grow(coeb_kfdb* db, int want)
         HIP_TRY(c, hipMemcpyAsync(slab, db->v.slab, (size_t)db->nslots * db->v.stride, hipMemcpyDeviceToDevice, s));
         HIP_TRY(c, hipMemcpyAsync(meta, db->v.meta, (size_t)db->nslots * 16, hipMemcpyDeviceToDevice, s));
         if (geo) HIP_TRY(c, hipMemcpyAsync(geo, db->geo, (size_t)db->nslots * db->geo_stride, hipMemcpyDeviceToDevice, s));
+        if (gridp) HIP_TRY(c, hipMemcpyAsync(gridp, db->grid, (size_t)db->nslots * db->grid_stride, hipMemcpyDeviceToDevice, s));
     }
     HIP_TRY(c, hipStreamSynchronize(s));
     if (db->v.slab) (void)hipFree(db->v.slab);
     if (db->v.meta) (void)hipFree(db->v.meta);
     if (db->q) (void)hipFree(db->q);
     if (db->geo) (void)hipFree(db->geo);
-    db->v.slab = slab; db->v.meta = meta; db->q = q; db->geo = geo; db->cap = ncap;
+    if (db->grid) (void)hipFree(db->grid);
+    db->v.slab = slab; db->v.meta = meta; db->q = q; db->geo = geo; db->grid = gridp; db->cap = ncap;
+    db->grid_rec.resize(ncap, KfdbGridRec{});
     db->used.resize(ncap, 0); db->has_geo.resize(ncap, 0); db->n.resize(ncap, 0); db->nd.resize(ncap, 0); db->seq.resize(ncap, 0);
     return 0;
 }
@@ -424,7 +668,8 @@ void release_device(coeb_kfdb* db)
     if (db->v.meta) (void)hipFree(db->v.meta);
     if (db->q) (void)hipFree(db->q);
     if (db->geo) (void)hipFree(db->geo);
-    db->v.slab = nullptr; db->v.meta = nullptr; db->q = nullptr; db->geo = nullptr;
+    if (db->grid) (void)hipFree(db->grid);
+    db->v.slab = nullptr; db->v.meta = nullptr; db->q = nullptr; db->geo = nullptr; db->grid = nullptr;
     db->cap = db->nslots = db->nkf = 0;
 }
 
@@ -510,6 +755,7 @@ int coeb_kfdb_add(coeb_kfdb* db, const coeb_kfdb_keyframe* kf, int* slot_out)
     HIP_TRY(c, hipStreamSynchronize(s));
     db->used[slot] = 1;
     db->has_geo[slot] = 0;
+    db->grid_rec[slot].built = 0;
     db->n[slot] = n;
     db->nd[slot] = reinterpret_cast<const int32_t*>(c->pin)[0];
     db->seq[slot] = db->next_seq++;
@@ -528,6 +774,7 @@ int coeb_kfdb_erase(coeb_kfdb* db, int slot)
     HIP_TRY(c, hipMemsetAsync(db->v.meta + slot * 4, 0, 16, main_stream(c)));
     db->used[slot] = 0;
     db->has_geo[slot] = 0;
+    db->grid_rec[slot].built = 0;
     db->n[slot] = db->nd[slot] = 0;
     db->nkf--;
     return COEB_OK;
@@ -541,6 +788,7 @@ int coeb_kfdb_clear(coeb_kfdb* db)
     HIP_TRY(c, hipMemsetAsync(db->v.meta, 0, (size_t)db->cap * 16, main_stream(c)));
     std::fill(db->used.begin(), db->used.end(), 0);
     std::fill(db->has_geo.begin(), db->has_geo.end(), 0);
+    std::fill(db->grid_rec.begin(), db->grid_rec.end(), KfdbGridRec{});
     std::fill(db->n.begin(), db->n.end(), 0);
     std::fill(db->nd.begin(), db->nd.end(), 0);
     db->nslots = db->nkf = 0;
@@ -701,6 +949,7 @@ int coeb_kfdb_set_geometry(coeb_kfdb* db, int slot, const coeb_keypoint* keys_un
         HIP_TRY(c, hipStreamSynchronize(s));       // the page-locked buffer is the next call's
     }
     db->has_geo[slot] = 1;
+    db->grid_rec[slot].built = 0;
     return COEB_OK;
 }
 
@@ -758,6 +1007,77 @@ int coeb_kfdb_search_triangulation(coeb_kfdb* db, int slot1, const uint8_t* has_
     if ((rc = st.finish(c, s, o_m, back_end, false))) return rc;
     memcpy(match_out, st.host<int32_t>(o_m), rows * 4);
     memcpy(nmatches, st.host<int32_t>(o_nm), (size_t)nnb * 4);
+    return COEB_OK;
+}
+
+// Uploaded: the point list, the job table, the skip bytes, mvInvLevelSigma2 and the slots whose grid is
+// built first.  Copied back: best_idx and best_dist, which k_fuse writes for every pair.
+int coeb_kfdb_fuse_search(coeb_kfdb* db, const coeb_camera* cam, const coeb_fuse_points* pts, const coeb_fuse_job* jobs,
+                          int njobs, float th, int32_t* best_idx, int32_t* best_dist)
+{
+    const std::string w("coeb_kfdb_fuse_search: ");
+    if (!db || !db->c) return db_err(db, (w + "invalid arguments").c_str());
+    coeb_ctx* c = db->c;
+    int code;
+    int64_t total;
+    const char* why = kfdb_fuse_check(db->used.data(), db->has_geo.data(), db->nslots, cam, pts, jobs, njobs, th, best_idx,
+                                      best_dist, &code, &total);
+    if (why) return set_err(c, code, w + why);
+    if (total == 0) return COEB_OK;
+    (void)hipSetDevice(c->device);
+    hipStream_t s = main_stream(c);
+    if (!db->grid) {
+        const size_t stride = (fuse_grid_ints(db->v.mf) * 4 + 255) & ~(size_t)255;
+        const hipError_t e = hipMalloc(&db->grid, (size_t)db->cap * stride);
+        if (e != hipSuccess) {
+            db->grid = nullptr;
+            return set_err(c, COEB_ENOMEM, std::string("hipMalloc kfdb grids: ") + hipGetErrorString(e));
+        }
+        db->grid_stride = stride;
+    }
+    std::vector<KfdbFuseJob> tab;
+    std::vector<uint8_t> skip;
+    std::vector<int32_t> build;
+    kfdb_fuse_pack(jobs, njobs, db->grid_rec.data(), cam, tab, skip, build);
+    const size_t n = (size_t)pts->n;
+    int max_count = 0;
+    for (const KfdbFuseJob& t : tab) max_count = std::max(max_count, t.count);
+    Staged st;
+    const size_t o_v = st.add(pts->valid, n), o_x = st.add(pts->world_pos, n * 12), o_nr = st.add(pts->normal, n * 12);
+    const size_t o_mx = st.add(pts->max_distance, n * 4), o_mn = st.add(pts->min_distance, n * 4);
+    const size_t o_d = st.add(pts->descriptor, n * 32);
+    const size_t o_tab = st.add(tab.data(), tab.size() * sizeof(KfdbFuseJob)), o_sk = st.add(skip.data(), skip.size());
+    const size_t o_is = st.add(c->tab.inv_sigma2, sizeof(float) * COEB_MAXL);
+    const size_t o_bs = st.add(build.data(), build.size() * 4);
+    const size_t o_bi = st.take((size_t)total * 4), o_bd = st.take((size_t)total * 4);
+    const size_t back_end = st.end();
+    int rc;
+    if ((rc = st.stage(c, s, false))) return rc;
+    const MatchCam mc = make_cam(c, cam);
+    if (!build.empty()) {
+        FuseGridArgs g;
+        g.v = db->v; g.geo = db->geo; g.geo_stride = db->geo_stride; g.grid = db->grid; g.grid_stride = db->grid_stride;
+        g.slots = st.dev<int>(o_bs);
+        g.min_x = mc.min_x; g.min_y = mc.min_y; g.inv_w = mc.grid_inv_w; g.inv_h = mc.grid_inv_h;
+        prof_begin(&c->hook, "k_fuse_grid", s);
+        hipLaunchKernelGGL(k_fuse_grid, dim3((unsigned)build.size()), dim3(kGridThreads), 0, s, g);
+        prof_end(&c->hook, s);
+    }
+    FuseArgs a;
+    a.v = db->v; a.geo = db->geo; a.geo_stride = db->geo_stride; a.grid = db->grid; a.grid_stride = db->grid_stride;
+    a.jobs = st.dev<KfdbFuseJob>(o_tab); a.skip = st.dev<uint8_t>(o_sk);
+    a.valid = st.dev<uint8_t>(o_v); a.pos = st.dev<float>(o_x); a.nrm = st.dev<float>(o_nr);
+    a.maxd = st.dev<float>(o_mx); a.mind = st.dev<float>(o_mn); a.desc = st.dev<uint8_t>(o_d);
+    a.inv_sigma2 = st.dev<float>(o_is); a.cam = mc; a.th = th;
+    a.best_idx = st.dev<int>(o_bi); a.best_dist = st.dev<int>(o_bd);
+    prof_begin(&c->hook, "k_fuse", s);
+    hipLaunchKernelGGL(k_fuse, dim3((max_count + kFusePts - 1) / kFusePts, njobs), dim3(kFuseThreads), 0, s, a);
+    prof_end(&c->hook, s);
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = st.finish(c, s, o_bi, back_end, false))) return rc;
+    for (const int32_t sl : build) db->grid_rec[sl] = KfdbGridRec{1, cam->min_x, cam->max_x, cam->min_y, cam->max_y};
+    memcpy(best_idx, st.host<int32_t>(o_bi), (size_t)total * 4);
+    memcpy(best_dist, st.host<int32_t>(o_bd), (size_t)total * 4);
     return COEB_OK;
 }
 

@@ -113,3 +113,84 @@ void kfdb_tri_pack(const int* n, const int32_t* slots2, int nnb, const uint8_t* 
         if (nj) std::copy(has_mp2[j], has_mp2[j] + nj, masks.begin() + tab[2 * j + 1]);
     }
 }
+
+// ---- Fuse's search over stored keyframes: packing and argument rules ----
+bool kfdb_grid_current(const KfdbGridRec& r, const coeb_camera* cam)
+{
+    return r.built && r.min_x == cam->min_x && r.max_x == cam->max_x && r.min_y == cam->min_y && r.max_y == cam->max_y;
+}
+
+const char* kfdb_fuse_check(const uint8_t* used, const uint8_t* geo, int nslots, const coeb_camera* cam,
+                            const coeb_fuse_points* pts, const coeb_fuse_job* jobs, int njobs, float th,
+                            const int32_t* best_idx, const int32_t* best_dist, int* code, int64_t* total)
+{
+    *code = COEB_EINVAL;
+    *total = 0;
+    if (!cam || !pts) return "missing camera or point list";
+    if (njobs < 0 || njobs > COEB_FUSE_MAX_JOBS) return "the job count lies outside 0..128";
+    if (!(th >= 0.0f) || !std::isfinite(th)) return "th is negative or not finite";
+    if (!std::isfinite(cam->min_x) || !std::isfinite(cam->max_x) || !std::isfinite(cam->min_y) ||
+        !std::isfinite(cam->max_y) || !(cam->max_x > cam->min_x) || !(cam->max_y > cam->min_y))
+        return "camera bounds are not finite with max > min";
+    const int n = pts->n;
+    if (n < 0) return "negative point count";
+    if (njobs && !jobs) return "missing job array";
+    if (n && (!pts->valid || !pts->world_pos || !pts->normal || !pts->max_distance || !pts->min_distance || !pts->descriptor))
+        return "missing point arrays";
+    int64_t sum = 0;
+    for (int j = 0; j < njobs; j++) {
+        const coeb_fuse_job& b = jobs[j];
+        if (b.slot < 0 || b.slot >= nslots || !used[b.slot]) return "no keyframe in a job's slot";
+        if (!geo[b.slot]) return "a job's slot has no geometry (coeb_kfdb_set_geometry)";
+        if (b.first < 0 || b.count < 0 || (int64_t)b.first + b.count > n) return "a job's range lies outside the list";
+        for (int k = 0; k < 9; k++)
+            if (!std::isfinite(b.Rcw[k])) return "a job's pose is not finite";
+        for (int k = 0; k < 3; k++)
+            if (!std::isfinite(b.tcw[k]) || !std::isfinite(b.Ow[k])) return "a job's pose is not finite";
+        sum += b.count;
+    }
+    if (sum && (!best_idx || !best_dist)) return "missing output arrays";
+    // PredictScale's (int)ceil(log(mfMaxDistance / dist) / mfLogScaleFactor) is undefined otherwise
+    for (int q = 0; q < n; q++) {
+        if (!pts->valid[q]) continue;
+        for (int k = 0; k < 3; k++)
+            if (!std::isfinite(pts->world_pos[3 * q + k]) || !std::isfinite(pts->normal[3 * q + k]))
+                return "non-finite position or normal of a valid point";
+        const float mn = pts->min_distance[q], mx = pts->max_distance[q];
+        if (!(mn > 0.0f && mn <= mx && std::isfinite(mx))) return "distance range of a valid point is not 0 < min <= max < inf";
+    }
+    *code = COEB_ERANGE;
+    if (sum > COEB_FUSE_MAX_PAIRS) return "more than COEB_FUSE_MAX_PAIRS (job, point) pairs";
+    if (n > COEB_FUSE_MAX_PAIRS) return "more than COEB_FUSE_MAX_PAIRS points";
+    *code = COEB_OK;
+    *total = sum;
+    return nullptr;
+}
+
+void kfdb_fuse_pack(const coeb_fuse_job* jobs, int njobs, const KfdbGridRec* rec, const coeb_camera* cam,
+                    std::vector<KfdbFuseJob>& tab, std::vector<uint8_t>& skip, std::vector<int32_t>& build)
+{
+    tab.assign((size_t)njobs, KfdbFuseJob{});
+    build.clear();
+    size_t bytes = 0;
+    int32_t out = 0;
+    for (int j = 0; j < njobs; j++) {
+        const coeb_fuse_job& b = jobs[j];
+        KfdbFuseJob& t = tab[j];
+        t.slot = b.slot; t.first = b.first; t.count = b.count; t.out_off = out; t.skip_off = -1;
+        std::copy(b.Rcw, b.Rcw + 9, t.Rcw);
+        std::copy(b.tcw, b.tcw + 3, t.tcw);
+        std::copy(b.Ow, b.Ow + 3, t.Ow);
+        out += b.count;
+        if (b.skip && b.count) {
+            t.skip_off = (int32_t)bytes;
+            bytes += ((size_t)b.count + 15) & ~(size_t)15;
+        }
+        if (b.count && !kfdb_grid_current(rec[b.slot], cam)) build.push_back(b.slot);
+    }
+    std::sort(build.begin(), build.end());
+    build.erase(std::unique(build.begin(), build.end()), build.end());
+    skip.assign(bytes, 0);
+    for (int j = 0; j < njobs; j++)
+        if (tab[j].skip_off >= 0) std::copy(jobs[j].skip, jobs[j].skip + jobs[j].count, skip.begin() + tab[j].skip_off);
+}

@@ -37,3 +37,24 @@ const char* kfdb_tri_check(const uint8_t* used, const uint8_t* geo, const int* n
 // kernel reads: tab[2 j] = slots2[j], tab[2 j + 1] = the offset of has_mp2[j] in masks.
 void kfdb_tri_pack(const int* n, const int32_t* slots2, int nnb, const uint8_t* const* has_mp2,
                    std::vector<uint8_t>& masks, std::vector<int32_t>& tab);
+
+// ---- LocalMapping::SearchInNeighbors' Fuse search over stored keyframes ----
+// One job as k_fuse reads it: the slot, the range of the list, where its results start, where its skip
+// bytes start in the packed skip array (-1: none), and the keyframe's pose.
+struct KfdbFuseJob { int32_t slot, first, count, out_off, skip_off; float Rcw[9], tcw[3], Ow[3]; };
+static_assert(sizeof(KfdbFuseJob) == 80, "the job table holds 80 bytes per job");
+
+// The bounds a slot's feature grid was built with (coeb_kfdb_fuse_search); built == 0: no grid.
+struct KfdbGridRec { uint8_t built; float min_x, max_x, min_y, max_y; };
+bool kfdb_grid_current(const KfdbGridRec& r, const coeb_camera* cam);
+
+// The rules of coeb_kfdb_fuse_search's arguments that need no device.  nullptr: the call may go on, with
+// *total = the sum of the counts; else the text of its error and *code = COEB_EINVAL or COEB_ERANGE.
+const char* kfdb_fuse_check(const uint8_t* used, const uint8_t* geo, int nslots, const coeb_camera* cam,
+                            const coeb_fuse_points* pts, const coeb_fuse_job* jobs, int njobs, float th,
+                            const int32_t* best_idx, const int32_t* best_dist, int* code, int64_t* total);
+
+// The job table, the skip bytes of all jobs one after the other at 16-byte rounded offsets, and the
+// distinct slots whose grid has to be built (rec[slot] not current for cam), ascending.
+void kfdb_fuse_pack(const coeb_fuse_job* jobs, int njobs, const KfdbGridRec* rec, const coeb_camera* cam,
+                    std::vector<KfdbFuseJob>& tab, std::vector<uint8_t>& skip, std::vector<int32_t>& build);

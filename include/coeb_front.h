@@ -107,6 +107,9 @@
  *                                      LocalMapping::CreateNewMapPoints  src/LocalMapping.cc:255-270,
  *                                      src/ORBmatcher.cc:657-824 (coeb_kfdb_set_geometry: the
  *                                      KeyFrame's mvKeysUn / mvuRight it reads)
+ *   coeb_kfdb_fuse_search           <- the search of ORBmatcher::Fuse (src/ORBmatcher.cc:826-951) for
+ *                                      the loops of LocalMapping::SearchInNeighbors
+ *                                      src/LocalMapping.cc:455-535
  *   coeb_tum_read_list            <- associate.py read_file_list  associate.py:49-69
  *   coeb_tum_associate              <- associate.py associate  associate.py:71-102 (host only)
  *
@@ -739,6 +742,49 @@ int coeb_kfdb_set_geometry(coeb_kfdb* db, int slot, const coeb_keypoint* keys_un
 int coeb_kfdb_search_triangulation(coeb_kfdb* db, int slot1, const uint8_t* has_mp1, const int32_t* slots2, int nnb,
                                    const uint8_t* const* has_mp2, const float* F12, const float* epipole,
                                    int only_stereo, int check_orientation, int32_t* match_out, int32_t* nmatches);
+
+/* ---- ORBmatcher::Fuse's search against many stored keyframes (src/ORBmatcher.cc:826-951, the loops of
+ * LocalMapping::SearchInNeighbors, src/LocalMapping.cc:455-535) ----
+ * The search half of Fuse (bestIdx, bestDist) is a pure function of the point, the keyframe's constant
+ * features, its pose and the camera; the skips and the action (Replace / AddObservation, :953-971)
+ * depend on the map's state and stay on the host (adapter/LocalMapping_coeb.h). */
+typedef struct {                       /* the MapPoints of a call, as Fuse reads them */
+    int32_t n;
+    const uint8_t* valid;              /* pMP && !pMP->isBad() */
+    const float* world_pos;            /* n x 3 */
+    const float* normal;               /* n x 3 */
+    const float* max_distance;         /* mfMaxDistance (invariance = 1.2f * it; PredictScale reads it raw) */
+    const float* min_distance;         /* mfMinDistance (0.8f * it) */
+    const uint8_t* descriptor;         /* n x 32 */
+} coeb_fuse_points;
+typedef struct {
+    int32_t slot;                      /* a stored keyframe with geometry */
+    float Rcw[9], tcw[3], Ow[3];       /* GetRotation / GetTranslation / GetCameraCenter: the caller's, nothing derived here */
+    int32_t first, count;              /* the points first .. first+count of the list */
+    const uint8_t* skip;               /* count bytes, pMP->IsInKeyFrame(pKF); may be NULL */
+} coeb_fuse_job;
+#define COEB_FUSE_MAX_JOBS 128
+/* The (job, point) pairs of one call, and the points of its list.  A pair costs 8 bytes of result and a
+ * point 56 bytes of upload in the page-locked staging buffer and on the device: at most 8 MiB + 56 MiB
+ * (about 64 MiB on each side).  128 targets over a list of 8192 points take 8.5 MiB. */
+#define COEB_FUSE_MAX_PAIRS (1 << 20)
+/* For job j and its point i (entry = the counts of the jobs before j, plus i - first): the search of
+ * Fuse(KF[slot], points, th) for that point.  best_idx = bestIdx where bestDist <= TH_LOW (50), else -1;
+ * best_dist = bestDist (256 when no candidate was accepted).  A point with valid 0 or skip 1, or one
+ * the projection tests reject, gets -1 / 256.  Jobs may repeat a slot and overlap in range.  One upload,
+ * one download, one synchronisation.  The keyframe's 64 x 48 feature grid (AssignFeaturesToGrid under
+ * cam's bounds) is built on the device by the first call that names the slot and kept with it; add on a
+ * reused slot, erase, clear and coeb_kfdb_set_geometry drop it, other bounds rebuild it.
+ * mvScaleFactors, mvInvLevelSigma2, mfLogScaleFactor and mnScaleLevels are the context's.  The float
+ * forms are listed in DESIGN.md s2.1; parity against the reference binary is UNPINNED.
+ * COEB_EINVAL, with nothing written: a slot that is empty, out of range or without geometry; njobs
+ * outside 0..128; a range outside the list; a missing array; th or a pose entry that is not finite (th
+ * negative); camera bounds that are not finite with max > min; a valid point with a non-finite position
+ * or normal, or whose distances are not 0 < min <= max < inf.  COEB_ERANGE: more than
+ * COEB_FUSE_MAX_PAIRS pairs or points.  njobs == 0 or all counts 0: COEB_OK. */
+int coeb_kfdb_fuse_search(coeb_kfdb* db, const coeb_camera* cam, const coeb_fuse_points* pts,
+                          const coeb_fuse_job* jobs, int njobs, float th,
+                          int32_t* best_idx, int32_t* best_dist);   /* job-major, sum of counts entries */
 
 /* The Frame fields Optimizer::PoseOptimization reads (Optimizer.cc:276-357). */
 typedef struct {
