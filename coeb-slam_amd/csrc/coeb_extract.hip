@@ -816,9 +816,12 @@ __device__ __forceinline__ int corner_strength(const uint8_t* c, int st)
 // One wave per cell, four cells per workgroup, no workgroup barriers.
 //  1. stage the cell ROI in the wave's LDS slab with aligned 32-bit loads (slab row starts at
 //     the ROI's x0 & 3, so words are stored unshifted);
-//  2. OpenCV's pre-test at minThFAST (ring pairs 0/8, 2/10, 4/12, 6/14 -- a necessary
-//     condition of a corner) on every detection pixel; survivors (a few %) are compacted
-//     (ballot) into a per-wave list, keeping row-major order;
+//  2. a two-pair pre-test at minThFAST (the compass pairs 0/8 and 4/12, the first half of
+//     OpenCV's own rejection -- a necessary condition of a corner) on every detection pixel;
+//     survivors (9 %) are compacted (ballot) into a per-wave list, keeping row-major order.  It
+//     is only a filter: step 3 decides, so its depth changes the work, never the output.  Two
+//     pairs pass 84 pixels per cell on the bench frames where four pass 49, and cost 20 VALU
+//     and 3 LDS reads less per pass (profiles/r10);
 //  3. exact strength M of the survivors; M > minThFAST <=> corner at minThFAST.  Corners go to
 //     Ms (all other pixels keep M = 0: not a corner at any threshold the reference uses) and,
 //     still in row-major order, to the corner list;
@@ -829,7 +832,11 @@ constexpr int kFastRowBytes = 72;          // >= 1 + 64 + 7 (slab byte = ROI col
 constexpr int kFastRowBytesM = 96;         // ROIs up to 46 wide: pixels in bytes 0..47, M in bytes 48..95
 // (24 dwords: the four rows a half-wave's pre-test reads land on disjoint banks, (a/4) mod 32)
 constexpr int kFastGuard = 16;             // bytes before each wave's slab (unaligned staging spill)
-constexpr int kFastEnt = 128;              // pre-test entries (u16: first pixel's offset / 4 | survivor mask << 12)
+// pre-test entries (u16: first pixel's offset / 4 | survivor mask << 12).  The list is drained
+// when a further pass could overflow it: 192 lets a cell with up to 128 entries before its last
+// pass drain once, at its end (with 128 the two-pair pre-test's survivors drained the list in
+// mid-cell and cost it its whole gain; 256 and 384 measured slower than 192, profiles/r10/ab.md)
+constexpr int kFastEnt = 192;
 constexpr int kFastSurv = 4 * 64 + 8;      // survivors of one 64-entry expansion, + the odd-count pad
 constexpr int kFastCorners = 256;          // corner list (more corners: NMS walks the whole window)
 constexpr int kFastLists = kFastSurv;      // u16 entries before the corner list
@@ -870,33 +877,18 @@ __device__ __forceinline__ us2 pk_min(us2 a, us2 b) { return __builtin_elementwi
 __device__ __forceinline__ us2 pk_max(us2 a, us2 b) { return __builtin_elementwise_max(a, b); }
 __device__ __forceinline__ us2 pk_subs(us2 a, us2 b) { return __builtin_elementwise_sub_sat(a, b); }
 
-// Three-input packed max / min of u16 pixel pairs (values <= 255) as v_pk_maximum3_f16 /
-// v_pk_minimum3_f16: read as f16 the patterns are positive denormals, ordered like the integers
-// (f16 denormals are not flushed), so one instruction replaces two v_pk_max/min_u16
-__device__ __forceinline__ us2 pk_max3(us2 a, us2 b, us2 c)
-{
-    uint32_t r;
-    asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(as_u32(a)), "v"(as_u32(b)), "v"(as_u32(c)));
-    return as_us2(r);
-}
-__device__ __forceinline__ us2 pk_min3(us2 a, us2 b, us2 c)
-{
-    uint32_t r;
-    asm("v_pk_minimum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(as_u32(a)), "v"(as_u32(b)), "v"(as_u32(c)));
-    return as_us2(r);
-}
-
-__device__ __forceinline__ uint32_t pretest_half(us2 v, us2 p0, us2 p8, us2 p2, us2 p10, us2 p4, us2 p12, us2 p6,
-                                                 us2 p14, us2 T)
+__device__ __forceinline__ uint32_t pretest_half(us2 v, us2 p0, us2 p8, us2 p4, us2 p12, us2 T)
 {
     // dark survives <=> v - md > t, bright <=> mb - v > t: one threshold test of their maximum
-    const us2 md = pk_max3(pk_min(p0, p8), pk_min(p2, p10), pk_max(pk_min(p4, p12), pk_min(p6, p14)));
-    const us2 mb = pk_min3(pk_max(p0, p8), pk_max(p2, p10), pk_min(pk_max(p4, p12), pk_max(p6, p14)));
+    const us2 md = pk_max(pk_min(p0, p8), pk_min(p4, p12));
+    const us2 mb = pk_min(pk_max(p0, p8), pk_max(p4, p12));
     return as_u32(pk_subs(pk_max(pk_subs(v, md), pk_subs(mb, v)), T));
 }
 
-// v_pk_maximum3_f16 / v_pk_minimum3_f16 on u16 patterns (see pk_max3) with the halves of the
-// second (S1) and / or third (S2) operand swapped by op_sel
+// Three-input packed max / min of u16 pixel pairs (values <= 255) as v_pk_maximum3_f16 /
+// v_pk_minimum3_f16: read as f16 the patterns are positive denormals, ordered like the integers
+// (f16 denormals are not flushed), so one instruction replaces two v_pk_max/min_u16.  The halves
+// of the second (S1) and / or third (S2) operand are swapped by op_sel
 template <bool kMax, bool S1, bool S2>
 __device__ __forceinline__ uint32_t pk3(uint32_t a, uint32_t b, uint32_t c)
 {
@@ -990,28 +982,22 @@ __device__ __forceinline__ int corner_strength_pos2(const uint8_t* c, int t)
 }
 
 // Same test, raw packed results: pixel q survives iff 16-bit half q of (lo, hi) is nonzero.
+// w points at the word three rows above the first pixel (the lowest word read, so every read takes
+// a positive immediate offset).
 template <int RB>
-__device__ __forceinline__ void fast_pretest4_raw(const uint8_t* c, int t, uint32_t& lo, uint32_t& hi)
+__device__ __forceinline__ void fast_pretest4_raw(lds_cu32 w, int t, uint32_t& lo, uint32_t& hi)
 {
-    constexpr int st = RB;
-    // base at the lowest word read (row -3), so every read takes a positive immediate offset
-    lds_cu32 w = (lds_cu32)(c - 3 * st);
-    asm volatile("" : "+v"(w));
-    constexpr int o = 3 * st / 4;            // word index of c
+    constexpr int o = 3 * RB / 4;            // word index of the first pixel
     const uint32_t a0 = w[o - 1], b0 = w[o], c0 = w[o + 1];
-    const uint32_t ap = w[o + 2 * st / 4 - 1], bp = w[o + 2 * st / 4], cp = w[o + 2 * st / 4 + 1];
-    const uint32_t am = w[o - 2 * st / 4 - 1], bm = w[o - 2 * st / 4], cm = w[o - 2 * st / 4 + 1];
-    const uint32_t u3 = w[o + 3 * st / 4];
+    const uint32_t u3 = w[2 * o];
     const uint32_t d3 = w[0];
     const us2 T = pk2(t, t);
     lo = pretest_half(
         as_us2(__builtin_amdgcn_perm(0u, b0, 0x0c010c00u)), as_us2(__builtin_amdgcn_perm(0u, u3, 0x0c010c00u)),
-        as_us2(__builtin_amdgcn_perm(0u, d3, 0x0c010c00u)), as_us2(win_lo(bp, cp, 2)), as_us2(win_lo(am, bm, 2)),
-        as_us2(win_lo(b0, c0, 3)), as_us2(win_lo(a0, b0, 1)), as_us2(win_lo(bm, cm, 2)), as_us2(win_lo(ap, bp, 2)), T);
+        as_us2(__builtin_amdgcn_perm(0u, d3, 0x0c010c00u)), as_us2(win_lo(b0, c0, 3)), as_us2(win_lo(a0, b0, 1)), T);
     hi = pretest_half(
         as_us2(__builtin_amdgcn_perm(0u, b0, 0x0c030c02u)), as_us2(__builtin_amdgcn_perm(0u, u3, 0x0c030c02u)),
-        as_us2(__builtin_amdgcn_perm(0u, d3, 0x0c030c02u)), as_us2(win_hi(bp, cp, 2)), as_us2(win_hi(am, bm, 2)),
-        as_us2(win_hi(b0, c0, 3)), as_us2(win_hi(a0, b0, 1)), as_us2(win_hi(bm, cm, 2)), as_us2(win_hi(ap, bp, 2)), T);
+        as_us2(__builtin_amdgcn_perm(0u, d3, 0x0c030c02u)), as_us2(win_hi(b0, c0, 3)), as_us2(win_hi(a0, b0, 1)), T);
 }
 
 // M of the detection window (zero around it, for the NMS neighbours):
@@ -1251,6 +1237,11 @@ __device__ __forceinline__ void fast_cell(const Plan* P, const ExtractBufs& b, i
     // lanes' pixel columns inside the window (fixed for the cell)
     const uint32_t vmask4 = (1u << min(max(ww - 4 * cg, 0), 4)) - 1u;   // columns 4 cg + k < ww
     int o = (rsub + 3) * RB + 4 + 4 * cg;
+    // the pre-test's read base (three rows above the first pixel) stepped with o, and the row mask
+    // of the last pass (the only one with rows past the window) taken once: neither is redone per pass
+    lds_cu32 pw = (lds_cu32)(roi + o - 3 * RB);
+    const int r0_last = wh > 0 ? (wh - 1) & -rpi : 0;             // rpi: 4 or 8
+    const uint32_t vmask4_last = rsub < wh - r0_last ? vmask4 : 0u;
     const uint32_t one2 = 0x00010001u;
     FC_MARK(t_scan);
     long long t_str = 0;
@@ -1298,17 +1289,17 @@ __device__ __forceinline__ void fast_cell(const Plan* P, const ExtractBufs& b, i
     // (round 6: the passes' pre-tests first with the survivor masks gathered in registers, then
     // one entry append per pass -- no cross-lane step between pre-tests -- measured slower,
     // 0.857 vs 0.836 ms per 1025-frame launch, profiles/r06/fast)
-    for (int r0 = 0; npix > 0 && r0 < wh; r0 += rpi, o += rpi * RB) {
+    for (int r0 = 0; npix > 0 && r0 < wh; r0 += rpi, o += rpi * RB, pw += rpi * RB / 4) {
         // every lane runs the test (rows past the window read slab bytes that are masked off)
         uint32_t lo, hi;
-        fast_pretest4_raw<RB>(&roi[o], th_min, lo, hi);
+        fast_pretest4_raw<RB>(pw, th_min, lo, hi);
         // survivor bits: a packed u16 half is nonzero iff its pixel survives.  min(half, 1) as an
         // opaque v_pk_min_u16: written in C the compiler turns it into per-half compares and selects
         uint32_t s01, s23;
         asm("v_pk_min_u16 %0, %1, %2" : "=v"(s01) : "v"(lo), "v"(one2));
         asm("v_pk_min_u16 %0, %1, %2" : "=v"(s23) : "v"(hi), "v"(one2));
         const uint32_t t2 = s01 | (s23 << 2);
-        const uint32_t m4 = (t2 | (t2 >> 15)) & (rsub < wh - r0 ? vmask4 : 0u);   // wh - r0: scalar
+        const uint32_t m4 = (t2 | (t2 >> 15)) & (r0 == r0_last ? vmask4_last : vmask4);   // scalar select
         const uint64_t mk = __ballot(m4 != 0u);
         if (mk) {
             if (m4) ent[ne + mbcnt(mk)] = (uint16_t)(((uint32_t)o >> 2) | (m4 << 12));   // o = 4 mod 4: exact
