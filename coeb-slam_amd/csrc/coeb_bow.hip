@@ -190,6 +190,11 @@ __global__ __launch_bounds__(kCsrThreads) void k_bow_rot(int* inout, const int* 
 
 }  // namespace
 
+double word_weight(const coeb_ctx* c, int word)
+{
+    return (word >= 0 && word < (int)c->voc.word_weight.size()) ? c->voc.word_weight[word] : 0.0;
+}
+
 int launch_transform(coeb_ctx* c, const uint8_t* d_desc, const int* d_counts, int n_fixed, int stride, int F,
                      int levelsup, int* d_word, int* d_node, hipStream_t s)
 {
@@ -282,38 +287,24 @@ int coeb_bow_transform(coeb_ctx* c, const uint8_t* desc, int n, int levelsup, in
         return set_err(c, COEB_EINVAL, "coeb_bow_transform: incomplete feature-vector outputs");
     (void)hipSetDevice(c->device);
     const int cap = std::max(n, 1);
-    const size_t nout = (size_t)2 * cap + csr_ints(n);      // word[cap], node[cap], the CSR
-    int rc;
-    if ((rc = ensure(c, c->bow.w_out, nout))) return rc;
     hipStream_t s = main_stream(c);
-    Pack pk;
-    const size_t o_d = pk.add(desc, (size_t)n * 32);
-    uint8_t* dbase;
-    // the results come back through the same page-locked buffer: sized before the upload starts
-    if ((rc = pinned(c, std::max(pk.total, nout * 4))) || (rc = stage_in(c, pk, &dbase, s))) return rc;
-    int* d_word = c->bow.w_out.p;
-    int* d_node = d_word + cap;
-    int* d_csr = d_node + cap;
-    if (n && launch_transform(c, dbase + o_d, nullptr, n, n, 1, levelsup, d_word, d_node, s))
+    Staged st;
+    const size_t o_d = st.add(desc, (size_t)n * 32);
+    const size_t o_w = st.take((size_t)cap * 4), o_n = st.take((size_t)cap * 4), o_csr = st.take((size_t)csr_ints(n) * 4);
+    int rc;
+    if ((rc = st.stage(c, s, false))) return rc;
+    if (n && launch_transform(c, st.dev<uint8_t>(o_d), nullptr, n, n, 1, levelsup, st.dev<int>(o_w), st.dev<int>(o_n), s))
         return hip_err(c, hipGetLastError(), "k_bow_transform");
     CsrArgs ca{};
-    ca.side[0] = CsrSide{d_node, nullptr, n, d_csr};
+    ca.side[0] = CsrSide{st.dev<int>(o_n), nullptr, n, st.dev<int>(o_csr)};
     launch_bow_csr(c, ca, 1, s);
     HIP_TRY(c, hipGetLastError());
-    const int32_t* h = reinterpret_cast<const int32_t*>(c->pin);
-    HIP_TRY(c, hipMemcpyAsync(c->pin, d_word, nout * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    const int32_t* h_word = h;
-    const int32_t* h_node = h + cap;
-    const int32_t* h_csr = h_node + cap;
-    for (int i = 0; i < n; i++) {
-        if (word_out) word_out[i] = h_word[i];
-        if (node_out) node_out[i] = h_node[i];
-        if (weight_out) {
-            const int w = h_word[i];
-            weight_out[i] = (w >= 0 && w < (int)c->voc.word_weight.size()) ? c->voc.word_weight[w] : 0.0;
-        }
-    }
+    if ((rc = st.finish(c, s, o_w, st.end(), false))) return rc;
+    const int32_t* h_word = st.host<int32_t>(o_w);
+    const int32_t* h_csr = st.host<int32_t>(o_csr);
+    if (word_out) memcpy(word_out, h_word, (size_t)n * 4);
+    if (node_out) memcpy(node_out, st.host<int32_t>(o_n), (size_t)n * 4);
+    for (int i = 0; weight_out && i < n; i++) weight_out[i] = word_weight(c, h_word[i]);
     if (want_fv) {
         const int nd = h_csr[0], m = h_csr[1];
         *nfv_out = nd;
@@ -366,26 +357,24 @@ int coeb_match_bow(coeb_ctx* c, const coeb_bow_keyframe* kf, const coeb_bow_fram
         return set_err(c, COEB_EINVAL, "coeb_match_bow: missing current-frame arrays");
     (void)hipSetDevice(c->device);
     const int cs = std::max(n, 1);
-    BowBufs& bw = c->bow;
     int rc;
-    if ((rc = bow_search_bufs(c, nq, n)) || (rc = ensure(c, bw.m_out, (size_t)cs + 1))) return rc;
+    if ((rc = bow_search_bufs(c, nq, n))) return rc;
     hipStream_t s = main_stream(c);
-    Pack pk;
-    const size_t o_v = pk.add(kf->valid, (size_t)nq), o_kd = pk.add(kf->descriptor, (size_t)nq * 32);
-    const size_t o_kn = pk.add(kf->node_id, (size_t)nq * 4), o_ka = pk.add(kf->angle, (size_t)nq * 4);
-    const size_t o_cd = pk.add(cur->descriptor, (size_t)n * 32), o_cn = pk.add(cur->node_id, (size_t)n * 4);
-    const size_t o_ca = pk.add(cur->angle, (size_t)n * 4);
-    uint8_t* dbase;
-    if ((rc = pinned(c, std::max(pk.total, ((size_t)cs + 1) * 4))) || (rc = stage_in(c, pk, &dbase, s))) return rc;
+    Staged st;
+    const size_t o_v = st.add(kf->valid, (size_t)nq), o_kd = st.add(kf->descriptor, (size_t)nq * 32);
+    const size_t o_kn = st.add(kf->node_id, (size_t)nq * 4), o_ka = st.add(kf->angle, (size_t)nq * 4);
+    const size_t o_cd = st.add(cur->descriptor, (size_t)n * 32), o_cn = st.add(cur->node_id, (size_t)n * 4);
+    const size_t o_ca = st.add(cur->angle, (size_t)n * 4);
+    const size_t o_m = st.take(((size_t)cs + 1) * 4);
+    if ((rc = st.stage(c, s, false))) return rc;
     BowSearch bs;
-    bs.kf_valid = dbase + o_v; bs.kf_desc = dbase + o_kd; bs.kf_node = (const int*)(dbase + o_kn);
-    bs.kf_angle = (const float*)(dbase + o_ka); bs.kf_n = nq;
-    bs.cur_desc = dbase + o_cd; bs.cur_node = (const int*)(dbase + o_cn); bs.cur_angle = (const float*)(dbase + o_ca);
-    bs.cur_n = n; bs.match = bw.m_out.p;
+    bs.kf_valid = st.dev<uint8_t>(o_v); bs.kf_desc = st.dev<uint8_t>(o_kd); bs.kf_node = st.dev<int>(o_kn);
+    bs.kf_angle = st.dev<float>(o_ka); bs.kf_n = nq;
+    bs.cur_desc = st.dev<uint8_t>(o_cd); bs.cur_node = st.dev<int>(o_cn); bs.cur_angle = st.dev<float>(o_ca);
+    bs.cur_n = n; bs.match = st.dev<int>(o_m);
     if (launch_search_by_bow(c, bs, nnratio, check_orientation, s)) return hip_err(c, hipGetLastError(), "launch_search_by_bow");
-    int32_t* hout = reinterpret_cast<int32_t*>(c->pin);
-    HIP_TRY(c, hipMemcpyAsync(hout, bw.m_out.p, ((size_t)cs + 1) * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
+    if ((rc = st.finish(c, s, o_m, st.end(), false))) return rc;
+    const int32_t* hout = st.host<int32_t>(o_m);
     if (n) memcpy(match_out, hout, (size_t)n * 4);
     *nmatches = hout[cs];
     return COEB_OK;

@@ -504,7 +504,7 @@ int err_word_seen(coeb_ctx* c, const uint8_t* src)
     return err_word_report(c, h);
 }
 
-// the word fetched by a copy and a synchronisation of its own
+// coeb_synchronize: the word fetched by a copy and a synchronisation of its own
 int check_err_word(coeb_ctx* c)
 {
     main_stream(c);
@@ -571,26 +571,14 @@ void match_copy_out(const int32_t* hout, int n, int cs, int32_t* match_out, int*
     *nmatches = hout[cs];
 }
 
-// device buffers of coeb_match_localmap / coeb_match_keyframe: cs current keypoints, qs points
-int projection_bufs(coeb_ctx* c, int cs, int qs)
+// scratch of coeb_match_localmap / coeb_match_keyframe (qs points) and the error word they read
+int projection_bufs(coeb_ctx* c, int qs)
 {
     SingleFrameBufs& sf = c->sf;
     int rc;
-    if ((rc = ensure(c, sf.l_out, (size_t)cs + 1)) || (rc = ensure(c, sf.l_list, (size_t)qs * kCQ)) ||
-        (rc = ensure(c, c->ex.err, 4)) || (rc = ensure(c, sf.l_path, 2)))
+    if ((rc = ensure(c, sf.l_list, (size_t)qs * kCQ)) || (rc = ensure(c, c->ex.err, 4)) || (rc = ensure(c, sf.l_path, 2)))
         return rc;
     return 0;
-}
-
-// their epilogue: one copy back of match[cs], nmatch, the synchronisation, the error word
-int projection_finish(coeb_ctx* c, hipStream_t s, int n, int cs, int32_t* match_out, int* nmatches)
-{
-    int32_t* hout = reinterpret_cast<int32_t*>(c->pin);
-    HIP_TRY(c, hipMemcpyAsync(hout, c->sf.l_out.p, ((size_t)cs + 1) * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (int rc = check_err_word(c)) return rc;
-    match_copy_out(hout, n, cs, match_out, nmatches);
-    return COEB_OK;
 }
 
 // ---- shared by the single-frame tracking calls ----
@@ -1416,8 +1404,7 @@ int coeb_match_localmap(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe
     const int cs = std::max(n, 1), qs = std::max(nq, 1);
     int rc;
     SingleFrameBufs& sf = c->sf;
-    if ((rc = projection_bufs(c, cs, qs))) return rc;
-    int32_t* dout = sf.l_out.p;
+    if ((rc = projection_bufs(c, qs))) return rc;
     hipStream_t s = main_stream(c);
     Staged st;
     const CurOff o_c = pack_cur(st, cur);
@@ -1426,18 +1413,21 @@ int coeb_match_localmap(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe
     const size_t o_py = st.add(mp->proj_y, (size_t)nq * 4), o_pxr = st.add(mp->proj_xr, (size_t)nq * 4);
     const size_t o_l = st.add(mp->level, (size_t)nq * 4), o_vc = st.add(mp->view_cos, (size_t)nq * 4);
     const size_t o_qd = st.add(mp->descriptor, (size_t)nq * 32), o_no = st.add(mp->observations, (size_t)nq * 4);
-    if ((rc = st.stage(c, s, false))) return rc;
+    const size_t o_m = st.take(((size_t)cs + 1) * 4);           // match[cs], nmatch
+    if ((rc = st.stage(c, s, true))) return rc;
     LocalBufs b;
     b.cur_kps = st.dev<void>(o_c.k); b.cur_desc = st.dev<uint8_t>(o_c.d); b.cur_ur = st.dev<float>(o_c.ur);
     b.cur_obs = st.dev<int>(o_co); b.cur_n = n;
     b.in_view = st.dev<uint8_t>(o_v); b.proj_x = st.dev<float>(o_px); b.proj_y = st.dev<float>(o_py);
     b.proj_xr = st.dev<float>(o_pxr); b.level = st.dev<int>(o_l); b.view_cos = st.dev<float>(o_vc);
     b.desc = st.dev<uint8_t>(o_qd); b.nobs = st.dev<int>(o_no); b.mp_n = nq;
-    b.match = dout; b.nmatch = dout + cs; b.lists = sf.l_list.p; b.err = c->ex.err.p; b.path = sf.l_path.p;
+    b.match = st.dev<int32_t>(o_m); b.nmatch = b.match + cs; b.lists = sf.l_list.p; b.err = c->ex.err.p; b.path = sf.l_path.p;
     rc = launch_match_local(make_cam(c, cam), b, th, nnratio, s, &c->hook);
     if (rc == -2) return set_err(c, COEB_ERANGE, "coeb_match_localmap: frame and local map exceed the LDS budget");
     if (rc) return hip_err(c, hipGetLastError(), "launch_match_local");
-    return projection_finish(c, s, n, cs, match_out, nmatches);
+    if ((rc = st.finish(c, s, o_m, st.end(), true))) return rc;
+    match_copy_out(st.host<int32_t>(o_m), n, cs, match_out, nmatches);
+    return COEB_OK;
 }
 
 int coeb_match_keyframe(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe* cur, const uint8_t* cur_has,
@@ -1457,8 +1447,7 @@ int coeb_match_keyframe(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe
     const int cs = std::max(n, 1), qs = std::max(nq, 1);
     int rc;
     SingleFrameBufs& sf = c->sf;
-    if ((rc = projection_bufs(c, cs, qs))) return rc;
-    int32_t* dout = sf.l_out.p;
+    if ((rc = projection_bufs(c, qs))) return rc;
     hipStream_t s = main_stream(c);
     Staged st;
     const size_t o_k = st.add(cur->keys_un, (size_t)n * sizeof(coeb_keypoint)), o_d = st.add(cur->descriptors, (size_t)n * 32);
@@ -1467,17 +1456,20 @@ int coeb_match_keyframe(coeb_ctx* c, const coeb_camera* cam, const coeb_curframe
     const size_t o_qd = st.add(kf->descriptor, (size_t)nq * 32), o_mx = st.add(kf->max_distance, (size_t)nq * 4);
     const size_t o_mn = st.add(kf->min_distance, (size_t)nq * 4), o_a = st.add(kf->angle, (size_t)nq * 4);
     const size_t o_T = st.add(Tcw, 64);
-    if ((rc = st.stage(c, s, false))) return rc;
+    const size_t o_m = st.take(((size_t)cs + 1) * 4);           // match[cs], nmatch
+    if ((rc = st.stage(c, s, true))) return rc;
     KfBufs b;
     b.cur_kps = st.dev<void>(o_k); b.cur_desc = st.dev<uint8_t>(o_d); b.cur_has = st.dev<uint8_t>(o_h); b.cur_n = n;
     b.valid = st.dev<uint8_t>(o_v); b.xw = st.dev<float>(o_x); b.desc = st.dev<uint8_t>(o_qd);
     b.maxd = st.dev<float>(o_mx); b.mind = st.dev<float>(o_mn); b.angle = st.dev<float>(o_a);
     b.kf_n = nq; b.Tcw = st.dev<float>(o_T);
-    b.match = dout; b.nmatch = dout + cs; b.lists = sf.l_list.p; b.err = c->ex.err.p; b.path = sf.l_path.p;
+    b.match = st.dev<int32_t>(o_m); b.nmatch = b.match + cs; b.lists = sf.l_list.p; b.err = c->ex.err.p; b.path = sf.l_path.p;
     rc = launch_match_kf(make_cam(c, cam), b, th, orb_dist, check_ori ? 1 : 0, s, &c->hook);
     if (rc == -2) return set_err(c, COEB_ERANGE, "coeb_match_keyframe: frame and keyframe exceed the LDS budget");
     if (rc) return hip_err(c, hipGetLastError(), "launch_match_kf");
-    return projection_finish(c, s, n, cs, match_out, nmatches);
+    if ((rc = st.finish(c, s, o_m, st.end(), true))) return rc;
+    match_copy_out(st.host<int32_t>(o_m), n, cs, match_out, nmatches);
+    return COEB_OK;
 }
 
 int coeb_pose_optimization(coeb_ctx* c, const coeb_camera* cam, const coeb_pose_frame* fr, float Tcw[16],
@@ -1736,11 +1728,7 @@ int coeb_track_reference_keyframe(coeb_ctx* c, const coeb_camera* cam, const coe
         const int32_t* h_word = st.host<int32_t>(o_wd);
         if (word_out) memcpy(word_out, h_word, (size_t)n * 4);
         if (node_out) memcpy(node_out, st.pin + o_nd, (size_t)n * 4);
-        if (weight_out)
-            for (int i = 0; i < n; i++) {
-                const int wd = h_word[i];
-                weight_out[i] = (wd >= 0 && wd < (int)c->voc.word_weight.size()) ? c->voc.word_weight[wd] : 0.0;
-            }
+        for (int i = 0; weight_out && i < n; i++) weight_out[i] = word_weight(c, h_word[i]);
     }
     if (n) memcpy(match_out, hm, (size_t)n * 4);
     if (n && discarded_out) memcpy(discarded_out, st.pin + o_dis, (size_t)n * 4);

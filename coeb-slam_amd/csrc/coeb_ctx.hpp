@@ -80,15 +80,16 @@ struct TrackLocalMapBufs {  // coeb_track_local_map_batch_device
                         tl_lnobs, tl_lmatch, tl_nlocal, tl_path, tl_n2, tl_res2, tl_lists);
     }
 };
-struct SingleFrameBufs {    // coeb_match_lastframe (m_*), _localmap / _keyframe (l_*), coeb_pose_optimization (p_*);
+struct SingleFrameBufs {    // scratch only (results live in the call's staged region): coeb_match_lastframe (m_*),
+                            // _localmap / _keyframe (l_*), coeb_pose_optimization (p_*);
                             // coeb_search_local_points / coeb_track_local_map use l_list, l_path and p_*
                             // coeb_track_reference_keyframe uses p_* (and BowBufs' m_csr / m_aux)
-    DevArr<int32_t> m_scr{"m_scr"}, m_qn{"m_qn"}, l_out{"l_out"}, l_path{"l_path"};
+    DevArr<int32_t> m_scr{"m_scr"}, m_qn{"m_qn"}, l_path{"l_path"};
     DevArr<uint32_t> l_list{"l_list"};
     DevArr<uint8_t> p_act{"p_act"};
     DevArr<PoseEdgeRec> p_edge{"p_edge"};
     DevArr<double> p_chi{"p_chi"};
-    auto all() { return std::tie(m_scr, m_qn, l_out, l_path, l_list, p_act, p_edge, p_chi); }
+    auto all() { return std::tie(m_scr, m_qn, l_path, l_list, p_act, p_edge, p_chi); }
 };
 struct TimingBufs {         // diagnostic phase clocks (COEB_MATCH_CLOCK / COEB_POSE_CLOCK builds)
     DevArr<long long> m_timing{"m_timing"}, p_timing{"p_timing"};
@@ -101,11 +102,12 @@ struct HelperBufs {         // scratch of coeb_flow.hip (flow) and of coeb_frame
     DevArr<coeb_keypoint> ud_in{"ud_in"}, ud_out{"ud_out"};
     auto all() { return std::tie(flow, bf_img, pp_img, pp_gray, pp_dsrc, bf_box, pp_dep, bf_out, ud_in, ud_out); }
 };
-struct BowBufs {            // coeb_bow.hip: the vocabulary tables (v_*) and the scratch of its entry points
+struct BowBufs {            // coeb_bow.hip: the vocabulary tables (v_*), the batch transform's ids (b_*) and the
+                            // scratch SearchByBoW's callers share (m_csr, m_aux; coeb_kfdb.hip too)
     DevArr<VocRec> v_rec{"v_rec"};
     DevArr<uint8_t> v_desc{"v_desc"};
-    DevArr<int32_t> w_out{"w_out"}, b_word{"b_word"}, b_node{"b_node"}, m_csr{"m_csr"}, m_out{"m_out"}, m_aux{"m_aux"};
-    auto all() { return std::tie(v_rec, v_desc, w_out, b_word, b_node, m_csr, m_out, m_aux); }
+    DevArr<int32_t> b_word{"b_word"}, b_node{"b_node"}, m_csr{"m_csr"}, m_aux{"m_aux"};
+    auto all() { return std::tie(v_rec, v_desc, b_word, b_node, m_csr, m_aux); }
 };
 
 template <class G, class F>
@@ -279,7 +281,7 @@ int pinned(coeb_ctx* c, size_t bytes);          // the page-locked buffer holds 
 // pack -> pinned -> one H2D copy into the "stage" device buffer; *dbase = its device address
 int stage_in(coeb_ctx* c, const Pack& pk, uint8_t** dbase, hipStream_t s);
 
-// The staged region of one single-frame tracking call, at the same offsets of the "stage" device
+// The staged region of one host-array call, at the same offsets of the "stage" device
 // buffer and of the page-locked buffer: the packed inputs (uploaded in one copy; results that have
 // an initial value are uploaded with them), then what take() hands out behind them at 16-byte
 // rounded offsets -- first the results the kernels write, which finish() copies back in one piece
@@ -311,6 +313,7 @@ struct Staged {
 // coeb_bow.hip, called by coeb_capi.hip (coeb_track_reference_keyframe): Frame::ComputeBoW's transform and
 // SearchByBoW on device arrays.  launch_transform: descriptor i of frame f at d_desc + (f * stride + i) * 32,
 // d_counts ? d_counts[f] : n_fixed of them; d_word / d_node [F][stride].
+double word_weight(const coeb_ctx* c, int word);            // of a word id the transform returned (-1: 0.0)
 int launch_transform(coeb_ctx* c, const uint8_t* d_desc, const int* d_counts, int n_fixed, int stride, int F,
                      int levelsup, int* d_word, int* d_node, hipStream_t s);
 struct BowSearch {

@@ -13,6 +13,7 @@
 // restates DBoW2's L1Scoring; parity against DBoW2 itself is UNPINNED.
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <climits>
 #include <cstring>
 #include <vector>
@@ -35,26 +36,32 @@ struct KfdbView {
     __host__ __device__ int* csr(int slot) const { return reinterpret_cast<int*>(slab + slot * stride + (size_t)mf * 48); }
 };
 
+// One device array of the database: `stride` bytes per slot, `cap` slots.  stride 0: not in use, never
+// allocated; p is null before the first allocation and after release_device.
+struct KfdbSlab {
+    uint8_t* p = nullptr;
+    size_t stride = 0;
+};
+// The database's device memory: the keyframe slots (KfdbView), meta[slot][4], and the two arrays the
+// first call that needs them adds (lazy_slab) -- KfdbGeo[mf] per slot (coeb_kfdb_set_geometry) and the
+// keyframe's 64 x 48 feature grid as a CSR, fuse_grid_ints(mf) ints per slot (coeb_kfdb_fuse_search).
+enum { kSlab, kMeta, kGeo, kGrid, kNumSlabs };
+using KfdbSlabs = std::array<KfdbSlab, kNumSlabs>;
+
 struct coeb_kfdb {
     coeb_ctx* c = nullptr;          // null once the context is gone
-    KfdbView v{nullptr, 0, nullptr, 0};
+    KfdbSlabs sl;
+    int mf = 0;                     // max_features
     int cap = 0;                    // allocated slots
     int nslots = 0;                 // one past the highest slot handed out
     int nkf = 0;
-    int* q = nullptr;               // query scratch: hdr[4] {max, min}, common[cap], first[cap], score[cap]
     int64_t next_seq = 0;
     std::vector<uint8_t> used;
     std::vector<int> n, nd;         // features and feature-vector nodes per slot
     std::vector<int64_t> seq;       // insertion sequence number per slot
-    // coeb_kfdb_set_geometry: KfdbGeo[mf] per slot, allocated by the first call (null before)
-    uint8_t* geo = nullptr;
-    size_t geo_stride = 0;
     std::vector<uint8_t> has_geo;   // the slot's keyframe has its geometry
-    // coeb_kfdb_fuse_search: the keyframe's 64 x 48 feature grid as a CSR, fuse_grid_ints(mf) ints per
-    // slot, allocated by the first call (null before); grid_rec: the bounds each was built with
-    uint8_t* grid = nullptr;
-    size_t grid_stride = 0;
-    std::vector<KfdbGridRec> grid_rec;
+    std::vector<KfdbGridRec> grid_rec;      // the bounds each slot's grid was built with
+    KfdbView view() const { return KfdbView{sl[kSlab].p, sl[kSlab].stride, reinterpret_cast<int*>(sl[kMeta].p), mf}; }
 };
 
 namespace {
@@ -618,7 +625,54 @@ int db_err(coeb_kfdb* db, const char* what)
     return set_err(db ? db->c : nullptr, COEB_EINVAL, std::string(what));
 }
 
-// the storage holds at least `want` slots afterwards: doubled, copied device to device
+// the one free list: every slab of the set released, the strides kept
+void free_slabs(KfdbSlabs& sl)
+{
+    for (KfdbSlab& a : sl) {
+        if (a.p) (void)hipFree(a.p);
+        a.p = nullptr;
+    }
+}
+
+// every slab of the set that is in use allocated for cap slots; all or (freed again) none
+hipError_t alloc_slabs(KfdbSlabs& sl, int cap)
+{
+    for (KfdbSlab& a : sl) {
+        const hipError_t e = a.stride ? hipMalloc(&a.p, (size_t)cap * a.stride) : hipSuccess;
+        if (e != hipSuccess) {
+            a.p = nullptr;
+            free_slabs(sl);
+            return e;
+        }
+    }
+    return hipSuccess;
+}
+
+// a (geo or grid) exists afterwards, slot_bytes per slot rounded up to 256: allocated by the first call that needs it
+int lazy_slab(coeb_kfdb* db, KfdbSlab& a, size_t slot_bytes, const char* what)
+{
+    if (a.p) return 0;
+    a.stride = (slot_bytes + 255) & ~(size_t)255;
+    const hipError_t e = hipMalloc(&a.p, (size_t)db->cap * a.stride);
+    if (e == hipSuccess) return 0;
+    a = KfdbSlab{};
+    return set_err(db->c, COEB_ENOMEM, std::string("hipMalloc kfdb ") + what + ": " + hipGetErrorString(e));
+}
+
+// grow()'s copies: meta cleared, then the first nslots slots of every slab, device to device
+int copy_slots(coeb_ctx* c, const KfdbSlabs& from, const KfdbSlabs& to, int nslots, int ncap, hipStream_t s)
+{
+    HIP_TRY(c, hipMemsetAsync(to[kMeta].p, 0, (size_t)ncap * to[kMeta].stride, s));
+    for (int k = 0; k < kNumSlabs; k++) {
+        const KfdbSlab &a = to[k], &o = from[k];
+        if (a.p && nslots) HIP_TRY(c, hipMemcpyAsync(a.p, o.p, (size_t)nslots * a.stride, hipMemcpyDeviceToDevice, s));
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return 0;
+}
+
+// the storage holds at least `want` slots afterwards: doubled, copied device to device.  The new set is
+// a local until the copies have completed, so every return before the swap frees it.
 int grow(coeb_kfdb* db, int want)
 {
     coeb_ctx* c = db->c;
@@ -626,37 +680,17 @@ int grow(coeb_kfdb* db, int want)
     int ncap = std::max(db->cap, 1);
     while (ncap < want) ncap *= 2;
     hipStream_t s = main_stream(c);
-    uint8_t* slab = nullptr;
-    int* meta = nullptr;
-    int* q = nullptr;
-    uint8_t* geo = nullptr;
-    uint8_t* gridp = nullptr;
-    hipError_t e = hipMalloc(&slab, (size_t)ncap * db->v.stride);
-    if (e == hipSuccess) e = hipMalloc(&meta, (size_t)ncap * 16);
-    if (e == hipSuccess) e = hipMalloc(&q, (4 + 3 * (size_t)ncap) * 4);
-    if (e == hipSuccess && db->geo) e = hipMalloc(&geo, (size_t)ncap * db->geo_stride);
-    if (e == hipSuccess && db->grid) e = hipMalloc(&gridp, (size_t)ncap * db->grid_stride);
-    if (e != hipSuccess) {
-        if (slab) (void)hipFree(slab);
-        if (meta) (void)hipFree(meta);
-        if (q) (void)hipFree(q);
-        if (geo) (void)hipFree(geo);
-        return set_err(c, COEB_ENOMEM, std::string("hipMalloc kfdb: ") + hipGetErrorString(e));
+    KfdbSlabs nw = db->sl;              // the strides
+    for (KfdbSlab& a : nw) a.p = nullptr;
+    const hipError_t e = alloc_slabs(nw, ncap);
+    if (e != hipSuccess) return set_err(c, COEB_ENOMEM, std::string("hipMalloc kfdb: ") + hipGetErrorString(e));
+    if (const int rc = copy_slots(c, db->sl, nw, db->nslots, ncap, s)) {
+        free_slabs(nw);
+        return rc;
     }
-    HIP_TRY(c, hipMemsetAsync(meta, 0, (size_t)ncap * 16, s));
-    if (db->nslots) {
-        HIP_TRY(c, hipMemcpyAsync(slab, db->v.slab, (size_t)db->nslots * db->v.stride, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(meta, db->v.meta, (size_t)db->nslots * 16, hipMemcpyDeviceToDevice, s));
-        if (geo) HIP_TRY(c, hipMemcpyAsync(geo, db->geo, (size_t)db->nslots * db->geo_stride, hipMemcpyDeviceToDevice, s));
-        if (gridp) HIP_TRY(c, hipMemcpyAsync(gridp, db->grid, (size_t)db->nslots * db->grid_stride, hipMemcpyDeviceToDevice, s));
-    }
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (db->v.slab) (void)hipFree(db->v.slab);
-    if (db->v.meta) (void)hipFree(db->v.meta);
-    if (db->q) (void)hipFree(db->q);
-    if (db->geo) (void)hipFree(db->geo);
-    if (db->grid) (void)hipFree(db->grid);
-    db->v.slab = slab; db->v.meta = meta; db->q = q; db->geo = geo; db->grid = gridp; db->cap = ncap;
+    free_slabs(db->sl);
+    db->sl = nw;
+    db->cap = ncap;
     db->grid_rec.resize(ncap, KfdbGridRec{});
     db->used.resize(ncap, 0); db->has_geo.resize(ncap, 0); db->n.resize(ncap, 0); db->nd.resize(ncap, 0); db->seq.resize(ncap, 0);
     return 0;
@@ -664,12 +698,7 @@ int grow(coeb_kfdb* db, int want)
 
 void release_device(coeb_kfdb* db)
 {
-    if (db->v.slab) (void)hipFree(db->v.slab);
-    if (db->v.meta) (void)hipFree(db->v.meta);
-    if (db->q) (void)hipFree(db->q);
-    if (db->geo) (void)hipFree(db->geo);
-    if (db->grid) (void)hipFree(db->grid);
-    db->v.slab = nullptr; db->v.meta = nullptr; db->q = nullptr; db->geo = nullptr; db->grid = nullptr;
+    free_slabs(db->sl);
     db->cap = db->nslots = db->nkf = 0;
 }
 
@@ -695,8 +724,9 @@ int coeb_kfdb_create(coeb_ctx* c, int max_features, int initial_slots, coeb_kfdb
     (void)hipSetDevice(c->device);
     coeb_kfdb* db = new coeb_kfdb;
     db->c = c;
-    db->v.mf = max_features;
-    db->v.stride = slot_stride(max_features);
+    db->mf = max_features;
+    db->sl[kSlab].stride = slot_stride(max_features);
+    db->sl[kMeta].stride = 16;
     const int rc = grow(db, initial_slots);
     if (rc) { delete db; return rc; }
     c->kfdbs.push_back(db);
@@ -721,7 +751,7 @@ int coeb_kfdb_add(coeb_kfdb* db, const coeb_kfdb_keyframe* kf, int* slot_out)
 {
     if (!db || !db->c || !kf || !slot_out) return db_err(db, "coeb_kfdb_add: invalid arguments");
     coeb_ctx* c = db->c;
-    const int n = kf->n, nw = kf->nw, mf = db->v.mf;
+    const int n = kf->n, nw = kf->nw, mf = db->mf;
     if (n < 0 || nw < 0 || n > mf || nw > mf) return db_err(db, "coeb_kfdb_add: n or nw outside 0..max_features");
     if ((n && (!kf->descriptor || !kf->node_id || !kf->angle)) || (nw && (!kf->bow_word || !kf->bow_value)))
         return db_err(db, "coeb_kfdb_add: missing keyframe arrays");
@@ -738,20 +768,21 @@ int coeb_kfdb_add(coeb_kfdb* db, const coeb_kfdb_keyframe* kf, int* slot_out)
     const size_t o_node = pk.add(kf->node_id, (size_t)n * 4);
     uint8_t* dbase;
     if ((rc = stage_in(c, pk, &dbase, s))) return rc;
+    const KfdbView v = db->view();
     StoreArgs sa;
-    sa.seg[0] = StoreSeg{(const uint32_t*)(dbase + o_val), (uint32_t*)db->v.value(slot), nw * 2};
-    sa.seg[1] = StoreSeg{(const uint32_t*)(dbase + o_word), (uint32_t*)db->v.word(slot), nw};
-    sa.seg[2] = StoreSeg{(const uint32_t*)(dbase + o_ang), (uint32_t*)db->v.angle(slot), n};
-    sa.seg[3] = StoreSeg{(const uint32_t*)(dbase + o_desc), (uint32_t*)db->v.desc(slot), n * 8};
-    sa.meta = db->v.meta + slot * 4; sa.n = n; sa.nw = nw;
+    sa.seg[0] = StoreSeg{(const uint32_t*)(dbase + o_val), (uint32_t*)v.value(slot), nw * 2};
+    sa.seg[1] = StoreSeg{(const uint32_t*)(dbase + o_word), (uint32_t*)v.word(slot), nw};
+    sa.seg[2] = StoreSeg{(const uint32_t*)(dbase + o_ang), (uint32_t*)v.angle(slot), n};
+    sa.seg[3] = StoreSeg{(const uint32_t*)(dbase + o_desc), (uint32_t*)v.desc(slot), n * 8};
+    sa.meta = v.meta + slot * 4; sa.n = n; sa.nw = nw;
     prof_begin(&c->hook, "k_kfdb_store", s);
     hipLaunchKernelGGL(k_kfdb_store, dim3(std::max(1, (n * 8 + kDbThreads - 1) / kDbThreads)), dim3(kDbThreads), 0, s, sa);
     prof_end(&c->hook, s);
     CsrArgs ca{};
-    ca.side[0] = CsrSide{(const int*)(dbase + o_node), nullptr, n, db->v.csr(slot)};
+    ca.side[0] = CsrSide{(const int*)(dbase + o_node), nullptr, n, v.csr(slot)};
     launch_bow_csr(c, ca, 1, s);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->pin, db->v.csr(slot), 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(c->pin, v.csr(slot), 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     db->used[slot] = 1;
     db->has_geo[slot] = 0;
@@ -771,7 +802,7 @@ int coeb_kfdb_erase(coeb_kfdb* db, int slot)
     if (slot < 0 || slot >= db->nslots || !db->used[slot]) return db_err(db, "coeb_kfdb_erase: no keyframe in that slot");
     coeb_ctx* c = db->c;
     (void)hipSetDevice(c->device);
-    HIP_TRY(c, hipMemsetAsync(db->v.meta + slot * 4, 0, 16, main_stream(c)));
+    HIP_TRY(c, hipMemsetAsync(db->sl[kMeta].p + slot * 16, 0, 16, main_stream(c)));
     db->used[slot] = 0;
     db->has_geo[slot] = 0;
     db->grid_rec[slot].built = 0;
@@ -785,7 +816,7 @@ int coeb_kfdb_clear(coeb_kfdb* db)
     if (!db || !db->c) return db_err(db, "coeb_kfdb_clear: invalid arguments");
     coeb_ctx* c = db->c;
     (void)hipSetDevice(c->device);
-    HIP_TRY(c, hipMemsetAsync(db->v.meta, 0, (size_t)db->cap * 16, main_stream(c)));
+    HIP_TRY(c, hipMemsetAsync(db->sl[kMeta].p, 0, (size_t)db->cap * 16, main_stream(c)));
     std::fill(db->used.begin(), db->used.end(), 0);
     std::fill(db->has_geo.begin(), db->has_geo.end(), 0);
     std::fill(db->grid_rec.begin(), db->grid_rec.end(), KfdbGridRec{});
@@ -811,7 +842,7 @@ int coeb_kfdb_query(coeb_kfdb* db, const int32_t* word, const double* value, int
     coeb_ctx* c = db->c;
     const int ns = db->nslots;
     if (ns && (!common || !score || !order)) return db_err(db, "coeb_kfdb_query: missing output arrays");
-    if (nw > db->v.mf) return db_err(db, "coeb_kfdb_query: more query words than max_features");
+    if (nw > db->mf) return db_err(db, "coeb_kfdb_query: more query words than max_features");
     if (!kfdb_words_ascending(word, nw)) return db_err(db, "coeb_kfdb_query: word is not strictly ascending");
     *n_sharing = *max_common = *min_common = 0;
     if (!ns || !nw || !db->nkf) {
@@ -820,35 +851,30 @@ int coeb_kfdb_query(coeb_kfdb* db, const int32_t* word, const double* value, int
     }
     (void)hipSetDevice(c->device);
     hipStream_t s = main_stream(c);
-    Pack pk;
-    const size_t o_val = pk.add(value, (size_t)nw * 8), o_word = pk.add(word, (size_t)nw * 4);
-    const size_t nout = 4 + 3 * (size_t)ns;
-    uint8_t* dbase;
+    Staged st;
+    const size_t o_val = st.add(value, (size_t)nw * 8), o_word = st.add(word, (size_t)nw * 4);
+    // results: the header {max, min common words, 0, 0} with its initial value, then what the kernels write per slot
+    const size_t o_hdr = st.fill(0, 16);
+    const size_t o_com = st.take((size_t)ns * 4), o_first = st.take((size_t)ns * 4), o_score = st.take((size_t)ns * 4);
     int rc;
-    if ((rc = pinned(c, std::max(pk.total, nout * 4))) || (rc = stage_in(c, pk, &dbase, s))) return rc;
-    int* hdr = db->q;
-    int* d_common = hdr + 4;
-    int* d_first = d_common + ns;
-    float* d_score = reinterpret_cast<float*>(d_first + ns);
-    HIP_TRY(c, hipMemsetAsync(hdr, 0, 16, s));
+    if ((rc = st.stage(c, s, false))) return rc;
+    const KfdbView v = db->view();
     const dim3 grid((ns + kDbWaves - 1) / kDbWaves);
     prof_begin(&c->hook, "k_kfdb_common", s);
-    hipLaunchKernelGGL(k_kfdb_common, grid, dim3(kDbThreads), 0, s, db->v, ns, (const int*)(dbase + o_word), nw, hdr,
-                       d_common, d_first);
+    hipLaunchKernelGGL(k_kfdb_common, grid, dim3(kDbThreads), 0, s, v, ns, st.dev<int>(o_word), nw, st.dev<int>(o_hdr),
+                       st.dev<int>(o_com), st.dev<int>(o_first));
     prof_end(&c->hook, s);
     prof_begin(&c->hook, "k_kfdb_score", s);
-    hipLaunchKernelGGL(k_kfdb_score, grid, dim3(kDbThreads), 0, s, db->v, ns, (const int*)(dbase + o_word),
-                       (const double*)(dbase + o_val), nw, hdr, d_common, d_score);
+    hipLaunchKernelGGL(k_kfdb_score, grid, dim3(kDbThreads), 0, s, v, ns, st.dev<int>(o_word), st.dev<double>(o_val),
+                       nw, st.dev<int>(o_hdr), st.dev<int>(o_com), st.dev<float>(o_score));
     prof_end(&c->hook, s);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->pin, hdr, nout * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    const int32_t* h = reinterpret_cast<const int32_t*>(c->pin);
-    *max_common = h[0];
-    *min_common = h[1];
-    memcpy(common, h + 4, (size_t)ns * 4);
-    memcpy(score, h + 4 + 2 * (size_t)ns, (size_t)ns * 4);
-    *n_sharing = kfdb_sharing_order(common, h + 4 + ns, db->seq.data(), ns, order);
+    if ((rc = st.finish(c, s, o_hdr, st.end(), false))) return rc;
+    *max_common = st.host<int32_t>(o_hdr)[0];
+    *min_common = st.host<int32_t>(o_hdr)[1];
+    memcpy(common, st.host<int32_t>(o_com), (size_t)ns * 4);
+    memcpy(score, st.host<float>(o_score), (size_t)ns * 4);
+    *n_sharing = kfdb_sharing_order(common, st.host<int32_t>(o_first), db->seq.data(), ns, order);
     return COEB_OK;
 }
 
@@ -876,32 +902,30 @@ int coeb_match_bow_kfdb(coeb_kfdb* db, const int32_t* slots, int ncand, const ui
     const size_t nout = (size_t)ncand * cs + ncand;
     BowBufs& bw = c->bow;
     int rc;
-    if ((rc = ensure(c, bw.m_csr, (size_t)csr_ints(n))) || (rc = ensure(c, bw.m_out, nout)) ||
-        (rc = ensure(c, bw.m_aux, (size_t)ncand * (cs + 32))))
-        return rc;
+    if ((rc = ensure(c, bw.m_csr, (size_t)csr_ints(n))) || (rc = ensure(c, bw.m_aux, (size_t)ncand * (cs + 32)))) return rc;
     hipStream_t s = main_stream(c);
-    Pack pk;
+    Staged st;
     std::vector<int32_t> cand((size_t)ncand * 2);
-    const size_t o_cand = pk.add(cand.data(), cand.size() * 4);
-    const size_t o_cd = pk.add(cur->descriptor, (size_t)n * 32), o_cn = pk.add(cur->node_id, (size_t)n * 4);
-    const size_t o_ca = pk.add(cur->angle, (size_t)n * 4);
+    const size_t o_cand = st.add(cand.data(), cand.size() * 4);
+    const size_t o_cd = st.add(cur->descriptor, (size_t)n * 32), o_cn = st.add(cur->node_id, (size_t)n * 4);
+    const size_t o_ca = st.add(cur->angle, (size_t)n * 4);
     for (int j = 0; j < ncand; j++) {
         cand[2 * j] = slots[j];
-        cand[2 * j + 1] = (int32_t)pk.add(valid[j], (size_t)db->n[slots[j]]);
+        cand[2 * j + 1] = (int32_t)st.add(valid[j], (size_t)db->n[slots[j]]);
     }
-    uint8_t* dbase;
-    if ((rc = pinned(c, std::max(pk.total, nout * 4))) || (rc = stage_in(c, pk, &dbase, s))) return rc;
+    const size_t o_m = st.take(nout * 4);           // the match rows, then the counts: k_bow_csr clears them in one run
+    if ((rc = st.stage(c, s, false))) return rc;
     int* csr_c = bw.m_csr.p;
     DbMatch a;
-    a.v = db->v;
-    a.cand = (const int*)(dbase + o_cand);
-    a.stage = dbase;
-    a.cur = BowSide{dbase + o_cd, (const float*)(dbase + o_ca), csr_c, n};
+    a.v = db->view();
+    a.cand = st.dev<int>(o_cand);
+    a.stage = st.dbase;
+    a.cur = BowSide{st.dev<uint8_t>(o_cd), st.dev<float>(o_ca), csr_c, n};
     a.nnratio = nnratio; a.check_ori = check_orientation ? 1 : 0; a.cs = cs;
-    a.match = bw.m_out.p; a.nm = a.match + (size_t)ncand * cs;
+    a.match = st.dev<int>(o_m); a.nm = a.match + (size_t)ncand * cs;
     a.bin = bw.m_aux.p; a.hist = a.bin + (size_t)ncand * cs;
     CsrArgs ca{};
-    ca.side[0] = CsrSide{(const int*)(dbase + o_cn), nullptr, n, csr_c};
+    ca.side[0] = CsrSide{st.dev<int>(o_cn), nullptr, n, csr_c};
     ca.clear_m1 = a.match; ca.clear_n = (int)nout;
     ca.clear_0 = a.bin; ca.clear_0n = ncand * (cs + 32);
     launch_bow_csr(c, ca, 1, s);
@@ -914,9 +938,8 @@ int coeb_match_bow_kfdb(coeb_kfdb* db, const int32_t* slots, int ncand, const ui
     hipLaunchKernelGGL(k_bow_rot_db, dim3(ncand), dim3(kCsrThreads), 0, s, a);
     prof_end(&c->hook, s);
     HIP_TRY(c, hipGetLastError());
-    int32_t* hout = reinterpret_cast<int32_t*>(c->pin);
-    HIP_TRY(c, hipMemcpyAsync(hout, a.match, nout * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
+    if ((rc = st.finish(c, s, o_m, st.end(), false))) return rc;
+    const int32_t* hout = st.host<int32_t>(o_m);
     for (int j = 0; j < ncand && n; j++) memcpy(match_out + (size_t)j * n, hout + (size_t)j * cs, (size_t)n * 4);
     memcpy(nmatches, hout + (size_t)ncand * cs, (size_t)ncand * 4);
     return COEB_OK;
@@ -934,18 +957,11 @@ int coeb_kfdb_set_geometry(coeb_kfdb* db, int slot, const coeb_keypoint* keys_un
     if ((rc = pinned(c, (size_t)n * sizeof(KfdbGeo)))) return rc;
     if (!kfdb_pack_geometry(keys_un, u_right, n, c->tab.nlevels, reinterpret_cast<KfdbGeo*>(c->pin)))
         return db_err(db, "coeb_kfdb_set_geometry: keypoint octave outside the pyramid");
-    if (!db->geo) {
-        const size_t stride = ((size_t)db->v.mf * sizeof(KfdbGeo) + 255) & ~(size_t)255;
-        const hipError_t e = hipMalloc(&db->geo, (size_t)db->cap * stride);
-        if (e != hipSuccess) {
-            db->geo = nullptr;
-            return set_err(c, COEB_ENOMEM, std::string("hipMalloc kfdb geometry: ") + hipGetErrorString(e));
-        }
-        db->geo_stride = stride;
-    }
+    KfdbSlab& geo = db->sl[kGeo];
+    if ((rc = lazy_slab(db, geo, (size_t)db->mf * sizeof(KfdbGeo), "geometry"))) return rc;
     if (n) {
         hipStream_t s = main_stream(c);
-        HIP_TRY(c, hipMemcpyAsync(db->geo + slot * db->geo_stride, c->pin, (size_t)n * sizeof(KfdbGeo), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(geo.p + slot * geo.stride, c->pin, (size_t)n * sizeof(KfdbGeo), hipMemcpyHostToDevice, s));
         HIP_TRY(c, hipStreamSynchronize(s));       // the page-locked buffer is the next call's
     }
     db->has_geo[slot] = 1;
@@ -990,7 +1006,7 @@ int coeb_kfdb_search_triangulation(coeb_kfdb* db, int slot1, const uint8_t* has_
     int rc;
     if ((rc = st.stage(c, s, false))) return rc;
     TriArgs a;
-    a.v = db->v; a.geo = db->geo; a.geo_stride = db->geo_stride; a.slot1 = slot1;
+    a.v = db->view(); a.geo = db->sl[kGeo].p; a.geo_stride = db->sl[kGeo].stride; a.slot1 = slot1;
     a.has1 = st.dev<uint8_t>(o_h1); a.tab = st.dev<int>(o_tab); a.masks = st.dev<uint8_t>(o_mk);
     a.F = st.dev<float>(o_F); a.epi = st.dev<float>(o_e); a.scale = st.dev<float>(o_sc); a.sigma2 = st.dev<float>(o_sg);
     a.only_stereo = only_stereo ? 1 : 0; a.check_ori = check_orientation ? 1 : 0; a.cs = n1;
@@ -1026,15 +1042,9 @@ int coeb_kfdb_fuse_search(coeb_kfdb* db, const coeb_camera* cam, const coeb_fuse
     if (total == 0) return COEB_OK;
     (void)hipSetDevice(c->device);
     hipStream_t s = main_stream(c);
-    if (!db->grid) {
-        const size_t stride = (fuse_grid_ints(db->v.mf) * 4 + 255) & ~(size_t)255;
-        const hipError_t e = hipMalloc(&db->grid, (size_t)db->cap * stride);
-        if (e != hipSuccess) {
-            db->grid = nullptr;
-            return set_err(c, COEB_ENOMEM, std::string("hipMalloc kfdb grids: ") + hipGetErrorString(e));
-        }
-        db->grid_stride = stride;
-    }
+    int rc;
+    if ((rc = lazy_slab(db, db->sl[kGrid], fuse_grid_ints(db->mf) * 4, "grids"))) return rc;
+    const KfdbSlab &geo = db->sl[kGeo], &grid = db->sl[kGrid];
     std::vector<KfdbFuseJob> tab;
     std::vector<uint8_t> skip;
     std::vector<int32_t> build;
@@ -1051,12 +1061,11 @@ int coeb_kfdb_fuse_search(coeb_kfdb* db, const coeb_camera* cam, const coeb_fuse
     const size_t o_bs = st.add(build.data(), build.size() * 4);
     const size_t o_bi = st.take((size_t)total * 4), o_bd = st.take((size_t)total * 4);
     const size_t back_end = st.end();
-    int rc;
     if ((rc = st.stage(c, s, false))) return rc;
     const MatchCam mc = make_cam(c, cam);
     if (!build.empty()) {
         FuseGridArgs g;
-        g.v = db->v; g.geo = db->geo; g.geo_stride = db->geo_stride; g.grid = db->grid; g.grid_stride = db->grid_stride;
+        g.v = db->view(); g.geo = geo.p; g.geo_stride = geo.stride; g.grid = grid.p; g.grid_stride = grid.stride;
         g.slots = st.dev<int>(o_bs);
         g.min_x = mc.min_x; g.min_y = mc.min_y; g.inv_w = mc.grid_inv_w; g.inv_h = mc.grid_inv_h;
         prof_begin(&c->hook, "k_fuse_grid", s);
@@ -1064,7 +1073,7 @@ int coeb_kfdb_fuse_search(coeb_kfdb* db, const coeb_camera* cam, const coeb_fuse
         prof_end(&c->hook, s);
     }
     FuseArgs a;
-    a.v = db->v; a.geo = db->geo; a.geo_stride = db->geo_stride; a.grid = db->grid; a.grid_stride = db->grid_stride;
+    a.v = db->view(); a.geo = geo.p; a.geo_stride = geo.stride; a.grid = grid.p; a.grid_stride = grid.stride;
     a.jobs = st.dev<KfdbFuseJob>(o_tab); a.skip = st.dev<uint8_t>(o_sk);
     a.valid = st.dev<uint8_t>(o_v); a.pos = st.dev<float>(o_x); a.nrm = st.dev<float>(o_nr);
     a.maxd = st.dev<float>(o_mx); a.mind = st.dev<float>(o_mn); a.desc = st.dev<uint8_t>(o_d);
