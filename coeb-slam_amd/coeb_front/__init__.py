@@ -50,6 +50,12 @@ LIB_PATH = os.environ.get("COEB_LIB_PATH") or os.path.join(os.path.dirname(HERE)
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                            ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
 assert KEYPOINT_DTYPE.itemsize == 28
+# one pair of a moving-object batch as coeb_debug_read("flow_pair") returns it (FlowPairRecord, coeb_ctx.hpp)
+FLOW_PAIR_PTS = 1024
+FLOW_PAIR_DTYPE = np.dtype([("npts", "<i4"), ("nf", "<i4"), ("F", "<f8", (9,)), ("pts", "<f4", (FLOW_PAIR_PTS, 2)),
+                            ("nxt", "<f4", (FLOW_PAIR_PTS, 2)), ("status", "u1", (FLOW_PAIR_PTS,)),
+                            ("state", "u1", (FLOW_PAIR_PTS,))])
+assert FLOW_PAIR_DTYPE.itemsize == 18512
 MAX_LEVELS = 16
 DEPTH_U16, DEPTH_F32 = 0, 1          # COEB_DEPTH_U16 / COEB_DEPTH_F32
 
@@ -810,6 +816,17 @@ class Context:
         buf = np.zeros(size.value, np.uint8)
         self.check(lib().coeb_debug_read(self.h, what.encode(), f, _p(buf), size.value, C.byref(size)))
         return buf
+
+    def flow_pair(self, z):
+        """Pair z (frames z, z + 1) of the last moving-object batch, from the flow scratch
+        (coeb_debug_read "flow_pair"): dict(npts, corners (npts, 2), next_pts (npts, 2), status,
+        state, F (3, 3), nf).  F holds findFundamentalMat's result only where the pair's T_M is
+        not None.  Raises CoebError when the context holds no batch or z is out of range."""
+        r = self.debug_read("flow_pair", z).view(FLOW_PAIR_DTYPE)[0]
+        n = max(0, min(int(r["npts"]), FLOW_PAIR_PTS))
+        return dict(npts=int(r["npts"]), corners=r["pts"][:n].copy(), next_pts=r["nxt"][:n].copy(),
+                    status=r["status"][:n].copy(), state=r["state"][:n].copy(), F=r["F"].reshape(3, 3).copy(),
+                    nf=int(r["nf"]))
 
     # ---- caller-owned device buffers ----
     def alloc(self, nbytes):

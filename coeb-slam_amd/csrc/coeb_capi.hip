@@ -2589,7 +2589,16 @@ int coeb_marker_synchronize(coeb_marker* m)
 
 /* Debug readback of intermediate buffers of frame f of the last batch (test support):
  * what = "pyr" | "blur" | "cand_n" | "lvl_n" | "lvl_kp" | "dyn" | "u_right" | "kp_depth"; copies
- * min(bytes, size). */
+ * min(bytes, size).
+ * Of the context's last moving-object batch (coeb_frame_batch_device with F >= 2; both refuse with
+ * COEB_EINVAL when there is none, or a single-pair flow call has rewritten the flow scratch since):
+ *   "flow_counts": [pairs][2] int32 {Harris candidate keys, corners}, f ignored;
+ *   "flow_pair":   pair f (frames f, f + 1; COEB_EINVAL outside 0 .. pairs - 1) as one fixed record
+ *                  (FlowPairRecord): int32 npts, int32 nf, double F[9], float pts[1024][2] (sub-pixel
+ *                  corners), float nxt[1024][2] (LK next points), uint8 status[1024] (LK),
+ *                  uint8 state[1024] (after the SAD / edge test); entries past npts, and F when
+ *                  findFundamentalMat returned none, are whatever the scratch held.
+ * Both synchronise the context stream. */
 int coeb_debug_read(coeb_ctx* c, const char* what, int f, void* host, size_t bytes, size_t* size_out)
 {
     if (c) join_pose(c);
@@ -2612,7 +2621,15 @@ int coeb_debug_read(coeb_ctx* c, const char* what, int f, void* host, size_t byt
         if (host) memcpy(host, t, std::min(bytes, n));
         return COEB_OK;
     }
-    if (c && what && std::string(what) == "oct_timing") {       // [4096][6] k_octree clocks (COEB_OCT_CLOCK)
+    if (c && what && std::string(what) == "flow_pair") {       // FlowPairRecord of pair f (coeb_ctx.hpp)
+        static thread_local FlowPairRecord rec;
+        int rc = flow_pair(c, f, &rec);
+        if (rc) return rc;
+        if (size_out) *size_out = sizeof(rec);
+        if (host) memcpy(host, &rec, std::min(bytes, sizeof(rec)));
+        return COEB_OK;
+    }
+    if (c && what && std::string(what) == "oct_timing") {      // [4096][6] k_octree clocks (COEB_OCT_CLOCK)
         static long long t[4096 * 6];
         if (size_out) *size_out = sizeof(t);
         if (!host) return 0;

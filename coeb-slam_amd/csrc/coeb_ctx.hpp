@@ -210,7 +210,7 @@ struct coeb_ctx {
     hipEvent_t ev_tlm = nullptr;
     int tlm_frames = 0;
     // geometry of the last moving-object batch whose results the flow scratch still holds
-    // (pairs == 0: none), for flow_counts
+    // (pairs == 0: none), for flow_counts / flow_pair
     struct { int w, h, pairs; } pmo_last{0, 0, 0};
     // pinned host staging of the host-buffer entry points: their inputs are packed here and
     // moved in one copy (a dozen small pageable copies cost more than the kernels)
@@ -327,6 +327,18 @@ int launch_search_by_bow(coeb_ctx* c, const BowSearch& a, float nnratio, int che
 // coeb_flow.hip / coeb_frame.hip, called by coeb_capi.hip
 int pmo_batch(coeb_ctx* c, const uint8_t* d_gray, int F, int w, int h, float* tm_out, int* ntm_out, int tm_cap);
 int flow_counts(coeb_ctx* c, int* out, int cap, int* npairs);
+// one pair's block of the flow scratch as coeb_debug_read("flow_pair") returns it
+constexpr int kFlowPairPts = 1024;
+struct FlowPairRecord {
+    int32_t npts;                       // corners of the pair's previous frame (-1: sort capacity exceeded)
+    int32_t nf;                         // |F_prepoint|: pairs that entered findFundamentalMat
+    double F[9];
+    float pts[2 * kFlowPairPts];        // sub-pixel corners
+    float nxt[2 * kFlowPairPts];        // LK next points
+    uint8_t status[kFlowPairPts];       // LK status
+    uint8_t state[kFlowPairPts];        // after the SAD and edge test
+};
+int flow_pair(coeb_ctx* c, int z, FlowPairRecord* out);
 int blur_flags_batch(coeb_ctx* c, const uint8_t* d_gray, int W, int H, const float* d_boxes, const int* d_box_off, int F,
                      int* d_box_frame, int nbox, int* d_out, hipStream_t s);
 

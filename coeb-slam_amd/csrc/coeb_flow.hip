@@ -2202,6 +2202,32 @@ int flow_counts(coeb_ctx* c, int* out, int cap, int* npairs)
     return COEB_OK;
 }
 
+// Pair z of the context's last moving-object batch: the corner count and sub-pixel corners, the LK
+// next points and status, the state after the SAD / edge test, F and |F_prepoint|, as the pair's
+// block of the flow scratch holds them (test support).  Synchronises the context stream.
+static_assert(kFlowPairPts == kMaxPts, "FlowPairRecord holds kMaxPts points");
+int flow_pair(coeb_ctx* c, int z, FlowPairRecord* out)
+{
+    const auto g = c->pmo_last;
+    if (!g.pairs || z < 0 || z >= g.pairs) return COEB_EINVAL;
+    FlowCall fc;
+    fc.s = main_stream(c);
+    (void)hipSetDevice(c->device);
+    int rc = flow_alloc(c, g.w, g.h, &fc.d, g.pairs);
+    if (rc) return rc;
+    FL_TRY(c, hipStreamSynchronize(fc.s));
+    const size_t o = (size_t)z * (size_t)fc.d.pz;
+    auto at = [&](const void* p) { return (const uint8_t*)p + o; };
+    FL_TRY(c, hipMemcpy(&out->npts, at(fc.d.npts), 4, hipMemcpyDeviceToHost));
+    FL_TRY(c, hipMemcpy(&out->nf, at(fc.d.nf), 4, hipMemcpyDeviceToHost));
+    FL_TRY(c, hipMemcpy(out->F, at(fc.d.F), sizeof(out->F), hipMemcpyDeviceToHost));
+    FL_TRY(c, hipMemcpy(out->pts, at(fc.d.pts), sizeof(out->pts), hipMemcpyDeviceToHost));
+    FL_TRY(c, hipMemcpy(out->nxt, at(fc.d.nxt), sizeof(out->nxt), hipMemcpyDeviceToHost));
+    FL_TRY(c, hipMemcpy(out->status, at(fc.d.status), sizeof(out->status), hipMemcpyDeviceToHost));
+    FL_TRY(c, hipMemcpy(out->state, at(fc.d.state), sizeof(out->state), hipMemcpyDeviceToHost));
+    return COEB_OK;
+}
+
 // Frame::ProcessMovingObject for every consecutive pair of a device-resident batch (the Frame
 // constructor's T_M, Frame.cc:164-166): pair f-1 = frames (f-1, f) of d_gray (packed, w x h),
 // T_M of frame f into tm_out + f * tm_cap * 2 floats, |T_M| (or -1: F empty) into ntm_out[f];
