@@ -21,8 +21,16 @@
  * coeb::SearchForTriangulationNeighbors snapshots GetMapPoint(i) != NULL of every keyframe,
  * computes each neighbour's epipole with the reference's own expressions (:664-670; F12 comes from
  * the caller's ComputeF12) and fills one vMatchedPairs per neighbour.  A neighbour that is not in
- * the store gets no pairs.  The triangulation stays the caller's.  The line and epipole tests use
- * the fused forms seen in the reference binary; parity against it is UNPINNED.
+ * the store gets no pairs.  The line and epipole tests use the fused forms seen in the reference
+ * binary; parity against it is UNPINNED.
+ *
+ * coeb::CreateNewMapPointsNeighbors goes on from there (src/LocalMapping.cc:271-433): it
+ * snapshots the views (pose, camera) and masks of all keyframes once and returns, per neighbour, the
+ * pairs that reach `new MapPoint` with their x3D, in the reference's order.  KeyFrameStore::add uploads
+ * mvKeys / mvDepth for it (coeb_kfdb_set_stereo) when the keyframe type has them.  The triangulated point
+ * is a canonical float32 Jacobi's, not cv::SVD's bit for bit; parity is UNPINNED.  A MapPoint that
+ * another thread adds to one of the keyframes after the snapshot is not seen, as in
+ * SearchForTriangulationNeighbors.
  *
  * The two loops of LocalMapping::SearchInNeighbors (src/LocalMapping.cc:455-535):
  *   coeb::FuseSearch   the snapshot of a point list (under MapPoint::mGlobalMutex) and one
@@ -57,6 +65,27 @@
 
 namespace coeb
 {
+
+// mvKeys / mvDepth of a keyframe type that has them (the reference's KeyFrame), for coeb_kfdb_set_stereo;
+// false for a stand-in without them, whose slots then refuse coeb_kfdb_create_new_map_points
+template <class KeyFrameT>
+inline auto stereo_arrays(KeyFrameT* pKF, std::vector<float>& xy, std::vector<float>& depth, int)
+    -> decltype(pKF->mvKeys.size(), pKF->mvDepth.size(), bool())
+{
+    const size_t n = pKF->mvKeys.size();
+    xy.resize(2 * n);
+    for (size_t i = 0; i < n; ++i) {
+        xy[2 * i] = pKF->mvKeys[i].pt.x;
+        xy[2 * i + 1] = pKF->mvKeys[i].pt.y;
+    }
+    depth.assign(pKF->mvDepth.begin(), pKF->mvDepth.end());
+    return true;
+}
+template <class KeyFrameT>
+inline bool stereo_arrays(KeyFrameT*, std::vector<float>&, std::vector<float>&, long)
+{
+    return false;
+}
 
 template <class KeyFrameT>
 class KeyFrameStore
@@ -99,7 +128,10 @@ public:
         coeb_kfdb_keyframe kf{n, desc.empty() ? nullptr : desc.ptr<uint8_t>(0), node.data(), ang.data(), nullptr, nullptr, 0};
         int slot = -1;
         if (coeb_kfdb_add(mDb, &kf, &slot) != COEB_OK) throw std::runtime_error(coeb_last_error(mCtx));
-        if (coeb_kfdb_set_geometry(mDb, slot, keys.data(), pKF->mvuRight.data()) != COEB_OK) {
+        std::vector<float> xy, depth;
+        const bool stereo = stereo_arrays(pKF, xy, depth, 0);
+        if (coeb_kfdb_set_geometry(mDb, slot, keys.data(), pKF->mvuRight.data()) != COEB_OK ||
+            (stereo && ((int)depth.size() != n || coeb_kfdb_set_stereo(mDb, slot, xy.data(), depth.data()) != COEB_OK))) {
             const std::string msg = coeb_last_error(mCtx);
             coeb_kfdb_erase(mDb, slot);
             throw std::runtime_error(msg);
@@ -207,6 +239,99 @@ inline int SearchForTriangulationNeighbors(KeyFrameStore<KeyFrameT>& store, KeyF
                 if (m >= 0) pairs.push_back(std::make_pair((size_t)i, (size_t)m));
             }
             total += nm[j];
+        }
+    }
+    return total;
+}
+
+// One pair that reaches `new MapPoint` (LocalMapping.cc:435): the features and x3D.
+struct NewMapPointPair {
+    size_t idx1, idx2;
+    float x3D[3];
+};
+
+template <class KeyFrameT>
+inline coeb_kf_view kf_view(KeyFrameT* pKF)
+{
+    coeb_kf_view v;
+    const cv::Mat R = pKF->GetRotation(), t = pKF->GetTranslation(), O = pKF->GetCameraCenter();
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) v.Rcw[3 * r + c] = R.template at<float>(r, c);
+        v.tcw[r] = t.template at<float>(r);
+        v.Ow[r] = O.template at<float>(r);
+    }
+    v.fx = pKF->fx; v.fy = pKF->fy; v.cx = pKF->cx; v.cy = pKF->cy;
+    v.invfx = pKF->invfx; v.invfy = pKF->invfy; v.mb = pKF->mb; v.mbf = pKF->mbf;
+    return v;
+}
+
+// The loop of LocalMapping::CreateNewMapPoints from SearchForTriangulation to the scale test (:269-433) for
+// every neighbour vpKF2[j] with vF12[j], in one call per 32 neighbours: vvNewPoints[j] holds, ascending in
+// idx1, the pairs of neighbour j for which the reference reaches `new MapPoint`, in its order -- a feature of
+// pKF1 that an earlier neighbour gave a MapPoint is skipped by the later ones.  Views and masks are read once,
+// before the first call.  A neighbour that is not in the store gets no pairs.  Returns the number of pairs.
+template <class KeyFrameT>
+inline int CreateNewMapPointsNeighbors(KeyFrameStore<KeyFrameT>& store, KeyFrameT* pKF1,
+                                       const std::vector<KeyFrameT*>& vpKF2, const std::vector<cv::Mat>& vF12,
+                                       std::vector<std::vector<NewMapPointPair> >& vvNewPoints)
+{
+    const size_t nKFs = vpKF2.size();
+    if (vF12.size() != nKFs) throw std::invalid_argument("CreateNewMapPointsNeighbors: one F12 per neighbour");
+    vvNewPoints.assign(nKFs, std::vector<NewMapPointPair>());
+    std::unique_lock<std::mutex> lock(store.mutex());
+    const int slot1 = store.slot(pKF1);
+    if (slot1 < 0) throw std::runtime_error("CreateNewMapPointsNeighbors: pKF1 is not in the store");
+    std::vector<uint8_t> has1 = has_map_point(pKF1);
+    const int n1 = (int)has1.size();
+    const coeb_kf_view view1 = kf_view(pKF1);
+    std::vector<size_t> which;
+    std::vector<int32_t> slots;
+    std::vector<std::vector<uint8_t> > has2;
+    std::vector<coeb_kf_view> views;
+    std::vector<float> F, epi;
+    for (size_t j = 0; j < nKFs; ++j) {
+        KeyFrameT* pKF2 = vpKF2[j];
+        const int slot2 = store.slot(pKF2);
+        if (slot2 < 0) continue;
+        which.push_back(j);
+        slots.push_back(slot2);
+        has2.push_back(has_map_point(pKF2));
+        views.push_back(kf_view(pKF2));
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) F.push_back(vF12[j].template at<float>(r, c));
+        // Compute epipole in second image (ORBmatcher.cc:664-670)
+        cv::Mat Cw = pKF1->GetCameraCenter();
+        cv::Mat R2w = pKF2->GetRotation();
+        cv::Mat t2w = pKF2->GetTranslation();
+        cv::Mat C2 = R2w * Cw + t2w;
+        const float invz = 1.0f / C2.template at<float>(2);
+        epi.push_back(pKF2->fx * C2.template at<float>(0) * invz + pKF2->cx);
+        epi.push_back(pKF2->fy * C2.template at<float>(1) * invz + pKF2->cy);
+    }
+    int total = 0;
+    for (size_t done = 0; done < which.size(); done += COEB_TRI_MAX_NEIGHBOURS) {
+        const int nnb = (int)std::min<size_t>(COEB_TRI_MAX_NEIGHBOURS, which.size() - done);
+        std::vector<const uint8_t*> hptr((size_t)nnb);
+        for (int j = 0; j < nnb; ++j) hptr[j] = has2[done + j].empty() ? nullptr : has2[done + j].data();
+        const size_t rows = (size_t)nnb * n1;
+        std::vector<int32_t> match(rows + 1), first((size_t)n1 + 1), nm((size_t)nnb);
+        std::vector<int8_t> status(rows + 1);
+        std::vector<float> x3d(3 * rows + 1);
+        if (coeb_kfdb_create_new_map_points(store.handle(), slot1, &view1, has1.empty() ? nullptr : has1.data(),
+                                            slots.data() + done, nnb, views.data() + done, hptr.data(), F.data() + done * 9,
+                                            epi.data() + done * 2, 0, match.data(), status.data(), x3d.data(), first.data(),
+                                            nm.data()) != COEB_OK)
+            throw std::runtime_error(coeb_last_error(store.ctx()));
+        for (int i = 0; i < n1; ++i) {
+            const int j = first[i];
+            if (j < 0) continue;
+            const size_t e = (size_t)j * n1 + i;
+            NewMapPointPair p;
+            p.idx1 = (size_t)i; p.idx2 = (size_t)match[e];
+            p.x3D[0] = x3d[3 * e]; p.x3D[1] = x3d[3 * e + 1]; p.x3D[2] = x3d[3 * e + 2];
+            vvNewPoints[which[done + j]].push_back(p);        // i ascends: so does every neighbour's list
+            has1[i] = 1;                                      // the MapPoint the caller adds: later neighbours skip it
+            ++total;
         }
     }
     return total;

@@ -84,7 +84,8 @@ ABI_SYMBOLS = [
     "coeb_match_bow",
     "coeb_bow_vector", "coeb_kfdb_create", "coeb_kfdb_destroy", "coeb_kfdb_add", "coeb_kfdb_erase", "coeb_kfdb_clear",
     "coeb_kfdb_size", "coeb_kfdb_query", "coeb_match_bow_kfdb", "coeb_kfdb_set_geometry",
-    "coeb_kfdb_search_triangulation", "coeb_kfdb_fuse_search",
+    "coeb_kfdb_search_triangulation", "coeb_kfdb_fuse_search", "coeb_kfdb_set_stereo",
+    "coeb_kfdb_create_new_map_points",
     "coeb_search_local_points", "coeb_track_local_map", "coeb_track_reference_keyframe",
     "coeb_track_motion_model", "coeb_reloc_refine",
     "coeb_rgbd_stream_create", "coeb_rgbd_stream_destroy", "coeb_rgbd_stream_reset", "coeb_rgbd_stream_frame",
@@ -345,6 +346,10 @@ def lib():
         L.coeb_kfdb_search_triangulation.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                                      C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                                      C.c_void_p, C.c_void_p]
+        L.coeb_kfdb_set_stereo.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.coeb_kfdb_create_new_map_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                      C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.coeb_kfdb_fuse_search.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(FusePointsC), C.POINTER(FuseJobC),
                                             C.c_int, C.c_float, C.c_void_p, C.c_void_p]
         L.coeb_profile_enable.argtypes = [C.c_void_p, C.c_int]
@@ -1355,6 +1360,25 @@ def bow_vector(word, weight, node, normalize_l1=True):
     return w_out[:nw.value].copy(), v_out[:nw.value].copy()
 
 
+# coeb_kf_view: one keyframe as CreateNewMapPoints' loop reads it
+KF_VIEW_DTYPE = np.dtype([("Rcw", np.float32, (9,)), ("tcw", np.float32, (3,)), ("Ow", np.float32, (3,)),
+                          ("fx", np.float32), ("fy", np.float32), ("cx", np.float32), ("cy", np.float32),
+                          ("invfx", np.float32), ("invfy", np.float32), ("mb", np.float32), ("mbf", np.float32)])
+NEWPTS_NO_PAIR, NEWPTS_ACCEPTED, NEWPTS_LOW_PARALLAX, NEWPTS_W_ZERO, NEWPTS_Z1, NEWPTS_Z2, NEWPTS_REPROJ1, \
+    NEWPTS_REPROJ2, NEWPTS_ZERO_DIST, NEWPTS_RATIO = range(10)
+NEWPTS_SRC_TRIANGULATED, NEWPTS_SRC_STEREO1, NEWPTS_SRC_STEREO2 = 1, 2, 3
+
+
+def kf_view(Rcw, tcw, Ow, fx, fy, cx, cy, invfx, invfy, mb, mbf):
+    """One KF_VIEW_DTYPE record; every entry is the caller's (nothing is derived)."""
+    v = np.zeros((), KF_VIEW_DTYPE)
+    v["Rcw"], v["tcw"], v["Ow"] = np.asarray(Rcw, np.float32).reshape(9), np.asarray(tcw, np.float32).reshape(3), \
+        np.asarray(Ow, np.float32).reshape(3)
+    for k, x in zip(("fx", "fy", "cx", "cy", "invfx", "invfy", "mb", "mbf"), (fx, fy, cx, cy, invfx, invfy, mb, mbf)):
+        v[k] = x
+    return v
+
+
 class KeyFrameDatabase:
     """ORB_SLAM2::KeyFrameDatabase for relocalisation, device resident (include/KeyFrameDatabase.h,
     src/KeyFrameDatabase.cc:40-73, 199-309): a keyframe's descriptors, feature-vector nodes, angles
@@ -1530,6 +1554,56 @@ class KeyFrameDatabase:
             _p(F12) if nnb else None, _p(epipole) if nnb else None, int(bool(only_stereo)), int(bool(check_orientation)),
             _p(out) if out.size else None, _p(nm)))
         return out, nm[:nnb]
+
+    def set_stereo(self, slot, key_xy, depth):
+        """What CreateNewMapPoints' triangulation reads of the keyframe in `slot` beyond set_geometry(): the raw
+        mvKeys[i].pt [n, 2] and mvDepth [n].  erase, clear and the reuse of a slot drop it."""
+        key_xy = np.ascontiguousarray(key_xy, np.float32).reshape(-1, 2)
+        depth = np.ascontiguousarray(depth, np.float32)
+        n = self._n.get(int(slot))
+        if n is not None and (len(key_xy) != n or len(depth) != n):
+            raise ValueError("the keyframe of slot %d has %d features" % (slot, n))
+        self.ctx.check(lib().coeb_kfdb_set_stereo(self.h, int(slot), _p(key_xy) if len(key_xy) else None,
+                                                  _p(depth) if len(depth) else None))
+
+    def create_new_map_points(self, slot1, view1, has_mp1, slots2, views2, has_mp2, F12, epipole, only_stereo=False):
+        """LocalMapping::CreateNewMapPoints' search and loop body (LocalMapping.cc:269-433) for every neighbour in
+        one call.  view1 / views2[j]: KF_VIEW_DTYPE records (or what kf_view() takes); the other arguments are
+        search_for_triangulation's.  -> dict(match [nnb, n1] int32, status [nnb, n1] int8: the way out of the loop
+        body (NEWPTS_*), source [nnb, n1] int8: where x3D came from (NEWPTS_SRC_*), x3d [nnb, n1, 3] float32 (NaN
+        where the pair was not accepted), first_ok [n1] int32: the neighbour whose pair becomes the MapPoint,
+        nmatches [nnb])."""
+        slots2 = np.ascontiguousarray(slots2, np.int32)
+        nnb = len(slots2)
+        if len(has_mp2) != nnb:
+            raise ValueError("one has_mp2 mask per neighbour")
+        has_mp1 = np.ascontiguousarray(has_mp1, np.uint8)
+        has_mp2 = [np.ascontiguousarray(m, np.uint8) for m in has_mp2]
+        n1 = self._n.get(int(slot1), len(has_mp1))
+        if len(has_mp1) != n1:
+            raise ValueError("has_mp1 has %d entries, the keyframe %d" % (len(has_mp1), n1))
+        for s, m in zip(slots2, has_mp2):
+            if int(s) in self._n and len(m) != self._n[int(s)]:
+                raise ValueError("has_mp2 of slot %d has %d entries, the keyframe %d" % (s, len(m), self._n[int(s)]))
+        v1 = np.ascontiguousarray(view1, KF_VIEW_DTYPE).reshape(1)
+        v2 = np.ascontiguousarray(views2, KF_VIEW_DTYPE).reshape(-1)
+        if len(v2) != nnb:
+            raise ValueError("one view per neighbour")
+        F12 = np.ascontiguousarray(F12, np.float32).reshape(nnb, 9)
+        epipole = np.ascontiguousarray(epipole, np.float32).reshape(nnb, 2)
+        mp = (C.c_void_p * max(nnb, 1))(*[m.ctypes.data if len(m) else None for m in has_mp2])
+        match = np.full((nnb, n1), -1, np.int32)
+        status = np.zeros((nnb, n1), np.int8)
+        x3d = np.full((nnb, n1, 3), np.nan, np.float32)
+        first = np.full(max(n1, 1), -1, np.int32)
+        nm = np.zeros(max(nnb, 1), np.int32)
+        self.ctx.check(lib().coeb_kfdb_create_new_map_points(
+            self.h, int(slot1), _p(v1), _p(has_mp1) if n1 else None, _p(slots2) if nnb else None, nnb,
+            _p(v2) if nnb else None, mp, _p(F12) if nnb else None, _p(epipole) if nnb else None, int(bool(only_stereo)),
+            _p(match) if match.size else None, _p(status) if match.size else None, _p(x3d) if match.size else None,
+            _p(first), _p(nm)))
+        return dict(match=match, status=status & 15, source=(status >> 4) & 3, x3d=x3d, first_ok=first[:n1],
+                    nmatches=nm[:nnb])
 
     def fuse_search(self, cam, points, jobs, th=3.0):
         """The search of ORBmatcher::Fuse(KF[slot], vpMapPoints[first : first + count], th) for every job in one

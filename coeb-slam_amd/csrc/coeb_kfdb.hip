@@ -5,6 +5,8 @@
 //   SearchByBoW against every candidate                  src/Tracking.cc:1449-1470 (k_match_bow_db)
 //   SearchForTriangulation against every neighbour       src/ORBmatcher.cc:657-824, 140-157 (k_tri_match,
 //                                                        k_tri_rot)
+//   the loop body of CreateNewMapPoints behind it        src/LocalMapping.cc:285-433, src/KeyFrame.cc:615-631
+//                                                        (k_tri_points)
 //   the search of ORBmatcher::Fuse for many (keyframe,   src/ORBmatcher.cc:826-951, src/KeyFrame.cc:569-608
 //   point list) pairs                                    (k_fuse_grid, k_fuse)
 // What a keyframe contributes never changes after KeyFrame::ComputeBoW, so it is uploaded once
@@ -43,9 +45,10 @@ struct KfdbSlab {
     size_t stride = 0;
 };
 // The database's device memory: the keyframe slots (KfdbView), meta[slot][4], and the two arrays the
-// first call that needs them adds (lazy_slab) -- KfdbGeo[mf] per slot (coeb_kfdb_set_geometry) and the
-// keyframe's 64 x 48 feature grid as a CSR, fuse_grid_ints(mf) ints per slot (coeb_kfdb_fuse_search).
-enum { kSlab, kMeta, kGeo, kGrid, kNumSlabs };
+// first call that needs them adds (lazy_slab) -- KfdbGeo[mf] per slot (coeb_kfdb_set_geometry), the
+// keyframe's 64 x 48 feature grid as a CSR, fuse_grid_ints(mf) ints per slot (coeb_kfdb_fuse_search), and
+// KfdbStereo[mf] per slot (coeb_kfdb_set_stereo).
+enum { kSlab, kMeta, kGeo, kGrid, kStereo, kNumSlabs };
 using KfdbSlabs = std::array<KfdbSlab, kNumSlabs>;
 
 struct coeb_kfdb {
@@ -61,6 +64,22 @@ struct coeb_kfdb {
     std::vector<int64_t> seq;       // insertion sequence number per slot
     std::vector<uint8_t> has_geo;   // the slot's keyframe has its geometry
     std::vector<KfdbGridRec> grid_rec;      // the bounds each slot's grid was built with
+    std::vector<uint8_t> has_st;    // the slot's keyframe has its stereo data
+    std::vector<uint8_t> st_conflict;       // ... and a feature with u_right >= 0 and depth <= 0
+    std::vector<std::vector<uint8_t> > is_stereo, depth_pos;    // u_right >= 0 / depth > 0 per feature, as uploaded
+    // has_geo / has_st of a slot go to 0, with what hangs on them
+    void drop(int slot)
+    {
+        has_geo[slot] = has_st[slot] = st_conflict[slot] = 0;
+        grid_rec[slot].built = 0;
+        is_stereo[slot].clear();
+        depth_pos[slot].clear();
+    }
+    void note_conflict(int slot)
+    {
+        st_conflict[slot] = has_geo[slot] && has_st[slot] &&
+                            kfdb_stereo_conflict(is_stereo[slot].data(), depth_pos[slot].data(), n[slot]);
+    }
     KfdbView view() const { return KfdbView{sl[kSlab].p, sl[kSlab].stride, reinterpret_cast<int*>(sl[kMeta].p), mf}; }
 };
 
@@ -388,6 +407,244 @@ __global__ __launch_bounds__(kCsrThreads) void k_tri_rot(TriArgs a, int n1)
                    &s_cnt);
 }
 
+// ============================== k_tri_points ==============================
+// The loop body of LocalMapping::CreateNewMapPoints (:285-433) for every entry of k_tri_match's rows, one lane
+// per (neighbour j = blockIdx.y, feature i of keyframe 1): the views and level tables are the same for a
+// whole workgroup, the two feature records come from the geometry and stereo slabs.  Every pair is decided
+// alone; first[i] takes the lowest accepted j by an integer atomicMin, which no order of arrival changes.
+// No LDS.
+// The null vector of the 4x4 system A (:323-332) is the canonical form of DESIGN.md s2.1: a one-sided
+// (Hestenes) Jacobi in float32 on A's columns, V accumulated from the identity, the pairs (0,1) (0,2) (0,3)
+// (1,2) (1,3) (2,3) in that order, at most kJacobiSweeps sweeps, a pair left alone where |ap.aq| <=
+// kJacobiEps * sqrt(|ap|^2 |aq|^2), a lane done after a sweep without a rotation (its own: no lane looks at
+// another's); the column of V under the smallest column norm, the last of equals.  A and V stay in
+// registers: every index below is a compile-time constant.  It is not cv::SVD's vt.row(3) bit for bit, and
+// no test asks that; the sign of the vector cancels in xyz / w.
+// Float forms: xn = ((u - cx) * invfx, (v - cy) * invfy, 1) in float; Rwc * xn as cv::Mat's
+// small gemm (float products summed left to right), a gemm's addend added in double; Mat::dot and cv::norm
+// in double; the rows of A as addWeighted leaves them, fl(xn * T2k) - T0k; x3D / w as a multiply by
+// (float)(1.0 / w); z = (float)(dot + tcw[2]); invz = (float)(1.0 / z); u = fma(fx * x, invz, cx), u_r =
+// fma(-mbf, invz, u), e2 = fma(ex, ex, ey * ey) then fma(er, er, .), compared in double with the double
+// products 5.991 * sigma2 and 7.8 * sigma2; the stereo parallax bound cos(2 atan2(mb / 2, depth)) as
+// (d^2 - h^2) / (d^2 + h^2) in double (no libm: it only feeds comparisons).
+constexpr int kPtsThreads = 256;
+constexpr int kJacobiSweeps = 12;
+constexpr float kJacobiEps = 4.76837158203125e-07f;         // 2^-21
+
+struct PtsArgs {
+    const uint8_t* geo; size_t geo_stride;
+    const uint8_t* st; size_t st_stride;
+    int slot1;
+    const int* tab;             // [nnb][2]: slot2, (the mask offset)
+    const coeb_kf_view* view;   // keyframe 1, then the neighbours
+    const float* scale;         // [COEB_MAXL] mvScaleFactors
+    const float* sigma2;        // [COEB_MAXL] mvLevelSigma2
+    float ratio_factor;
+    int n1;
+    const int* match;           // [nnb][n1], k_tri_match's
+    int8_t* status; float* x3d; int* first;
+};
+
+__device__ __forceinline__ float sq4(const float* a)
+{
+    return __fmaf_rn(a[3], a[3], __fmaf_rn(a[2], a[2], __fmaf_rn(a[1], a[1], a[0] * a[0])));
+}
+
+// one pair of columns; true when it was rotated
+template <int P, int Q>
+__device__ __forceinline__ bool jacobi_pair(float (&a)[4][4], float (&v)[4][4])
+{
+    const float alpha = sq4(a[P]), beta = sq4(a[Q]);
+    const float gamma =
+        __fmaf_rn(a[P][3], a[Q][3], __fmaf_rn(a[P][2], a[Q][2], __fmaf_rn(a[P][1], a[Q][1], a[P][0] * a[Q][0])));
+    if (fabsf(gamma) <= kJacobiEps * sqrtf(alpha * beta)) return false;
+    const float zeta = (beta - alpha) / (2.0f * gamma);
+    const float t = copysignf(1.0f, zeta) / (fabsf(zeta) + sqrtf(__fmaf_rn(zeta, zeta, 1.0f)));
+    const float c = 1.0f / sqrtf(__fmaf_rn(t, t, 1.0f));
+    const float s = c * t;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const float x = a[P][r], y = a[Q][r];
+        a[P][r] = __fmaf_rn(c, x, -(s * y));
+        a[Q][r] = __fmaf_rn(s, x, c * y);
+        const float vx = v[P][r], vy = v[Q][r];
+        v[P][r] = __fmaf_rn(c, vx, -(s * vy));
+        v[Q][r] = __fmaf_rn(s, vx, c * vy);
+    }
+    return true;
+}
+
+// a[c][r] = A(r, c) on entry; out = the right singular vector of A's smallest singular value
+__device__ __forceinline__ void jacobi_null4(float (&a)[4][4], float* out)
+{
+    float v[4][4];
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) v[c][r] = c == r ? 1.0f : 0.0f;
+    bool active = true;
+    for (int sweep = 0; sweep < kJacobiSweeps && active; sweep++) {
+        bool rot = jacobi_pair<0, 1>(a, v);
+        rot |= jacobi_pair<0, 2>(a, v);
+        rot |= jacobi_pair<0, 3>(a, v);
+        rot |= jacobi_pair<1, 2>(a, v);
+        rot |= jacobi_pair<1, 3>(a, v);
+        rot |= jacobi_pair<2, 3>(a, v);
+        active = rot;
+    }
+    float best = sq4(a[0]);
+#pragma unroll
+    for (int r = 0; r < 4; r++) out[r] = v[0][r];
+#pragma unroll
+    for (int c = 1; c < 4; c++) {
+        const float s = sq4(a[c]);
+        if (s <= best) {
+            best = s;
+#pragma unroll
+            for (int r = 0; r < 4; r++) out[r] = v[c][r];
+        }
+    }
+}
+
+// Rwc * x for Rwc = Rcw transposed: cv::Mat's small gemm
+__device__ __forceinline__ void rwc_mul(const float* Rcw, const float* x, float* out)
+{
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        float t = Rcw[0 + k] * x[0] + Rcw[3 + k] * x[1];
+        t = t + Rcw[6 + k] * x[2];
+        out[k] = t;
+    }
+}
+
+// Rcw.row(r).dot(x3Dt) + tcw(r), to float
+__device__ __forceinline__ float row_dot_add(const coeb_kf_view& V, int r, const float* X)
+{
+    double d = 0.0;
+    d += (double)V.Rcw[3 * r + 0] * (double)X[0];
+    d += (double)V.Rcw[3 * r + 1] * (double)X[1];
+    d += (double)V.Rcw[3 * r + 2] * (double)X[2];
+    return (float)(d + (double)V.tcw[r]);
+}
+
+// cos(2 atan2(mb / 2, depth)) = (d^2 - h^2) / (d^2 + h^2)
+__device__ __forceinline__ float stereo_parallax_bound(float mb, float depth)
+{
+    const double h = (double)(mb / 2.0f), d = (double)depth;
+    return (float)((d * d - h * h) / (d * d + h * h));
+}
+
+// KeyFrame::UnprojectStereo (KeyFrame.cc:615-631); the depth is positive (coeb_kfdb_create_new_map_points refuses otherwise)
+__device__ __forceinline__ void unproject_stereo(const coeb_kf_view& V, const KfdbStereo& s, float* X)
+{
+    const float z = s.depth;
+    const float Pc[3] = {(s.kx - V.cx) * z * V.invfx, (s.ky - V.cy) * z * V.invfy, z};
+    float t[3];
+    rwc_mul(V.Rcw, Pc, t);
+#pragma unroll
+    for (int k = 0; k < 3; k++) X[k] = (float)((double)t[k] + (double)V.Ow[k]);
+}
+
+// the reprojection test of one side (:363-414); mbf is keyframe 1's on both sides (:407)
+__device__ __forceinline__ bool reproj_fails(const coeb_kf_view& V, float mbf, const float* X, float z, const KfdbGeo& g,
+                                             float sigma2)
+{
+    const float x = row_dot_add(V, 0, X), y = row_dot_add(V, 1, X);
+    const float invz = (float)(1.0 / (double)z);
+    const float u = __fmaf_rn(V.fx * x, invz, V.cx), v = __fmaf_rn(V.fy * y, invz, V.cy);
+    const float ex = u - g.x, ey = v - g.y;
+    float e2 = __fmaf_rn(ex, ex, ey * ey);
+    if (!(g.u_right >= 0)) return (double)e2 > 5.991 * (double)sigma2;
+    const float er = __fmaf_rn(-mbf, invz, u) - g.u_right;
+    e2 = __fmaf_rn(er, er, e2);
+    return (double)e2 > 7.8 * (double)sigma2;
+}
+
+__global__ __launch_bounds__(kPtsThreads) void k_tri_points(PtsArgs a)
+{
+    const int i = blockIdx.x * kPtsThreads + threadIdx.x, j = blockIdx.y;
+    if (i >= a.n1) return;
+    const size_t e = (size_t)j * a.n1 + i;
+    const int i2 = a.match[e];
+    if (i2 < 0) { a.status[e] = kNpNoPair; return; }
+    const int slot2 = a.tab[2 * j];
+    const coeb_kf_view& V1 = a.view[0];
+    const coeb_kf_view& V2 = a.view[1 + j];
+    const KfdbGeo g1 = reinterpret_cast<const KfdbGeo*>(a.geo + a.slot1 * a.geo_stride)[i];
+    const KfdbGeo g2 = reinterpret_cast<const KfdbGeo*>(a.geo + slot2 * a.geo_stride)[i2];
+    const KfdbStereo s1 = reinterpret_cast<const KfdbStereo*>(a.st + a.slot1 * a.st_stride)[i];
+    const KfdbStereo s2 = reinterpret_cast<const KfdbStereo*>(a.st + slot2 * a.st_stride)[i2];
+    const bool st1 = g1.u_right >= 0, st2 = g2.u_right >= 0;
+    // the parallax between the rays (:300-317)
+    const float xn1[3] = {(g1.x - V1.cx) * V1.invfx, (g1.y - V1.cy) * V1.invfy, 1.0f};
+    const float xn2[3] = {(g2.x - V2.cx) * V2.invfx, (g2.y - V2.cy) * V2.invfy, 1.0f};
+    float ray1[3], ray2[3];
+    rwc_mul(V1.Rcw, xn1, ray1);
+    rwc_mul(V2.Rcw, xn2, ray2);
+    double dot = 0.0;
+    dot += (double)ray1[0] * (double)ray2[0];
+    dot += (double)ray1[1] * (double)ray2[1];
+    dot += (double)ray1[2] * (double)ray2[2];
+    const float cos_rays = (float)(dot / (norm3(ray1) * norm3(ray2)));
+    float cps1 = cos_rays + 1.0f, cps2 = cps1;
+    if (st1) cps1 = stereo_parallax_bound(V1.mb, s1.depth);
+    else if (st2) cps2 = stereo_parallax_bound(V2.mb, s2.depth);
+    const float cps = cps2 < cps1 ? cps2 : cps1;
+    float X[3];
+    int src;
+    if (cos_rays < cps && cos_rays > 0.0f && (st1 || st2 || (double)cos_rays < 0.9998)) {
+        src = COEB_NEWPTS_SRC_TRIANGULATED;
+        float A[4][4];                              // A[c][r] = the reference's A(r, c)
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const float t10 = c < 3 ? V1.Rcw[c] : V1.tcw[0], t11 = c < 3 ? V1.Rcw[3 + c] : V1.tcw[1];
+            const float t12 = c < 3 ? V1.Rcw[6 + c] : V1.tcw[2];
+            const float t20 = c < 3 ? V2.Rcw[c] : V2.tcw[0], t21 = c < 3 ? V2.Rcw[3 + c] : V2.tcw[1];
+            const float t22 = c < 3 ? V2.Rcw[6 + c] : V2.tcw[2];
+            A[c][0] = xn1[0] * t12 - t10;
+            A[c][1] = xn1[1] * t12 - t11;
+            A[c][2] = xn2[0] * t22 - t20;
+            A[c][3] = xn2[1] * t22 - t21;
+        }
+        float h[4];
+        jacobi_null4(A, h);
+        if (h[3] == 0.0f) { a.status[e] = (int8_t)(kNpW0 | (src << 4)); return; }
+        const float inv = (float)(1.0 / (double)h[3]);
+        X[0] = h[0] * inv; X[1] = h[1] * inv; X[2] = h[2] * inv;
+    } else if (st1 && cps1 < cps2) {
+        src = COEB_NEWPTS_SRC_STEREO1;
+        unproject_stereo(V1, s1, X);
+    } else if (st2 && cps2 < cps1) {
+        src = COEB_NEWPTS_SRC_STEREO2;
+        unproject_stereo(V2, s2, X);
+    } else {
+        a.status[e] = kNpLowParallax;
+        return;
+    }
+    int code = kNpAccepted;
+    const float z1 = row_dot_add(V1, 2, X);
+    const float z2 = row_dot_add(V2, 2, X);
+    if (z1 <= 0.0f) code = kNpZ1;
+    else if (z2 <= 0.0f) code = kNpZ2;
+    else if (reproj_fails(V1, V1.mbf, X, z1, g1, a.sigma2[g1.octave])) code = kNpReproj1;
+    else if (reproj_fails(V2, V1.mbf, X, z2, g2, a.sigma2[g2.octave])) code = kNpReproj2;
+    else {
+        const float d1[3] = {X[0] - V1.Ow[0], X[1] - V1.Ow[1], X[2] - V1.Ow[2]};
+        const float d2[3] = {X[0] - V2.Ow[0], X[1] - V2.Ow[1], X[2] - V2.Ow[2]};
+        const float dist1 = (float)norm3(d1), dist2 = (float)norm3(d2);
+        if (dist1 == 0.0f || dist2 == 0.0f) code = kNpZeroDist;
+        else {
+            const float ratio_dist = dist2 / dist1, ratio_oct = a.scale[g1.octave] / a.scale[g2.octave];
+            if (ratio_dist * a.ratio_factor < ratio_oct || ratio_dist > ratio_oct * a.ratio_factor) code = kNpRatio;
+        }
+    }
+    a.status[e] = (int8_t)(code | (src << 4));
+    if (code == kNpAccepted) {
+        a.x3d[3 * e] = X[0]; a.x3d[3 * e + 1] = X[1]; a.x3d[3 * e + 2] = X[2];
+        atomicMin(&a.first[i], j);
+    }
+}
+
 // ============================== k_fuse_grid ==============================
 // Frame::AssignFeaturesToGrid (Frame.cc:396-411; a KeyFrame copies the Frame's grid) of one stored
 // keyframe per workgroup, as a CSR in cell order (ix outer, iy inner, index order inside a cell):
@@ -693,6 +950,7 @@ int grow(coeb_kfdb* db, int want)
     db->cap = ncap;
     db->grid_rec.resize(ncap, KfdbGridRec{});
     db->used.resize(ncap, 0); db->has_geo.resize(ncap, 0); db->n.resize(ncap, 0); db->nd.resize(ncap, 0); db->seq.resize(ncap, 0);
+    db->has_st.resize(ncap, 0); db->st_conflict.resize(ncap, 0); db->is_stereo.resize(ncap); db->depth_pos.resize(ncap);
     return 0;
 }
 
@@ -785,8 +1043,7 @@ int coeb_kfdb_add(coeb_kfdb* db, const coeb_kfdb_keyframe* kf, int* slot_out)
     HIP_TRY(c, hipMemcpyAsync(c->pin, v.csr(slot), 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     db->used[slot] = 1;
-    db->has_geo[slot] = 0;
-    db->grid_rec[slot].built = 0;
+    db->drop(slot);
     db->n[slot] = n;
     db->nd[slot] = reinterpret_cast<const int32_t*>(c->pin)[0];
     db->seq[slot] = db->next_seq++;
@@ -804,8 +1061,7 @@ int coeb_kfdb_erase(coeb_kfdb* db, int slot)
     (void)hipSetDevice(c->device);
     HIP_TRY(c, hipMemsetAsync(db->sl[kMeta].p + slot * 16, 0, 16, main_stream(c)));
     db->used[slot] = 0;
-    db->has_geo[slot] = 0;
-    db->grid_rec[slot].built = 0;
+    db->drop(slot);
     db->n[slot] = db->nd[slot] = 0;
     db->nkf--;
     return COEB_OK;
@@ -818,8 +1074,7 @@ int coeb_kfdb_clear(coeb_kfdb* db)
     (void)hipSetDevice(c->device);
     HIP_TRY(c, hipMemsetAsync(db->sl[kMeta].p, 0, (size_t)db->cap * 16, main_stream(c)));
     std::fill(db->used.begin(), db->used.end(), 0);
-    std::fill(db->has_geo.begin(), db->has_geo.end(), 0);
-    std::fill(db->grid_rec.begin(), db->grid_rec.end(), KfdbGridRec{});
+    for (int sl = 0; sl < db->cap; sl++) db->drop(sl);
     std::fill(db->n.begin(), db->n.end(), 0);
     std::fill(db->nd.begin(), db->nd.end(), 0);
     db->nslots = db->nkf = 0;
@@ -966,6 +1221,37 @@ int coeb_kfdb_set_geometry(coeb_kfdb* db, int slot, const coeb_keypoint* keys_un
     }
     db->has_geo[slot] = 1;
     db->grid_rec[slot].built = 0;
+    // host-only bookkeeping for coeb_kfdb_create_new_map_points' refusal of a stereo feature without depth,
+    // whichever of this call and coeb_kfdb_set_stereo comes last; the slab and every other call are as before
+    db->is_stereo[slot].resize((size_t)n);
+    for (int i = 0; i < n; i++) db->is_stereo[slot][i] = u_right[i] >= 0;
+    db->note_conflict(slot);
+    return COEB_OK;
+}
+
+int coeb_kfdb_set_stereo(coeb_kfdb* db, int slot, const float* key_xy, const float* depth)
+{
+    if (!db || !db->c) return db_err(db, "coeb_kfdb_set_stereo: invalid arguments");
+    if (slot < 0 || slot >= db->nslots || !db->used[slot]) return db_err(db, "coeb_kfdb_set_stereo: no keyframe in that slot");
+    coeb_ctx* c = db->c;
+    const int n = db->n[slot];
+    if (n && (!key_xy || !depth)) return db_err(db, "coeb_kfdb_set_stereo: missing keyframe arrays");
+    (void)hipSetDevice(c->device);
+    int rc;
+    if ((rc = pinned(c, (size_t)n * sizeof(KfdbStereo)))) return rc;
+    std::vector<uint8_t> pos((size_t)n);
+    if (!kfdb_pack_stereo(key_xy, depth, n, reinterpret_cast<KfdbStereo*>(c->pin), pos.data()))
+        return db_err(db, "coeb_kfdb_set_stereo: a keypoint or depth entry is not finite");
+    KfdbSlab& st = db->sl[kStereo];
+    if ((rc = lazy_slab(db, st, (size_t)db->mf * sizeof(KfdbStereo), "stereo data"))) return rc;
+    if (n) {
+        hipStream_t s = main_stream(c);
+        HIP_TRY(c, hipMemcpyAsync(st.p + slot * st.stride, c->pin, (size_t)n * sizeof(KfdbStereo), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipStreamSynchronize(s));       // the page-locked buffer is the next call's
+    }
+    db->has_st[slot] = 1;
+    db->depth_pos[slot].swap(pos);
+    db->note_conflict(slot);
     return COEB_OK;
 }
 
@@ -1023,6 +1309,77 @@ int coeb_kfdb_search_triangulation(coeb_kfdb* db, int slot1, const uint8_t* has_
     if ((rc = st.finish(c, s, o_m, back_end, false))) return rc;
     memcpy(match_out, st.host<int32_t>(o_m), rows * 4);
     memcpy(nmatches, st.host<int32_t>(o_nm), (size_t)nnb * 4);
+    return COEB_OK;
+}
+
+// Uploaded: what coeb_kfdb_search_triangulation uploads without the histograms, the views, first_ok as
+// INT_MAX.  Copied back: the match rows, first_ok, x3d and the status bytes, one range.
+int coeb_kfdb_create_new_map_points(coeb_kfdb* db, int slot1, const coeb_kf_view* view1, const uint8_t* has_mp1,
+                                    const int32_t* slots2, int nnb, const coeb_kf_view* views2,
+                                    const uint8_t* const* has_mp2, const float* F12, const float* epipole,
+                                    int only_stereo, int32_t* match_out, int8_t* status, float* x3d,
+                                    int32_t* first_ok, int32_t* nmatches)
+{
+    const std::string w("coeb_kfdb_create_new_map_points: ");
+    if (!db || !db->c) return db_err(db, (w + "invalid arguments").c_str());
+    coeb_ctx* c = db->c;
+    const char* why = kfdb_newpts_check(db->used.data(), db->has_geo.data(), db->has_st.data(), db->st_conflict.data(),
+                                        db->n.data(), db->nslots, slot1, view1, has_mp1, slots2, nnb, views2, has_mp2, F12,
+                                        epipole, match_out, status, x3d, first_ok, nmatches);
+    if (why) return db_err(db, (w + why).c_str());
+    const int n1 = db->n[slot1];
+    for (int i = 0; i < n1; i++) first_ok[i] = -1;
+    if (nnb == 0) return COEB_OK;
+    if (n1 == 0) {
+        memset(nmatches, 0, (size_t)nnb * 4);
+        return COEB_OK;
+    }
+    (void)hipSetDevice(c->device);
+    hipStream_t s = main_stream(c);
+    std::vector<uint8_t> masks;
+    std::vector<int32_t> tab;
+    kfdb_tri_pack(db->n.data(), slots2, nnb, has_mp2, masks, tab);
+    const size_t rows = (size_t)nnb * n1;
+    const std::vector<int32_t> none((size_t)n1, INT_MAX);
+    std::vector<coeb_kf_view> views(1, *view1);         // keyframe 1, then the neighbours
+    views.insert(views.end(), views2, views2 + nnb);
+    Staged st;
+    const size_t o_h1 = st.add(has_mp1, (size_t)n1), o_mk = st.add(masks.data(), masks.size());
+    const size_t o_tab = st.add(tab.data(), tab.size() * 4), o_F = st.add(F12, (size_t)nnb * 36);
+    const size_t o_e = st.add(epipole, (size_t)nnb * 8);
+    const size_t o_sc = st.add(c->tab.scale, sizeof(float) * COEB_MAXL), o_sg = st.add(c->tab.sigma2, sizeof(float) * COEB_MAXL);
+    const size_t o_v1 = st.add(views.data(), views.size() * sizeof(coeb_kf_view));
+    // results: the match rows and first_ok with their initial values, then what k_tri_points writes
+    const size_t o_m = st.fill(0xFF, rows * 4), o_first = st.add(none.data(), (size_t)n1 * 4);
+    const size_t o_x = st.take(rows * 12), o_st = st.take(rows);
+    const size_t back_end = st.end();
+    int rc;
+    if ((rc = st.stage(c, s, false))) return rc;
+    TriArgs a;
+    a.v = db->view(); a.geo = db->sl[kGeo].p; a.geo_stride = db->sl[kGeo].stride; a.slot1 = slot1;
+    a.has1 = st.dev<uint8_t>(o_h1); a.tab = st.dev<int>(o_tab); a.masks = st.dev<uint8_t>(o_mk);
+    a.F = st.dev<float>(o_F); a.epi = st.dev<float>(o_e); a.scale = st.dev<float>(o_sc); a.sigma2 = st.dev<float>(o_sg);
+    a.only_stereo = only_stereo ? 1 : 0; a.check_ori = 0; a.cs = n1;
+    a.match = st.dev<int>(o_m); a.bin = nullptr; a.hist = nullptr; a.nm = nullptr;     // read under check_ori alone
+    if (db->nd[slot1]) {
+        prof_begin(&c->hook, "k_tri_match", s);
+        hipLaunchKernelGGL(k_tri_match, dim3(db->nd[slot1], nnb), dim3(kTriThreads), 0, s, a);
+        prof_end(&c->hook, s);
+    }
+    PtsArgs p;
+    p.geo = a.geo; p.geo_stride = a.geo_stride; p.st = db->sl[kStereo].p; p.st_stride = db->sl[kStereo].stride;
+    p.slot1 = slot1; p.tab = a.tab; p.view = st.dev<coeb_kf_view>(o_v1); p.scale = a.scale; p.sigma2 = a.sigma2;
+    p.ratio_factor = 1.5f * (float)c->tab.scale_factor;
+    p.n1 = n1; p.match = a.match;
+    p.status = st.dev<int8_t>(o_st); p.x3d = st.dev<float>(o_x); p.first = st.dev<int>(o_first);
+    prof_begin(&c->hook, "k_tri_points", s);
+    hipLaunchKernelGGL(k_tri_points, dim3((n1 + kPtsThreads - 1) / kPtsThreads, nnb), dim3(kPtsThreads), 0, s, p);
+    prof_end(&c->hook, s);
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = st.finish(c, s, o_m, back_end, false))) return rc;
+    memcpy(match_out, st.host<int32_t>(o_m), rows * 4);
+    memcpy(status, st.host<int8_t>(o_st), rows);
+    kfdb_newpts_unpack(match_out, status, st.host<float>(o_x), st.host<int32_t>(o_first), nnb, n1, x3d, first_ok, nmatches);
     return COEB_OK;
 }
 

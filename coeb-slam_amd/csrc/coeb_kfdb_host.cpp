@@ -194,3 +194,79 @@ void kfdb_fuse_pack(const coeb_fuse_job* jobs, int njobs, const KfdbGridRec* rec
     for (int j = 0; j < njobs; j++)
         if (tab[j].skip_off >= 0) std::copy(jobs[j].skip, jobs[j].skip + jobs[j].count, skip.begin() + tab[j].skip_off);
 }
+
+// ---- CreateNewMapPoints over stored keyframes: the stereo records and argument rules ----
+bool kfdb_pack_stereo(const float* key_xy, const float* depth, int n, KfdbStereo* out, uint8_t* depth_pos)
+{
+    for (int i = 0; i < n; i++) {
+        const float x = key_xy[2 * i], y = key_xy[2 * i + 1], d = depth[i];
+        if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(d)) return false;
+        out[i] = KfdbStereo{x, y, d, 0.f};
+        depth_pos[i] = d > 0.0f;
+    }
+    return true;
+}
+
+bool kfdb_stereo_conflict(const uint8_t* is_stereo, const uint8_t* depth_pos, int n)
+{
+    for (int i = 0; i < n; i++)
+        if (is_stereo[i] && !depth_pos[i]) return true;
+    return false;
+}
+
+static bool view_finite(const coeb_kf_view& v)
+{
+    for (int k = 0; k < 9; k++)
+        if (!std::isfinite(v.Rcw[k])) return false;
+    for (int k = 0; k < 3; k++)
+        if (!std::isfinite(v.tcw[k]) || !std::isfinite(v.Ow[k])) return false;
+    const float cam[8] = {v.fx, v.fy, v.cx, v.cy, v.invfx, v.invfy, v.mb, v.mbf};
+    for (int k = 0; k < 8; k++)
+        if (!std::isfinite(cam[k])) return false;
+    return true;
+}
+
+const char* kfdb_newpts_check(const uint8_t* used, const uint8_t* geo, const uint8_t* stereo, const uint8_t* conflict,
+                              const int* n, int nslots, int slot1, const coeb_kf_view* view1, const uint8_t* has_mp1,
+                              const int32_t* slots2, int nnb, const coeb_kf_view* views2, const uint8_t* const* has_mp2,
+                              const float* F12, const float* epipole, const int32_t* match_out, const int8_t* status,
+                              const float* x3d, const int32_t* first_ok, const int32_t* nmatches)
+{
+    if (const char* why = kfdb_tri_check(used, geo, n, nslots, slot1, has_mp1, slots2, nnb, has_mp2, F12, epipole, match_out,
+                                         nmatches))
+        return why;
+    if (!stereo[slot1]) return "slot1 has no stereo data (coeb_kfdb_set_stereo)";
+    if (conflict[slot1]) return "slot1 has a feature with u_right >= 0 and depth <= 0";
+    if (!view1) return "missing view of keyframe 1";
+    if (!view_finite(*view1)) return "a pose or camera entry of keyframe 1 is not finite";
+    if (n[slot1] && !first_ok) return "missing first_ok";
+    if (nnb == 0) return nullptr;
+    if (!views2) return "missing views of the neighbours";
+    if (n[slot1] && (!status || !x3d)) return "missing status or x3d";
+    for (int j = 0; j < nnb; j++) {
+        const int s = slots2[j];
+        if (s == slot1) return "a neighbour is keyframe 1 itself";
+        for (int k = 0; k < j; k++)
+            if (slots2[k] == s) return "a neighbour's slot is repeated";
+        if (!stereo[s]) return "a neighbour's slot has no stereo data (coeb_kfdb_set_stereo)";
+        if (conflict[s]) return "a neighbour has a feature with u_right >= 0 and depth <= 0";
+        if (!view_finite(views2[j])) return "a pose or camera entry of a neighbour is not finite";
+    }
+    return nullptr;
+}
+
+void kfdb_newpts_unpack(const int32_t* match, const int8_t* status, const float* x3d_dev, const int32_t* first_dev,
+                        int nnb, int n1, float* x3d, int32_t* first_ok, int32_t* nmatches)
+{
+    for (int j = 0; j < nnb; j++) {
+        int nm = 0;
+        for (int i = 0; i < n1; i++) {
+            const size_t e = (size_t)j * n1 + i;
+            nm += match[e] >= 0;
+            if ((status[e] & 15) == kNpAccepted)
+                for (int k = 0; k < 3; k++) x3d[3 * e + k] = x3d_dev[3 * e + k];
+        }
+        nmatches[j] = nm;
+    }
+    for (int i = 0; i < n1; i++) first_ok[i] = first_dev[i] >= nnb ? -1 : first_dev[i];
+}

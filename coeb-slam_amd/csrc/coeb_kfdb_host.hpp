@@ -58,3 +58,37 @@ const char* kfdb_fuse_check(const uint8_t* used, const uint8_t* geo, int nslots,
 // distinct slots whose grid has to be built (rec[slot] not current for cam), ascending.
 void kfdb_fuse_pack(const coeb_fuse_job* jobs, int njobs, const KfdbGridRec* rec, const coeb_camera* cam,
                     std::vector<KfdbFuseJob>& tab, std::vector<uint8_t>& skip, std::vector<int32_t>& build);
+
+// ---- the rest of LocalMapping::CreateNewMapPoints' loop body over stored keyframes ----
+// What coeb_kfdb_set_stereo keeps of one feature: the raw mvKeys[i].pt and mvDepth[i] that
+// KeyFrame::UnprojectStereo and the parallax bound read.
+struct KfdbStereo { float kx, ky, depth, pad; };
+static_assert(sizeof(KfdbStereo) == 16, "the stereo slab holds 16 bytes per feature");
+
+// out[0 .. n) from the keyframe's arrays (key_xy [n][2]), depth_pos[i] = depth[i] > 0; false, with out
+// unspecified, when an entry is not finite
+bool kfdb_pack_stereo(const float* key_xy, const float* depth, int n, KfdbStereo* out, uint8_t* depth_pos);
+
+// a feature with u_right >= 0 whose depth is not positive: UnprojectStereo would return an empty Mat
+bool kfdb_stereo_conflict(const uint8_t* is_stereo, const uint8_t* depth_pos, int n);
+
+// What k_tri_points writes per (neighbour, feature of keyframe 1): the way out of the loop body in the low
+// four bits, the source of x3D (COEB_NEWPTS_SRC_*) in bits 4 and 5.
+enum {
+    kNpNoPair = 0, kNpAccepted = 1, kNpLowParallax = 2, kNpW0 = 3, kNpZ1 = 4, kNpZ2 = 5, kNpReproj1 = 6,
+    kNpReproj2 = 7, kNpZeroDist = 8, kNpRatio = 9,
+};
+
+// The rules of coeb_kfdb_create_new_map_points' arguments that need no device, behind those of
+// kfdb_tri_check.  stereo[slot] != 0: the slot has its stereo data; conflict[slot] != 0:
+// kfdb_stereo_conflict holds for it.  nullptr: the call may go on; else the text of its COEB_EINVAL.
+const char* kfdb_newpts_check(const uint8_t* used, const uint8_t* geo, const uint8_t* stereo, const uint8_t* conflict,
+                              const int* n, int nslots, int slot1, const coeb_kf_view* view1, const uint8_t* has_mp1,
+                              const int32_t* slots2, int nnb, const coeb_kf_view* views2, const uint8_t* const* has_mp2,
+                              const float* F12, const float* epipole, const int32_t* match_out, const int8_t* status,
+                              const float* x3d, const int32_t* first_ok, const int32_t* nmatches);
+
+// What the host does with the downloaded rows: x3d of the accepted entries into the caller's array (every other
+// entry untouched), first_ok's INT_MAX to -1, nmatches[j] = the pairs of row j.
+void kfdb_newpts_unpack(const int32_t* match, const int8_t* status, const float* x3d_dev, const int32_t* first_dev,
+                        int nnb, int n1, float* x3d, int32_t* first_ok, int32_t* nmatches);

@@ -107,6 +107,8 @@
  *                                      LocalMapping::CreateNewMapPoints  src/LocalMapping.cc:255-270,
  *                                      src/ORBmatcher.cc:657-824 (coeb_kfdb_set_geometry: the
  *                                      KeyFrame's mvKeysUn / mvuRight it reads)
+ *   coeb_kfdb_create_new_map_points <- that search and the loop body behind it, src/LocalMapping.cc:271-433
+ *                                      (coeb_kfdb_set_stereo: the KeyFrame's mvKeys / mvDepth it reads)
  *   coeb_kfdb_fuse_search           <- the search of ORBmatcher::Fuse (src/ORBmatcher.cc:826-951) for
  *                                      the loops of LocalMapping::SearchInNeighbors
  *                                      src/LocalMapping.cc:455-535
@@ -138,6 +140,10 @@ extern "C" {
  * changes (3: coeb_rgbd_preprocess gained channels/depth_type and a byte depth stride); the
  * adapters compare it with coeb_abi_version() of the loaded library and refuse a mismatch. */
 #define COEB_ABI_VERSION 3
+/* Entry points added since (coeb_kfdb_search_triangulation, coeb_kfdb_fuse_search, coeb_kfdb_set_stereo,
+ * coeb_kfdb_create_new_map_points) do not move the number: no existing signature or layout changed.  A
+ * client built against this header therefore passes the coeb_abi_version() check against an older library
+ * and fails at symbol lookup instead. */
 int coeb_abi_version(void);
 
 #define COEB_MAX_LEVELS 16
@@ -742,6 +748,59 @@ int coeb_kfdb_set_geometry(coeb_kfdb* db, int slot, const coeb_keypoint* keys_un
 int coeb_kfdb_search_triangulation(coeb_kfdb* db, int slot1, const uint8_t* has_mp1, const int32_t* slots2, int nnb,
                                    const uint8_t* const* has_mp2, const float* F12, const float* epipole,
                                    int only_stereo, int check_orientation, int32_t* match_out, int32_t* nmatches);
+
+/* ---- the loop body of LocalMapping::CreateNewMapPoints for all neighbours (src/LocalMapping.cc:271-433) ----
+ * coeb_kfdb_set_stereo uploads what the triangulation reads of a stored keyframe beyond the geometry: the raw
+ * mvKeys[i].pt (key_xy [n][2]; KeyFrame::UnprojectStereo, src/KeyFrame.cc:615-631) and mvDepth[i] of the
+ * slot's n features.  They live in a slab of their own (16 bytes per feature, allocated by the first call,
+ * growing with the slots); erase, clear and the reuse of a slot drop them, a second call replaces them.
+ * COEB_EINVAL for an empty or out-of-range slot, a NULL array with n > 0 or an entry that is not finite. */
+int coeb_kfdb_set_stereo(coeb_kfdb* db, int slot, const float* key_xy, const float* depth);
+typedef struct {                       /* one keyframe as the loop reads it; nothing is derived here */
+    float Rcw[9], tcw[3], Ow[3];       /* GetRotation / GetTranslation / GetCameraCenter (Rwc is Rcw transposed) */
+    float fx, fy, cx, cy, invfx, invfy, mb, mbf;
+} coeb_kf_view;
+/* status[j][i]: the low four bits say how the pair (i, match_out[j][i]) left the loop body */
+#define COEB_NEWPTS_NO_PAIR 0          /* match_out[j][i] < 0 */
+#define COEB_NEWPTS_ACCEPTED 1         /* reached `new MapPoint` (:435) */
+#define COEB_NEWPTS_LOW_PARALLAX 2     /* :350, no stereo and very low parallax */
+#define COEB_NEWPTS_W_ZERO 3           /* :334, x3D[3] == 0 */
+#define COEB_NEWPTS_Z1 4               /* :356 */
+#define COEB_NEWPTS_Z2 5               /* :360 */
+#define COEB_NEWPTS_REPROJ1 6          /* :375 / :386 */
+#define COEB_NEWPTS_REPROJ2 7          /* :401 / :412 */
+#define COEB_NEWPTS_ZERO_DIST 8        /* :423 */
+#define COEB_NEWPTS_RATIO 9            /* :431 */
+/* ... and (status >> 4) & 3 where x3D came from (0 for the first two ways out above and for low parallax) */
+#define COEB_NEWPTS_SRC_TRIANGULATED 1 /* :321-340 */
+#define COEB_NEWPTS_SRC_STEREO1 2      /* :343, pKF1->UnprojectStereo(idx1) */
+#define COEB_NEWPTS_SRC_STEREO2 3      /* :347, pKF2->UnprojectStereo(idx2) */
+/* SearchForTriangulation(pKF1 = slot1, pKF2 = slots2[j], F12[j], vMatchedIndices, only_stereo) of an
+ * ORBmatcher(0.6, false) and then :285-433 on its pairs, for every neighbour j < nnb (nnb <= 32) in one
+ * upload, one download and one synchronisation.  view1 / views2[j] are the caller's poses and cameras;
+ * ratioFactor = 1.5f * mfScaleFactor, mvScaleFactors and mvLevelSigma2 are the context's.  The search's
+ * arguments are coeb_kfdb_search_triangulation's, without check_orientation.  Dense and neighbour-major, n1
+ * entries per neighbour:
+ *   match_out[j][i]  what coeb_kfdb_search_triangulation returns with check_orientation = 0;
+ *   status[j][i]     above; a pure function of the pair, whatever other neighbours decide;
+ *   x3d[j][i][3]     x3D of an accepted pair, untouched for every other entry;
+ *   first_ok[i]      the lowest j with (status & 15) == COEB_NEWPTS_ACCEPTED, else -1: a feature that got its
+ *                    MapPoint from an earlier neighbour is skipped by the later ones, so the host creates
+ *                    MapPoints for exactly the pairs (first_ok[i], i) in (j, i) ascending order;
+ *   nmatches[j]      the pairs of neighbour j.
+ * The null vector of the 4x4 system is a one-sided Jacobi's in float32, a canonical form that differs from
+ * cv::SVD by construction, and the stereo parallax bound cos(2 atan2(mb / 2, depth)) is evaluated as
+ * (d^2 - h^2) / (d^2 + h^2) in double; the float forms are listed in DESIGN.md s2.1 and parity against the
+ * reference binary is UNPINNED.
+ * COEB_EINVAL, with nothing written: the refusals of coeb_kfdb_search_triangulation; a slot without
+ * geometry or stereo data; a pose or camera entry that is not finite; a stored feature with u_right >= 0 and
+ * depth <= 0 (UnprojectStereo returns an empty Mat there); a repeated neighbour slot or slots2[j] == slot1.
+ * nnb == 0 or a keyframe 1 without features: COEB_OK, counts 0, first_ok all -1. */
+int coeb_kfdb_create_new_map_points(coeb_kfdb* db, int slot1, const coeb_kf_view* view1, const uint8_t* has_mp1,
+                                    const int32_t* slots2, int nnb, const coeb_kf_view* views2,
+                                    const uint8_t* const* has_mp2, const float* F12, const float* epipole,
+                                    int only_stereo, int32_t* match_out, int8_t* status, float* x3d,
+                                    int32_t* first_ok, int32_t* nmatches);
 
 /* ---- ORBmatcher::Fuse's search against many stored keyframes (src/ORBmatcher.cc:826-951, the loops of
  * LocalMapping::SearchInNeighbors, src/LocalMapping.cc:455-535) ----
